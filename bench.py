@@ -10,6 +10,12 @@
   python bench.py --config 3                                          (configs[3]: 8 shards of 4096 frames; --gpus 8 = one shard per
                                                                        GPU + RCCL gather, --gpus 1 = the 8 shards as 8 contexts on one GPU)
   python bench.py --gpus 2 --backend gloo --dry                       (launcher / sharding / exchange check without a GPU)
+  python bench.py --gpus 1 --steps K --warmup W --full                (+ per-kernel roofline, shader clock, CPU baseline,
+                                                                       PCIe-inclusive host legs and the workload checks)
+  python bench.py ... --dump-outputs DIR                              (the last timed step's records as DIR/*.npy)
+
+A plain run sets up, warms up, times the K steps and prints the line (metric, value, unit, higher_is_better, dtype,
+ms_per_step, ...); everything else it can measure or check runs only with --full.
 
 A step = one pass of the whole decode path (waterfall FFT -> Costas sync -> LLR -> LDPC BP -> CRC ->
 unpack -> dedup/spots) over the rank's batch of synthetic 15 s frames, resident in HBM before the
@@ -55,6 +61,33 @@ CONFIGS = {
                   "SNR U[{lo:g},{hi:g}] dB, K_MAX_CANDIDATES x4 = {C}, full pipeline incl. HIP LDPC(174,91) BP"),
 }
 
+DUMP_MAX_FRAMES = 8192                   # --dump-outputs writes 6 416 B per frame: 52.6 MB at most
+
+
+def dump_outputs(path, records, counts):
+    """--dump-outputs: what a caller of the timed path received from its last step, as .npy files in `path`:
+      records.npy      [frames, 50, 28] float32  every byte of the caller's record array (RESULT_DTYPE slots: call, loc, freq, snr;
+                                                 slots past the count hold what the array held before, zeros here)
+      freq.npy, snr.npy  [frames, 50] float64    the two integer fields of every slot
+      n_results.npy    [frames] float64          messages per frame
+      frame_index.npy  [frames] float64          the frame each row is (rows are all frames, or a sorted sample of them)
+    Beyond DUMP_MAX_FRAMES frames a fixed, seeded sample of the frames is written, the same on every run."""
+    import rtlsdr_ft8d_amd as ft8
+    counts = np.asarray(counts)
+    rec = np.ascontiguousarray(records).view(np.uint8).reshape(len(counts), ft8.MAX_MESSAGES, ft8.RESULT_DTYPE.itemsize)
+    idx = np.arange(len(counts))
+    if len(idx) > DUMP_MAX_FRAMES:
+        idx = np.sort(np.random.default_rng(0).choice(len(idx), DUMP_MAX_FRAMES, replace=False))
+    rec = np.ascontiguousarray(rec[idx])
+    slots = rec.view(ft8.RESULT_DTYPE).reshape(len(idx), ft8.MAX_MESSAGES)
+    arrays = {"records": rec.astype(np.float32), "freq": slots["freq"].astype(np.float64), "snr": slots["snr"].astype(np.float64),
+              "n_results": counts[idx].astype(np.float64), "frame_index": idx.astype(np.float64)}
+    os.makedirs(path, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(path, name + ".npy"), a)
+    return {"dir": path, "frames": int(len(idx)), "of_frames": int(len(counts)), "bytes": int(sum(a.nbytes for a in arrays.values())),
+            "files": sorted(name + ".npy" for name in arrays)}
+
 
 def csrc_hash():
     """identity of the kernel sources the committed PMC summaries were collected on: the device half of the library's
@@ -73,9 +106,15 @@ def parse_args(argv=None):
     ap.add_argument("--nsig", type=int, default=None, help="FT8 signals per frame")
     ap.add_argument("--snr", type=float, nargs=2, default=None)
     ap.add_argument("--max-candidates", type=int, default=None)
-    ap.add_argument("--cpu-frames", type=int, default=2048, help="frames timed on the host CPU (0 = skip)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-host-legs", action="store_true", help="skip the PCIe-inclusive end-to-end legs (host-fed decode, raw-capture replay)")
+    ap.add_argument("--full", action="store_true",
+                    help="besides the headline: the per-kernel stage timings and roofline, the shader clock / power sampler, the workload "
+                         "checks (messages and CQ spots per frame), the CPU baseline and the PCIe-inclusive host legs; a plain run does none of it")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps write what the last one computed (spot records and counts) as float32 / float64 .npy files to "
+                         "DIR (a fixed, seeded sample of frames beyond %d frames: at most 64 MB in all)" % DUMP_MAX_FRAMES)
+    ap.add_argument("--cpu-frames", type=int, default=2048, help="--full: frames timed on the host CPU (0 = skip)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU baseline")
+    ap.add_argument("--no-host-legs", action="store_true", help="--full: skip the PCIe-inclusive end-to-end legs (host-fed decode, raw-capture replay)")
     ap.add_argument("--force-dist", action="store_true",
                     help="initialise RCCL and run the spot all-gather even with one rank (exercises the N>1 code path on one GPU)")
     ap.add_argument("--backend", choices=("nccl", "gloo"), default="nccl", help="process-group backend (nccl = RCCL; gloo only with --dry)")
@@ -92,7 +131,8 @@ def parse_args(argv=None):
                          "0.1 s after idle -- a 60 s run of the same loop was 2.2 %% faster than the 80 ms timed region that preceded it on one box, "
                          "equal on another (profiles/r06_bench_sustained_60s*.json) -- so the timed region starts from the state a replay job "
                          "runs in; the steps actually run are reported as prewarm_steps")
-    ap.add_argument("--no-clock-sampler", action="store_true", help="do not poll the GPU's sysfs clock / power files during the timed region")
+    ap.add_argument("--no-clock-sampler", action="store_true",
+                    help="do not poll the GPU's sysfs clock / power files (during the timed region with --full, during --sustain-seconds)")
     ap.add_argument("--ctx-last", action="store_true",
                     help="create the decoder context AFTER the process group and a handful of framework streams (round 3 lost 0.27 ms per step "
                          "that way: streams shared hardware queues; the context now measures co-execution and re-rolls its side streams)")
@@ -156,9 +196,9 @@ def self_launch(args):
         sys.stderr.write(f"\nbench.py: the {args.gpus}-rank job failed (exit {p.returncode}, JSON line {'found' if line else 'missing'})\n")
         for ln in p.stdout.splitlines():            # the diagnosis a failing or hanging rank (or its watchdog) left: relay every such line
             if ln.startswith('{"metric"') and '"failed": true' in ln:
-                print(ln, flush=True)
+                emit(ln)
         raise SystemExit(p.returncode or 1)
-    print(line, flush=True)
+    emit(line)
     raise SystemExit(0)
 
 
@@ -287,6 +327,16 @@ def store_collect(store, prefix, world, wait_s=0.0):
         except Exception:
             continue
     return res
+
+
+def emit(line):
+    """print ONE JSON line as ONE write on stdout.  The ranks of a job share the pipe, and under torch.distributed.run their
+    stdout is unbuffered: there print() writes the text and its newline separately, and another rank's line can land in
+    between (two objects on one line, the newline later)."""
+    sys.stdout.flush()
+    data = (line + "\n").encode()
+    while data:
+        data = data[os.write(sys.stdout.fileno(), data):]
 
 
 def failure_line(out, rank, world, phase, exc, store, extra=None):
@@ -586,6 +636,8 @@ def main():
         raise SystemExit("--config 1 (CPU LDPC) is a single-GPU configuration")
     if args.backend == "gloo" and not args.dry:
         raise SystemExit("--backend gloo is only meaningful with --dry (the product path has no CPU form)")
+    if args.dump_outputs and args.dry:
+        raise SystemExit("--dump-outputs writes what the decode path computed: --dry runs none")
     total = B * world
     lo, hi = workload.shard_range(total, rank, world)
     assert hi - lo == B
@@ -612,9 +664,9 @@ def main():
         if rank == 0 and out.get("value") is not None:
             # the timed region was complete and reduced: the measurement stands, the error is reported beside it
             out.update({"completed": False, "error_after_timing": f"{type(exc).__name__}: {exc}"[:1000], "error_phase": wd.current})
-            print(json.dumps(out), flush=True)
+            emit(json.dumps(out))
         else:
-            print(failure_line(out, rank, world, wd.current, exc, ctl["store"], extra), flush=True)
+            emit(failure_line(out, rank, world, wd.current, exc, ctl["store"], extra))
         wd.done()
         sys.stdout.flush()
         sys.stderr.flush()
@@ -647,7 +699,7 @@ def main():
             die(e)
         wd.done()
         if rank == 0:
-            print(json.dumps(out), flush=True)
+            emit(json.dumps(out))
         raise SystemExit(0 if ok else 1)
 
     enter("create_context")
@@ -745,7 +797,7 @@ def main():
     if args.config == 3 and world == 1:
         run_config3_one_gpu(args, out, B, nsig, snr, maxc, dev)
         wd.done()
-        print(json.dumps(out), flush=True)
+        emit(json.dumps(out))
         return
 
     # The decoder keeps its OWN stream (its main / side streams are created together and sit on distinct hardware
@@ -769,7 +821,7 @@ def main():
         run_config1(args, out, dec, iq, B, maxc, stream, dev)
         dec.close()
         wd.done()
-        print(json.dumps(out), flush=True)
+        emit(json.dumps(out))
         return
 
     # spot records: two buffers per rank; the exchange of step k (one asynchronous RCCL all-gather of
@@ -805,8 +857,8 @@ def main():
         torch.cuda.synchronize()
 
     try:
-        # the clock / power sampler starts before the warm-up so that its thread start-up does not land in the first timed step
-        with ClockSampler(local_rank, not args.no_clock_sampler) as clk:
+        # the clock / power sampler (--full) starts before the warm-up so that its thread start-up does not land in the first timed step
+        with ClockSampler(local_rank, args.full and not args.no_clock_sampler) as clk:
             enter("warmup_with_exchange" if exchange else "warmup")
             n_pre = args.prewarm
             for _ in range(args.prewarm):
@@ -832,7 +884,8 @@ def main():
                 step()
             fence()
             enter("timed_steps", args.dist_timeout + 60.0)
-            dec.enable_timing(True)          # stage events are recorded on the stream, read after the fence
+            if args.full:
+                dec.enable_timing(True)      # stage events are recorded on the stream, read after the fence
             clk.clear()
             t0 = time.perf_counter()
             step_ev[0].record(stream)
@@ -846,9 +899,10 @@ def main():
                 t_kernels = time.perf_counter() - t0
             fence()
             elapsed = time.perf_counter() - t0
-        stage_avg = dec.timings()        # mean over the timed steps (ring of the last 32)
-        timed_runs = stage_avg.pop("runs")
-        dec.enable_timing(False)
+        if args.full:
+            stage_avg = dec.timings()    # mean over the timed steps (ring of the last 32)
+            timed_runs = stage_avg.pop("runs")
+            dec.enable_timing(False)
         spots, nres = exch.buffers(state["k"] - 1) if state["k"] > 0 else (spots, nres)    # the last step's local records
         per_step = [step_ev[i].elapsed_time(step_ev[i + 1]) for i in range(args.steps)]
 
@@ -891,20 +945,25 @@ def main():
         out["step_ms"] = {"min": round(min(per_step), 4), "median": round(float(np.median(per_step)), 4), "max": round(max(per_step), 4),
                           "slowest_step_index": int(np.argmax(per_step)),
                           "note": "hipEvent time between consecutive steps' last kernels on rank 0's stream"}
-        out["gpu_clock"] = clk.summary()
-        if (out["gpu_clock"] or {}).get("power_w_median"):
-            # hwmon's socket power is a moving average with a time constant of a fraction of a second: over a timed region of
-            # K x 4 ms that follows 0.1 s of warm-up from idle it still reads hundreds of watts low (round 5 quoted 889 W from here;
-            # a 60 s run of the same loop reads 1 380 W, --sustain-seconds).  Energy per frame is therefore reported there only.
-            out["gpu_clock"]["power_note"] = "moving average, lags a burst this short: read sustained.power_w (--sustain-seconds) for the power this loop draws"
         out["prewarm_steps"] = n_pre               # untimed, before the W warm-up steps (clock settling after idle; see --prewarm-seconds)
         out["prewarm_seconds"] = args.prewarm_seconds
-        out["config"]["decoded_messages_per_frame"] = round(float(nres.cpu().numpy().mean()), 2)
-        # slots the path wrote (messages whose first token starts with "CQ", rtlsdr_ft8d.c:1509-1519); the other messages are
-        # counted in n_results and leave their slot as the caller's array had it (zeros here)
-        rec = spots.view(B, ft8.MAX_MESSAGES, 28)
-        used = torch.arange(ft8.MAX_MESSAGES, device=dev)[None, :] < nres[:, None]
-        out["config"]["cq_spots_per_frame"] = round(float(((rec != 0).any(dim=2) & used).sum().item()) / B, 2)
+        if args.dump_outputs and rank == 0:
+            # what a caller receives from the last timed step: the whole job's gathered list where there is one, else the local records
+            rs, rc = exch.gathered(state["k"] - 1) if exchange and world > 1 else (spots, nres)
+            out["dumped_outputs"] = dump_outputs(args.dump_outputs, rs.cpu().numpy(), rc.cpu().numpy())
+        if args.full:
+            out["gpu_clock"] = clk.summary()
+            if (out["gpu_clock"] or {}).get("power_w_median"):
+                # hwmon's socket power is a moving average with a time constant of a fraction of a second: over a timed region of
+                # K x 4 ms that follows 0.1 s of warm-up from idle it still reads hundreds of watts low (round 5 quoted 889 W from here;
+                # a 60 s run of the same loop reads 1 380 W, --sustain-seconds).  Energy per frame is therefore reported there only.
+                out["gpu_clock"]["power_note"] = "moving average, lags a burst this short: read sustained.power_w (--sustain-seconds) for the power this loop draws"
+            out["config"]["decoded_messages_per_frame"] = round(float(nres.cpu().numpy().mean()), 2)
+            # slots the path wrote (messages whose first token starts with "CQ", rtlsdr_ft8d.c:1509-1519); the other messages are
+            # counted in n_results and leave their slot as the caller's array had it (zeros here)
+            rec = spots.view(B, ft8.MAX_MESSAGES, 28)
+            used = torch.arange(ft8.MAX_MESSAGES, device=dev)[None, :] < nres[:, None]
+            out["config"]["cq_spots_per_frame"] = round(float(((rec != 0).any(dim=2) & used).sum().item()) / B, 2)
         if rank == 0:
             wd.result(out)
         if exchange and world > 1:
@@ -937,7 +996,7 @@ def main():
             raise
         die(e, {"decode_only": decode_only, "steps_launched": state["k"]})
     enter("report", max(args.dist_timeout, 600.0))
-    if rank == 0:
+    if rank == 0 and args.full:
         launches = int(stage_avg.pop("launches_per_stage", 1))
         kernels = {k: v for k, v in stage_avg.items() if k != "total_ms"}
         dom = max(kernels, key=kernels.get)
@@ -994,7 +1053,7 @@ def main():
             ctypes.CDLL(None).fflush(None)
         except OSError:
             pass
-        print(json.dumps(out), flush=True)          # the one JSON line, after any library banners
+        emit(json.dumps(out))          # the one JSON line, after any library banners
 
 
 def run_config3_one_gpu(args, out, B, nsig, snr, maxc, dev):
@@ -1033,6 +1092,8 @@ def run_config3_one_gpu(args, out, B, nsig, snr, maxc, dev):
     elapsed = time.perf_counter() - t0
     out["value"] = round(total * args.steps / elapsed, 1)
     out["ms_per_step"] = round(1e3 * elapsed / args.steps, 3)
+    if args.dump_outputs:
+        out["dumped_outputs"] = dump_outputs(args.dump_outputs, decodes, n)
     out["step_ms"] = {"min": round(min(per_step), 3), "median": round(float(np.median(per_step)), 3), "max": round(max(per_step), 3)}
     out["config"].update({"global_frames": total, "shards": S, "parallelism": f"{S} contexts on one GPU, host threads, host-side gather (D2H of the records inside the step)",
                           "decoded_messages_per_frame": round(float(n.mean()), 2)})
@@ -1111,6 +1172,8 @@ def run_config1(args, out, dec, iq, B, maxc, stream, dev):
     stage = {k: v / args.steps for k, v in acc.items()}
     out["value"] = round(B * args.steps / elapsed, 1)
     out["ms_per_step"] = round(1e3 * elapsed / args.steps, 3)
+    if args.dump_outputs:
+        out["dumped_outputs"] = dump_outputs(args.dump_outputs, res["dec"], res["n"])
     # BASELINE configs[1] asks for "LDPC on CPU"; the product has no CPU LDPC, so that half is the test oracle and this
     # `value` is bound by it: it is NOT a product rate.  The product's share is roofline.gpu_part_frames_per_s.
     out["value_is_product"] = False

@@ -49,6 +49,36 @@ def build():
     subprocess.check_call(["make", "-s", "-C", ORACLE_DIR])
 
 
+def reference_dir():
+    """a checkout of the reference (rtlsdr-ft8d) this process can read, or None: $FT8_REFERENCE_DIR, else a directory
+    `reference` in any directory above this repository, in $HOME or in the user's home directory"""
+    import pwd
+    cands = [os.environ.get("FT8_REFERENCE_DIR")]
+    d = ROOT
+    while os.path.dirname(d) != d:
+        d = os.path.dirname(d)
+        cands.append(os.path.join(d, "reference"))
+    cands.append(os.path.join(os.path.expanduser("~"), "reference"))
+    try:
+        cands.append(os.path.join(pwd.getpwuid(os.getuid()).pw_dir, "reference"))
+    except KeyError:
+        pass
+    for c in cands:
+        if c and os.access(os.path.join(c, "rtlsdr_ft8d.c"), os.R_OK):
+            return os.path.abspath(c)
+    return None
+
+
+def build_ref():
+    """oracle/_ref (`make -C oracle ref`): the reference's rtlsdr_ft8d.c compiled against include/, for
+    tests/test_boundary_compile.py.  False, and oracle/_ref left as it is, when no checkout of the reference is at hand."""
+    ref = reference_dir()
+    if ref is None:
+        return False
+    subprocess.check_call(["make", "-s", "-C", ORACLE_DIR, "ref", f"REF_DIR={ref}"])
+    return True
+
+
 def lib():
     global _lib
     if _lib is not None:

@@ -7,7 +7,7 @@
 TAG=${TAG:-r06}
 STAGES=${STAGES:-"tests bench prof pmc"}
 OUT=gpurun_out/profiles_$TAG
-mkdir -p $OUT
+mkdir -p $OUT/log    # the bench runs' full output; the summaries sit in $OUT itself
 export TMPDIR=/tmp
 has() { [[ " $STAGES " == *" $1 "* ]]; }
 die_stage() { echo "*** stage '$1' aborted: $2 (profiles/ left untouched)"; }
@@ -60,16 +60,16 @@ if has pmc; then
   fi
 fi
 if has bench; then
-  python bench.py --steps ${STEPS:-20} --warmup 5 > gpurun_out/bench.log 2>&1; tail -1 gpurun_out/bench.log > $OUT/${TAG}_bench.json; cut -c1-400 $OUT/${TAG}_bench.json
-  python bench.py --config 4 --steps 40 --warmup 10 --cpu-frames 128 --no-host-legs > gpurun_out/bench_c4.log 2>&1; tail -1 gpurun_out/bench_c4.log > $OUT/${TAG}_bench_config4.json; cut -c1-300 $OUT/${TAG}_bench_config4.json
+  python bench.py --full --steps ${STEPS:-20} --warmup 5 > $OUT/log/bench.log 2>&1; tail -1 $OUT/log/bench.log > $OUT/${TAG}_bench.json; cut -c1-400 $OUT/${TAG}_bench.json
+  python bench.py --full --config 4 --steps 40 --warmup 10 --cpu-frames 128 --no-host-legs > $OUT/log/bench_c4.log 2>&1; tail -1 $OUT/log/bench_c4.log > $OUT/${TAG}_bench_config4.json; cut -c1-300 $OUT/${TAG}_bench_config4.json
   python bench.py --config 1 --steps 5 --warmup 1 > gpurun_out/bench_c1.log 2>&1; tail -1 gpurun_out/bench_c1.log > $OUT/${TAG}_bench_config1.json; cut -c1-300 $OUT/${TAG}_bench_config1.json
   python bench.py --config 3 --steps 5 --warmup 2 > gpurun_out/bench_c3.log 2>&1; tail -1 gpurun_out/bench_c3.log > $OUT/${TAG}_bench_config3_one_gpu.json; cut -c1-300 $OUT/${TAG}_bench_config3_one_gpu.json
-  python bench.py --steps 20 --warmup 5 --no-cpu-baseline --no-host-legs --force-dist > gpurun_out/bench_dist1.log 2>&1; tail -1 gpurun_out/bench_dist1.log > $OUT/${TAG}_bench_rccl_one_rank.json; cut -c1-200 $OUT/${TAG}_bench_rccl_one_rank.json
-  python bench.py --steps 20 --warmup 5 --no-cpu-baseline --no-host-legs --force-dist --ctx-last > gpurun_out/bench_dist1_last.log 2>&1; tail -1 gpurun_out/bench_dist1_last.log > $OUT/${TAG}_bench_rccl_one_rank_ctx_last.json; cut -c1-200 $OUT/${TAG}_bench_rccl_one_rank_ctx_last.json
-  python bench.py --steps 20 --warmup 5 --no-cpu-baseline --no-host-legs --force-dist --no-exchange > gpurun_out/bench_dist1_noex.log 2>&1; tail -1 gpurun_out/bench_dist1_noex.log > $OUT/${TAG}_bench_rccl_one_rank_no_exchange.json; cut -c1-200 $OUT/${TAG}_bench_rccl_one_rank_no_exchange.json
-  python bench.py --steps 20 --warmup 5 --no-cpu-baseline --no-host-legs > gpurun_out/bench_plain2.log 2>&1; tail -1 gpurun_out/bench_plain2.log > $OUT/${TAG}_bench_no_dist_same_session.json; cut -c1-200 $OUT/${TAG}_bench_no_dist_same_session.json
-  python bench.py --steps 20 --warmup 5 --traffic mixed --no-host-legs > gpurun_out/bench_mixed.log 2>&1; tail -1 gpurun_out/bench_mixed.log > $OUT/${TAG}_bench_mixed.json; cut -c1-200 $OUT/${TAG}_bench_mixed.json
-  [ -n "${SUSTAIN:-}" ] && { python bench.py --steps 20 --warmup 5 --no-cpu-baseline --no-host-legs --sustain-seconds $SUSTAIN > gpurun_out/bench_sustain.log 2>&1; tail -1 gpurun_out/bench_sustain.log > $OUT/${TAG}_bench_sustained_${SUSTAIN}s.json; cut -c1-200 $OUT/${TAG}_bench_sustained_${SUSTAIN}s.json; }
+  python bench.py --full --steps 20 --warmup 5 --no-cpu-baseline --no-host-legs --force-dist > $OUT/log/bench_dist1.log 2>&1; tail -1 $OUT/log/bench_dist1.log > $OUT/${TAG}_bench_rccl_one_rank.json; cut -c1-200 $OUT/${TAG}_bench_rccl_one_rank.json
+  python bench.py --full --steps 20 --warmup 5 --no-cpu-baseline --no-host-legs --force-dist --ctx-last > $OUT/log/bench_dist1_last.log 2>&1; tail -1 $OUT/log/bench_dist1_last.log > $OUT/${TAG}_bench_rccl_one_rank_ctx_last.json; cut -c1-200 $OUT/${TAG}_bench_rccl_one_rank_ctx_last.json
+  python bench.py --full --steps 20 --warmup 5 --no-cpu-baseline --no-host-legs --force-dist --no-exchange > $OUT/log/bench_dist1_noex.log 2>&1; tail -1 $OUT/log/bench_dist1_noex.log > $OUT/${TAG}_bench_rccl_one_rank_no_exchange.json; cut -c1-200 $OUT/${TAG}_bench_rccl_one_rank_no_exchange.json
+  python bench.py --full --steps 20 --warmup 5 --no-cpu-baseline --no-host-legs > $OUT/log/bench_plain2.log 2>&1; tail -1 $OUT/log/bench_plain2.log > $OUT/${TAG}_bench_no_dist_same_session.json; cut -c1-200 $OUT/${TAG}_bench_no_dist_same_session.json
+  python bench.py --full --steps 20 --warmup 5 --traffic mixed --no-host-legs > $OUT/log/bench_mixed.log 2>&1; tail -1 $OUT/log/bench_mixed.log > $OUT/${TAG}_bench_mixed.json; cut -c1-200 $OUT/${TAG}_bench_mixed.json
+  [ -n "${SUSTAIN:-}" ] && { python bench.py --full --steps 20 --warmup 5 --no-cpu-baseline --no-host-legs --sustain-seconds $SUSTAIN > $OUT/log/bench_sustain.log 2>&1; tail -1 $OUT/log/bench_sustain.log > $OUT/${TAG}_bench_sustained_${SUSTAIN}s.json; cut -c1-200 $OUT/${TAG}_bench_sustained_${SUSTAIN}s.json; }
   [ -f tools/ab/libft8gpu_r05.so ] && { python tools/ab_libs.py --libs tools/ab/libft8gpu_r05.so rtlsdr_ft8d_amd/libft8gpu.so --rounds 3 > gpurun_out/ab_r05.log 2>&1; tail -1 gpurun_out/ab_r05.log > $OUT/${TAG}_ab_r05_vs_${TAG}.json; cut -c1-300 $OUT/${TAG}_ab_r05_vs_${TAG}.json; }
   python -m torch.distributed.run --nnodes=1 --nproc-per-node 1 --master-addr 127.0.0.1 --master-port 29544 bench.py --gpus 1 --steps 5 --warmup 2 --no-cpu-baseline --no-host-legs > gpurun_out/bench_torchrun1.log 2>&1; tail -1 gpurun_out/bench_torchrun1.log | cut -c1-200
 fi
