@@ -238,6 +238,54 @@ int ft8gpu_collect_spots(ft8gpu_ctx *ctx, const ft8gpu_candidate *cands, const i
                          const ft8gpu_decode_status *status, int nframes,
                          struct decoder_results *decodes, int32_t *n_results, int flags);
 
+/* ---- every decoded message with SNR, time offset and frequency (a second output path beside the reference's) ----------
+ * ft8gpu_decode_batch keeps the reference's contract: only CQ messages reach a record, and decoder_results.snr is the sync
+ * score (rtlsdr_ft8d.c:1509-1520; the reference itself notes "score != snr", :1517).  The entries below number the unique
+ * messages of a frame exactly as that path does (:1487-1520, the same dedup, order and cap of 50, so n_msgs[f] ==
+ * n_results[f] for the same input and parameters) and write one record for EVERY one of them, CQ or not. */
+typedef struct {
+    char     text[25];       /*  0  message_t.text, as the LDPC kernel unpacked it (== ft8gpu_decode_status.text) */
+    int8_t   snr_db;         /* 25  estimated SNR in 2500 Hz, integer dB, [-30, 49] (DESIGN.md "Every decoded message") */
+    int16_t  score;          /* 26  sync score: what decoder_results.snr carries */
+    float    freq_hz;        /* 28  (freq_offset + (float)freq_sub / 2) * 6.25f, rtlsdr_ft8d.c:1470, before the int cast */
+    float    dt_s;           /* 32  (time_offset + (float)time_sub / 2) / 6.25f, the formula of rtlsdr_ft8d.c:1471, in float */
+    uint16_t hash;           /* 36  message.hash (crc_extracted) */
+    uint16_t cand_index;     /* 38  index in the frame's candidate list of the first candidate that carried the message */
+    ft8gpu_candidate cand;   /* 40  that candidate */
+    uint8_t  a91[12];        /* 48  its packed payload + CRC */
+    uint8_t  pad[4];         /* 60  zero */
+} ft8gpu_message;
+#ifndef __cplusplus
+_Static_assert(sizeof(ft8gpu_message) == 64, "ft8gpu_message is 64 bytes");
+_Static_assert(offsetof(ft8gpu_message, snr_db) == 25 && offsetof(ft8gpu_message, score) == 26 &&
+               offsetof(ft8gpu_message, freq_hz) == 28 && offsetof(ft8gpu_message, dt_s) == 32 &&
+               offsetof(ft8gpu_message, hash) == 36 && offsetof(ft8gpu_message, cand_index) == 38 &&
+               offsetof(ft8gpu_message, cand) == 40 && offsetof(ft8gpu_message, a91) == 48 &&
+               offsetof(ft8gpu_message, pad) == 60, "ft8gpu_message field offsets");
+#else
+static_assert(sizeof(ft8gpu_message) == 64, "ft8gpu_message is 64 bytes");
+static_assert(offsetof(ft8gpu_message, snr_db) == 25 && offsetof(ft8gpu_message, score) == 26 &&
+              offsetof(ft8gpu_message, freq_hz) == 28 && offsetof(ft8gpu_message, dt_s) == 32 &&
+              offsetof(ft8gpu_message, hash) == 36 && offsetof(ft8gpu_message, cand_index) == 38 &&
+              offsetof(ft8gpu_message, cand) == 40 && offsetof(ft8gpu_message, a91) == 48 &&
+              offsetof(ft8gpu_message, pad) == 60, "ft8gpu_message field offsets");
+#endif
+/* The whole path for a batch, host or device pointers, chunked by max_frames like ft8gpu_decode_batch.
+ * msgs: [nframes][50], n_msgs: [nframes].  Frame f gets its unique messages in the reference's order in slots
+ * 0..n_msgs[f]-1; slots n_msgs[f]..49 are left untouched.  ft8gpu_enable_timing: spots_ms then holds the noise
+ * baseline and message kernels. */
+int ft8gpu_decode_messages(ft8gpu_ctx *ctx, const float *iq, int nframes, ft8gpu_message *msgs, int32_t *n_msgs, int flags);
+/* stage entry, the counterpart of ft8gpu_collect_spots: mag [nframes][94208], cands / status [nframes][max_candidates],
+ * counts [nframes] -> msgs [nframes][50], n_msgs [nframes] */
+int ft8gpu_collect_messages(ft8gpu_ctx *ctx, const uint8_t *mag, const ft8gpu_candidate *cands, const int32_t *counts,
+                            const ft8gpu_decode_status *status, int nframes, ft8gpu_message *msgs, int32_t *n_msgs, int flags);
+/* per-frame noise floor of the SNR estimate: base[f][fs][j] = the 47th smallest (index 46) of the 184 bytes
+ * mag[f][b][ts][fs][j] over b < 92, ts < 2 (the 25th percentile over time).  base: [nframes][2][256] */
+int ft8gpu_noise_baseline(ft8gpu_ctx *ctx, const uint8_t *mag, int nframes, uint8_t *base, int flags);
+/* one line per message, "%3d %4.1f %4d ~  %s\n" of snr_db, dt_s, (int)freq_hz, text (NUL-terminated, truncated to cap);
+ * returns the untruncated length.  Host-side text formatting, no GPU involved. */
+int ft8gpu_format_messages(const ft8gpu_message *msgs, int32_t n, char *out, size_t cap);
+
 /* ---- tooling: encoder + synthetic frames (pack77 / ft8_encode / CPFSK synth of
  *      decoderSelfTest, rtlsdr_ft8d.c:924-955) --------------------------------------------- */
 /* Message text -> 77 bits in 10 bytes (pack77, :927); 0 = ok, -1 = the text fits no message type.  Tokens are separated

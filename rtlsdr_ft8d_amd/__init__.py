@@ -29,7 +29,11 @@ STATUS_DTYPE = np.dtype([("ldpc_errors", "<i2"), ("iters", "<i2"), ("crc_extract
                          ("a91", "u1", (12,)), ("text", "S25"), ("pad", "u1")])
 SIGNAL_DTYPE = np.dtype([("tones", "u1", (79,)), ("pad", "u1"), ("f0_hz", "<f4"), ("t0_s", "<f4"),
                          ("amplitude", "<f4")])
-assert RESULT_DTYPE.itemsize == 28 and CAND_DTYPE.itemsize == 8
+# ft8gpu_message: every unique message of a frame with SNR estimate, time offset and frequency (ft8gpu_decode_messages)
+MESSAGE_DTYPE = np.dtype({"names": ["text", "snr_db", "score", "freq_hz", "dt_s", "hash", "cand_index", "cand", "a91", "pad"],
+                          "formats": ["S25", "i1", "<i2", "<f4", "<f4", "<u2", "<u2", CAND_DTYPE, ("u1", (12,)), ("u1", (4,))],
+                          "offsets": [0, 25, 26, 28, 32, 36, 38, 40, 48, 60], "itemsize": 64})
+assert RESULT_DTYPE.itemsize == 28 and CAND_DTYPE.itemsize == 8 and MESSAGE_DTYPE.itemsize == 64
 assert STATUS_DTYPE.itemsize == 48 and SIGNAL_DTYPE.itemsize == 92
 
 
@@ -71,6 +75,7 @@ ABI_SYMBOLS = [
     "ft8gpu_overlap_active", "ft8gpu_overlap_reason", "ft8gpu_build_id", "ft8gpu_pack77",
     "ft8gpu_set_debug_flags", "ft8gpu_selftest_bp_math", "ft8gpu_selftest_norm_math", "ft8gpu_gather_spots", "ft8gpu_gather_shutdown",
     "ft8gpu_shard_workers", "ft8gpu_decode_batch_multi", "ft8gpu_decode_batch_multi_dev",
+    "ft8gpu_decode_messages", "ft8gpu_collect_messages", "ft8gpu_noise_baseline", "ft8gpu_format_messages",
     "ft8_find_sync", "ft8_decode", "ft8_encode", "pack77",            # ft8_lib level (include/ft8_lib/ft8/*.h)
     "initFFTW", "freeFFTW", "ft8_subsystem", "ft8gpu_read_raw_iq", "ft8gpu_read_c2", "ft8gpu_write_raw_iq",
 ]
@@ -191,6 +196,11 @@ def _declare(L):
     if hasattr(L, "ft8gpu_gather_spots"):
         L.ft8gpu_gather_spots.argtypes = [C.POINTER(vp), C.c_int, C.POINTER(vp), C.POINTER(vp), C.c_int, C.POINTER(vp), C.POINTER(vp)]
         L.ft8gpu_gather_shutdown.restype = None
+    if hasattr(L, "ft8gpu_decode_messages"):              # absent from older builds loaded by load_library_at
+        L.ft8gpu_decode_messages.argtypes = [vp, vp, C.c_int, vp, vp, C.c_int]
+        L.ft8gpu_collect_messages.argtypes = [vp, vp, vp, vp, vp, C.c_int, vp, vp, C.c_int]
+        L.ft8gpu_noise_baseline.argtypes = [vp, vp, C.c_int, vp, C.c_int]
+        L.ft8gpu_format_messages.argtypes = [vp, C.c_int32, vp, C.c_size_t]
     L.ft8gpu_rx_decimate.argtypes = [vp, vp, C.c_int, C.c_size_t, vp, C.c_int, C.c_int]
     L.ft8gpu_pskreporter_datagrams.argtypes = [vp, vp, vp, C.c_int, C.POINTER(ReportInfo), vp, vp, vp, C.c_int]
     L.ft8gpu_format_spots.argtypes = [vp, C.c_int32, C.c_uint32, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, vp, C.c_size_t]
@@ -409,7 +419,53 @@ class Decoder:
                                              decodes.ctypes.data, n.ctypes.data, HOST_PTRS))
         return decodes, n
 
+    def decode_messages(self, iq, msgs=None):
+        """every unique message of every frame -> (msgs [B][50] MESSAGE_DTYPE, n_msgs [B]); slots past n_msgs[f] keep
+        what `msgs` held (zeros when None)"""
+        iq = np.ascontiguousarray(iq, np.float32)
+        B = iq.shape[0]
+        assert iq.shape[1:] == (2, NSAMPLES)
+        if msgs is None:
+            msgs = np.zeros((B, MAX_MESSAGES), MESSAGE_DTYPE)
+        assert msgs.dtype == MESSAGE_DTYPE and msgs.shape == (B, MAX_MESSAGES) and msgs.flags["C_CONTIGUOUS"]
+        n = np.zeros(B, np.int32)
+        self._ck(self.lib.ft8gpu_decode_messages(self.h, iq.ctypes.data, B, msgs.ctypes.data, n.ctypes.data, HOST_PTRS))
+        return msgs, n
+
+    def collect_messages(self, mag, cands, counts, status, msgs=None):
+        mag = np.ascontiguousarray(mag, np.uint8).reshape(-1, MAG_ARRAY)
+        cands = np.ascontiguousarray(cands)
+        counts = np.ascontiguousarray(counts, np.int32)
+        status = np.ascontiguousarray(status)
+        B = counts.shape[0]
+        assert mag.shape[0] == B and cands.shape == (B, self.max_candidates) and status.shape == (B, self.max_candidates)
+        if msgs is None:
+            msgs = np.zeros((B, MAX_MESSAGES), MESSAGE_DTYPE)
+        assert msgs.dtype == MESSAGE_DTYPE and msgs.shape == (B, MAX_MESSAGES) and msgs.flags["C_CONTIGUOUS"]
+        n = np.zeros(B, np.int32)
+        self._ck(self.lib.ft8gpu_collect_messages(self.h, mag.ctypes.data, cands.ctypes.data, counts.ctypes.data, status.ctypes.data,
+                                                B, msgs.ctypes.data, n.ctypes.data, HOST_PTRS))
+        return msgs, n
+
+    def noise_baseline(self, mag):
+        """the per-frame noise floor of the SNR estimate: uint8 [B][2][256], the 47th smallest of each column"""
+        mag = np.ascontiguousarray(mag, np.uint8).reshape(-1, MAG_ARRAY)
+        B = mag.shape[0]
+        base = np.zeros((B, 2, 256), np.uint8)
+        self._ck(self.lib.ft8gpu_noise_baseline(self.h, mag.ctypes.data, B, base.ctypes.data, HOST_PTRS))
+        return base
+
     # ---- device-pointer API (inputs and outputs resident in HBM) --------------------------------
+    def decode_messages_dev(self, iq_dev, nframes, msgs_dev, n_msgs_dev):
+        self._ck(self.lib.ft8gpu_decode_messages(self.h, _ptr(iq_dev), nframes, _ptr(msgs_dev), _ptr(n_msgs_dev), DEVICE_PTRS))
+
+    def collect_messages_dev(self, mag_dev, cands_dev, counts_dev, status_dev, nframes, msgs_dev, n_msgs_dev):
+        self._ck(self.lib.ft8gpu_collect_messages(self.h, _ptr(mag_dev), _ptr(cands_dev), _ptr(counts_dev), _ptr(status_dev), nframes,
+                                                _ptr(msgs_dev), _ptr(n_msgs_dev), DEVICE_PTRS))
+
+    def noise_baseline_dev(self, mag_dev, nframes, base_dev):
+        self._ck(self.lib.ft8gpu_noise_baseline(self.h, _ptr(mag_dev), nframes, _ptr(base_dev), DEVICE_PTRS))
+
     def decode_batch_dev(self, iq_dev, nframes, decodes_dev, n_results_dev):
         self._ck(self.lib.ft8gpu_decode_batch(self.h, _ptr(iq_dev), nframes, _ptr(decodes_dev), _ptr(n_results_dev),
                                             DEVICE_PTRS))
@@ -573,6 +629,20 @@ def format_spots(decodes, n_results, dial_freq, year, month, mday, hour, minute)
     n = L.ft8gpu_format_spots(decodes.ctypes.data, int(n_results), int(dial_freq), year, month, mday, hour, minute, buf, len(buf))
     if n < 0:
         raise Ft8GpuError("ft8gpu_format_spots failed")
+    return buf.value.decode()
+
+
+def format_messages(msgs, n):
+    """ft8gpu_format_messages: "SNR DT Freq ~ Message", one line per record of msgs[0..n)"""
+    L = load_library()
+    msgs = np.ascontiguousarray(msgs)
+    assert msgs.dtype == MESSAGE_DTYPE
+    n = int(min(n, msgs.size))
+    need = L.ft8gpu_format_messages(msgs.ctypes.data, n, None, 0)
+    if need < 0:
+        raise Ft8GpuError("ft8gpu_format_messages failed")
+    buf = C.create_string_buffer(need + 1)
+    L.ft8gpu_format_messages(msgs.ctypes.data, n, buf, len(buf))
     return buf.value.decode()
 
 

@@ -281,7 +281,7 @@ void ft8gpu_destroy(ft8gpu_ctx *c) {
     void *bufs[] = { c->d_tab, c->d_iq, c->d_mag, c->d_lists, c->d_list_counts, c->d_cands, c->d_counts,
                      c->d_status, c->d_decodes, c->d_nres, c->d_scores, c->d_sigs,
                      c->d_rx_sums, c->d_rx_p2, c->d_rx_raw, c->d_rx_iq,
-                     c->d_rep, c->d_rep_len, c->d_rep_time, c->d_probe };
+                     c->d_rep, c->d_rep_len, c->d_rep_time, c->d_probe, c->d_base, c->d_msgtab, c->d_msgs };
     for (void *b : bufs) if (b) (void)hipFree(b);
     if (c->side) (void)hipStreamSynchronize(c->side);
     for (auto &slot : c->ev) for (auto &e : slot) if (e) (void)hipEventDestroy(e);

@@ -4,6 +4,27 @@
 
 namespace {
 
+// the last stage of the path: the reference's spot collection (ft8gpu_decode_batch), or the noise baseline and the
+// message records (ft8gpu_decode_messages).  Everything before it is the same launch sequence for both.
+struct Tail {
+    struct decoder_results *dec = nullptr;
+    int32_t *nres = nullptr;
+    ft8gpu_message *msgs = nullptr;        // non-null: the messages tail
+    int32_t *nmsgs = nullptr;
+};
+
+int launch_tail(ft8gpu_ctx *c, const Tail &tail, int n) {
+    const ft8gpu_params &p = c->params;
+    if (!tail.msgs) {
+        HIP_TRY(launch_spots(c->d_cands, c->d_counts, c->d_status, n, p.max_candidates, p.min_score, tail.dec, tail.nres, c->stream));
+        return 0;
+    }
+    HIP_TRY(launch_noise_baseline(c->d_mag, c->d_base, n, c->stream));
+    HIP_TRY(launch_messages(c->d_mag, c->d_base, c->d_cands, c->d_counts, c->d_status, c->d_msgtab, n, p.max_candidates, p.min_score,
+                            tail.msgs, tail.nmsgs, c->stream));
+    return 0;
+}
+
 struct StageTimer {
     ft8gpu_ctx *c;
     explicit StageTimer(ft8gpu_ctx *ctx) : c(ctx) {}
@@ -30,7 +51,7 @@ struct StageTimer {
 // heap(A) only sync(B) to hide under.  Measured alternatives, profiles/r02_ab_kernels.json and r03_ab_pipeline.json:
 // equal halves cost 0.1-0.16 ms more; a K-part pipeline with the waterfall of part k+1 beside the LDPC kernel of part k
 // is SLOWER -- the waterfall's large workgroups are not co-scheduled beside the LDPC kernel's small ones.)
-int run_pipeline_overlapped(ft8gpu_ctx *c, const float *d_iq, int n, struct decoder_results *d_dec, int32_t *d_nres) {
+int run_pipeline_overlapped(ft8gpu_ctx *c, const float *d_iq, int n, const Tail &tail) {
     StageTimer t(c);
     const ft8gpu_params &p = c->params;
     const int mc = p.max_candidates;
@@ -95,18 +116,16 @@ int run_pipeline_overlapped(ft8gpu_ctx *c, const float *d_iq, int n, struct deco
     // ONE spot collection for both parts behind the last LDPC launch (the parts' buffers are contiguous).  Until round 4 the
     // spots of part A ran on the side stream beside decode(B); since the kernel takes 27 us for 4096 frames that bought
     // nothing and cost two event hops on the main stream: 4.115 -> 4.077 ms per step in interleaved A/B.
-    HIP_TRY(launch_spots(c->d_cands, c->d_counts, c->d_status, n, mc, p.min_score, d_dec, d_nres, c->stream));
+    if (launch_tail(c, tail, n)) return -1;
     t.mark(7);
     t.mark(8);
     t.done(1);
     return 0;
 }
 
-}  // namespace
-
 // the pipeline on device pointers; all intermediates in the context's HBM buffers
-int run_pipeline(ft8gpu_ctx *c, const float *d_iq, int n, struct decoder_results *d_dec, int32_t *d_nres) {
-    if (c->overlap_ok && !(c->debug_flags & FT8GPU_DBG_NO_OVERLAP) && n >= 512) return run_pipeline_overlapped(c, d_iq, n, d_dec, d_nres);
+int run_pipeline_tail(ft8gpu_ctx *c, const float *d_iq, int n, const Tail &tail) {
+    if (c->overlap_ok && !(c->debug_flags & FT8GPU_DBG_NO_OVERLAP) && n >= 512) return run_pipeline_overlapped(c, d_iq, n, tail);
     StageTimer t(c);
     const ft8gpu_params &p = c->params;
     t.mark(0);
@@ -118,29 +137,47 @@ int run_pipeline(ft8gpu_ctx *c, const float *d_iq, int n, struct decoder_results
     t.mark(3);
     HIP_TRY(launch_decode(c->d_mag, c->d_cands, c->d_counts, c->d_status, n, p.max_candidates, p.ldpc_iters, false, force_ieee(c), c->stream));
     t.mark(4);
-    HIP_TRY(launch_spots(c->d_cands, c->d_counts, c->d_status, n, p.max_candidates, p.min_score, d_dec, d_nres, c->stream));
+    if (launch_tail(c, tail, n)) return -1;
     t.mark(5);
     t.done(0);
     return 0;
 }
 
+}  // namespace
+
+int run_pipeline(ft8gpu_ctx *c, const float *d_iq, int n, struct decoder_results *d_dec, int32_t *d_nres) {
+    Tail tail;
+    tail.dec = d_dec;
+    tail.nres = d_nres;
+    return run_pipeline_tail(c, d_iq, n, tail);
+}
+
+int run_pipeline_messages(ft8gpu_ctx *c, const float *d_iq, int n, ft8gpu_message *d_msgs, int32_t *d_nmsgs) {
+    Tail tail;
+    tail.msgs = d_msgs;
+    tail.nmsgs = d_nmsgs;
+    return run_pipeline_tail(c, d_iq, n, tail);
+}
+
 static constexpr int kHostChunk = 512;      // frames per upload chunk of a host-buffer batch
 
-extern "C" int ft8gpu_decode_batch(ft8gpu_ctx *c, const float *iq, int nframes, struct decoder_results *decodes,
-                        int32_t *n_results, int flags) {
-    CHECK_COMMON(c, nframes);
-    if (nframes == 0) return 0;
-    if (!iq || !decodes || !n_results) return ft8_fail("NULL array argument");
+namespace {
+
+// the pipeline over a batch of any size, host or device pointers: Rec is struct decoder_results (the reference's spot
+// list) or ft8gpu_message (every unique message); both leave the slots they do not write as the caller had them
+template <class Rec>
+int decode_frames(ft8gpu_ctx *c, const float *iq, int nframes, Rec *recs, int32_t *counts, int flags, Rec *d_stage, int32_t *d_counts,
+                  int (*run)(ft8gpu_ctx *, const float *, int, Rec *, int32_t *)) {
     const size_t frame_floats = 2 * (size_t)kNSamples;
     for (int f0 = 0; f0 < nframes; f0 += c->max_frames) {
         const int n = (nframes - f0 < c->max_frames) ? nframes - f0 : c->max_frames;
         if (flags & FT8GPU_DEVICE_PTRS) {
-            if (run_pipeline(c, iq + f0 * frame_floats, n, decodes + (size_t)f0 * kMaxMessages, n_results + f0)) return -1;
+            if (run(c, iq + f0 * frame_floats, n, recs + (size_t)f0 * kMaxMessages, counts + f0)) return -1;
         } else {
             if (!c->d_iq) HIP_TRY(hipMalloc(&c->d_iq, (size_t)c->max_frames * frame_floats * sizeof(float)));
-            // slots of non-CQ messages must keep the caller's bytes (rtlsdr_ft8d.c:1509-1520)
-            HIP_TRY(hipMemcpyAsync(c->d_decodes, decodes + (size_t)f0 * kMaxMessages,
-                                   (size_t)n * kMaxMessages * sizeof(struct decoder_results), hipMemcpyHostToDevice, c->stream));
+            // slots the path does not write must keep the caller's bytes (rtlsdr_ft8d.c:1509-1520)
+            HIP_TRY(hipMemcpyAsync(d_stage, recs + (size_t)f0 * kMaxMessages,
+                                   (size_t)n * kMaxMessages * sizeof(Rec), hipMemcpyHostToDevice, c->stream));
             // the upload is 384 KB per frame and takes longer than the decode: pipeline it in chunks on a
             // copy stream so that the kernels of chunk k run under the upload of chunk k+1
             const int chunk = (n > kHostChunk && !(c->debug_flags & FT8GPU_DBG_NO_OVERLAP)) ? kHostChunk : n;
@@ -156,15 +193,35 @@ extern "C" int ft8gpu_decode_batch(ft8gpu_ctx *c, const float *iq, int nframes, 
                     HIP_TRY(hipEventRecord(e, up));
                     HIP_TRY(hipStreamWaitEvent(c->stream, e, 0));
                 }
-                if (run_pipeline(c, c->d_iq + g0 * frame_floats, m, c->d_decodes + (size_t)g0 * kMaxMessages, c->d_nres + g0)) return -1;
+                if (run(c, c->d_iq + g0 * frame_floats, m, d_stage + (size_t)g0 * kMaxMessages, d_counts + g0)) return -1;
             }
-            HIP_TRY(hipMemcpyAsync(decodes + (size_t)f0 * kMaxMessages, c->d_decodes,
-                                   (size_t)n * kMaxMessages * sizeof(struct decoder_results), hipMemcpyDeviceToHost, c->stream));
-            HIP_TRY(hipMemcpyAsync(n_results + f0, c->d_nres, n * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
+            HIP_TRY(hipMemcpyAsync(recs + (size_t)f0 * kMaxMessages, d_stage,
+                                   (size_t)n * kMaxMessages * sizeof(Rec), hipMemcpyDeviceToHost, c->stream));
+            HIP_TRY(hipMemcpyAsync(counts + f0, d_counts, n * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
             HIP_TRY(hipStreamSynchronize(c->stream));
         }
     }
     return 0;
+}
+
+}  // namespace
+
+extern "C" int ft8gpu_decode_batch(ft8gpu_ctx *c, const float *iq, int nframes, struct decoder_results *decodes,
+                        int32_t *n_results, int flags) {
+    CHECK_COMMON(c, nframes);
+    if (nframes == 0) return 0;
+    if (!iq || !decodes || !n_results) return ft8_fail("NULL array argument");
+    return decode_frames(c, iq, nframes, decodes, n_results, flags, c->d_decodes, c->d_nres, run_pipeline);
+}
+
+extern "C" int ft8gpu_decode_messages(ft8gpu_ctx *c, const float *iq, int nframes, ft8gpu_message *msgs, int32_t *n_msgs, int flags) {
+    CHECK_COMMON(c, nframes);
+    if (nframes == 0) return 0;
+    if (!iq || !msgs || !n_msgs) return ft8_fail("NULL array argument");
+    if (ensure_messages_buffers(c)) return -1;
+    if (!(flags & FT8GPU_DEVICE_PTRS) && !c->d_msgs)
+        HIP_TRY(hipMalloc(&c->d_msgs, (size_t)c->max_frames * kMaxMessages * sizeof(ft8gpu_message)));
+    return decode_frames(c, iq, nframes, msgs, n_msgs, flags, c->d_msgs, c->d_nres, run_pipeline_messages);
 }
 
 // frames resident on the context's GPU, records to host arrays (used by the multi-GPU entry)

@@ -340,3 +340,15 @@ int ft8gpu_format_spots(const struct decoder_results *decodes, int32_t n_results
                                           (int)((uint32_t)decodes[i].freq + dial_freq), decodes[i].call, decodes[i].loc));
     return (int)at;
 }
+
+/* every decoded message, one line each: "SNR DT Freq ~ Message" as the list the reference never printed (:1462) */
+int ft8gpu_format_messages(const ft8gpu_message *msgs, int32_t n, char *out, size_t cap) {
+    char line[96];
+    size_t at = 0;
+    if (out && cap) out[0] = 0;
+    if (n > 0 && !msgs) return -1;
+    for (int32_t i = 0; i < n && i < FT8GPU_K_MAX_MESSAGES; i++)
+        emit(out, cap, &at, line, snprintf(line, sizeof line, "%3d %4.1f %4d ~  %.25s\n", msgs[i].snr_db, (double)msgs[i].dt_s,
+                                          (int)msgs[i].freq_hz, msgs[i].text));
+    return (int)at;
+}

@@ -55,6 +55,9 @@ struct ft8gpu_ctx {
     struct decoder_results *d_decodes = nullptr;
     int32_t *d_nres = nullptr;
     int16_t *d_scores = nullptr;           // lazily allocated (diagnostic)
+    uint8_t *d_base = nullptr;             // messages path, lazily allocated on its first call: noise baseline [max_frames][512]
+    MsgTables *d_msgtab = nullptr;         //   its constant tables
+    ft8gpu_message *d_msgs = nullptr;      //   host-pointer staging of the records [max_frames][50]
     ft8gpu_synth_signal *d_sigs = nullptr;
     size_t sigs_cap = 0;
     void *d_rx_sums = nullptr, *d_rx_p2 = nullptr;     // RX front end scratch
@@ -93,6 +96,10 @@ inline int force_ieee(const ft8gpu_ctx *c) { return (c->debug_flags & FT8GPU_DBG
 int probe_streams(ft8gpu_ctx *c);             // (re)establishes c->overlap_ok for the current main stream
 // api_pipeline.hip: the whole path on device pointers; all intermediates in the context's HBM buffers
 int run_pipeline(ft8gpu_ctx *c, const float *d_iq, int n, struct decoder_results *d_dec, int32_t *d_nres);
+// the same with the messages tail: noise baseline + message records instead of the spot collection
+int run_pipeline_messages(ft8gpu_ctx *c, const float *d_iq, int n, ft8gpu_message *d_msgs, int32_t *d_nmsgs);
+// api_messages.hip: allocates d_base / d_msgtab on the first messages call
+int ensure_messages_buffers(ft8gpu_ctx *c);
 // frames resident on the context's GPU, records to host arrays (used by the multi-GPU entries)
 int decode_dev_to_host(ft8gpu_ctx *c, const float *d_iq, int nframes, struct decoder_results *decodes, int32_t *n_results);
 // api_glue.hip: (re)allocates *buf when `need` exceeds *cap (the caller has synchronised the stream)

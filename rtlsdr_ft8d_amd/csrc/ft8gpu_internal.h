@@ -64,6 +64,19 @@ hipError_t launch_decode(const uint8_t *mag, const ft8gpu_candidate *cands, cons
 hipError_t launch_spots(const ft8gpu_candidate *cands, const int32_t *counts,
                         const ft8gpu_decode_status *status, int nframes, int max_candidates,
                         int min_score, struct decoder_results *decodes, int32_t *n_results, hipStream_t s);
+// messages.hip: the second output path (every unique message with SNR, DT, frequency).  Constant tables built on the
+// host (api_messages.hip): byte -> power, the SNR decision thresholds, the LDPC generator rows as big-endian words.
+constexpr int kSnrMin = -30, kSnrMax = 49, kSnrSteps = kSnrMax - kSnrMin + 1;
+constexpr int kBaseRank = 46;                                  // noise baseline: the 47th smallest of 184 bytes per column
+struct MsgTables {
+    double   power[256];           // P[v] = 10^((v - 240) / 20)  (byte = 2 dB + 240, rtlsdr_ft8d.c:1418-1425)
+    double   thr[kSnrSteps];       // T[d + 30] = (1 + 10^((d - 0.5 + K) / 10)) / q,  q = -ln(0.75)
+    uint32_t gen[kLdpcM][3];       // kFT8_generator rows, bytes 0..11 as three big-endian words
+};
+hipError_t launch_noise_baseline(const uint8_t *mag, uint8_t *base, int nframes, hipStream_t s);
+hipError_t launch_messages(const uint8_t *mag, const uint8_t *base, const ft8gpu_candidate *cands, const int32_t *counts,
+                           const ft8gpu_decode_status *status, const MsgTables *tab, int nframes, int max_candidates,
+                           int min_score, ft8gpu_message *msgs, int32_t *n_msgs, hipStream_t s);
 hipError_t launch_synth(const ft8gpu_synth_signal *sig_dev, int nframes, int nsig, float noise_sigma,
                         uint64_t seed, uint64_t first_frame, float *iq, hipStream_t s);
 hipError_t run_bp_math_selftest(uint64_t out[7], hipStream_t s);   // bp_selftest.hip: exhaustive check of bp_math.h

@@ -12,41 +12,9 @@
 // ones, and every new message parses its own text and writes its own spot record.  Texts, hashes and
 // candidates are staged in LDS, so the only global traffic is one coalesced fetch per candidate
 // record and the stores of the spot records.
-#include "ft8gpu_internal.h"
+#include "dedup_dev.h"          // wave_lds_sync, kTextDw, canonical_text, text_equal
 
 namespace {
-
-__device__ __forceinline__ void wave_lds_sync() {
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-}
-
-constexpr int kTextDw = 7;                    // message_t.text[25] in 7 aligned dwords (bytes 25..27 are 0)
-
-// Staged texts are kept in CANONICAL form: every byte behind the first NUL is zero (what strcmp never looks at), so
-// strcmp(a, b) == 0 is equality of the seven dwords -- a dozen instructions instead of a 25-step byte loop, and that
-// comparison runs once per (lane, kept message) and once per (lane, unique message of the chunk).  The LDPC kernel
-// writes its texts into zero-filled records, but collect_spots also takes caller-made records: canonicalising here
-// keeps the reference's semantics for any input.
-__device__ __forceinline__ void canonical_text(uint32_t (&w)[kTextDw]) {
-    bool open = true;                               // no terminator seen yet
-#pragma unroll
-    for (int k = 0; k < kTextDw; ++k) {
-        const uint32_t v = open ? w[k] : 0u;
-        const uint32_t z = ~(((v & 0x7F7F7F7Fu) + 0x7F7F7F7Fu) | v) & 0x80808080u;   // 0x80 in every zero byte (exact, no carries between bytes)
-        const uint32_t low = z & (0u - z);          // the first one: 0x80 << 8 i  (0 if none)
-        w[k] = v & ((low >> 7) - 1u);               // bytes below it (all four if none)
-        open = open && z == 0u;
-    }
-}
-// strcmp == 0 between the lane's own text (registers) and a staged one
-__device__ __forceinline__ bool text_equal(const uint32_t (&mine)[kTextDw], const uint32_t *other) {
-    uint32_t d = 0;
-#pragma unroll
-    for (int k = 0; k < kTextDw; ++k) d |= mine[k] ^ other[k];
-    return d == 0u;
-}
 
 // strtok(text, " ") semantics on message_t.text with text[24] taken as the terminator (:1509 works on a
 // NUL-terminated char[25]): returns start index of the next token at or after *pos, or -1; *len
@@ -150,7 +118,8 @@ void ft8_spots_kernel(const ft8gpu_candidate *__restrict__ cands, const int32_t 
         }
         wave_lds_sync();
 
-        // :1487-1503 -- is the message already known?  First against the messages kept from earlier chunks.
+        // :1487-1503 -- is the message already known?  (dedup_chunk of dedup_dev.h is this loop for messages.hip; it stays
+        // written out here because calling it reorders two register initialisations of this kernel's code.)  First against the messages kept from earlier chunks.
         bool dup = false;
         for (int t = 0; t < num_decoded; ++t)
             if (ok && L.thash[t] == my_hash && text_equal(mine, L.ttext[t])) dup = true;
