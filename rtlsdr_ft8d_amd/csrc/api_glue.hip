@@ -114,17 +114,14 @@ int ft8gpu_pskreporter_datagrams(ft8gpu_ctx *c, const struct decoder_results *de
     if (grow_buffer((void **)&c->d_rep, &c->rep_cap, F * FT8GPU_DATAGRAM_STRIDE)) return -1;
     if (grow_buffer((void **)&c->d_rep_len, &c->rep_len_cap, F * sizeof(int32_t))) return -1;
     if (unixtimes && grow_buffer((void **)&c->d_rep_time, &c->rep_time_cap, F * sizeof(uint32_t))) return -1;
-    for (int f0 = 0; f0 < nframes; f0 += c->max_frames) {
-        const int n = (nframes - f0 < c->max_frames) ? nframes - f0 : c->max_frames;
-        HIP_TRY(hipMemcpyAsync(c->d_decodes, decodes + (size_t)f0 * kMaxMessages, (size_t)n * kMaxMessages * sizeof(struct decoder_results), hipMemcpyHostToDevice, c->stream));
-        HIP_TRY(hipMemcpyAsync(c->d_nres, n_results + f0, n * sizeof(int32_t), hipMemcpyHostToDevice, c->stream));
-        if (unixtimes) HIP_TRY(hipMemcpyAsync(c->d_rep_time, unixtimes + f0, n * sizeof(uint32_t), hipMemcpyHostToDevice, c->stream));
-        HIP_TRY(launch_report(c->d_decodes, c->d_nres, n, pre, unixtimes ? c->d_rep_time : nullptr, c->d_rep, c->d_rep_len, c->stream));
-        HIP_TRY(hipMemcpyAsync(datagrams + (size_t)f0 * FT8GPU_DATAGRAM_STRIDE, c->d_rep, (size_t)n * FT8GPU_DATAGRAM_STRIDE, hipMemcpyDeviceToHost, c->stream));
-        HIP_TRY(hipMemcpyAsync(lengths + f0, c->d_rep_len, n * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
-        HIP_TRY(hipStreamSynchronize(c->stream));
-    }
-    return 0;
+    const StageArg a[] = { { decodes, c->d_decodes, kMaxMessages * sizeof(struct decoder_results), kIn },
+                           { n_results, c->d_nres, sizeof(int32_t), kIn }, { unixtimes, c->d_rep_time, sizeof(uint32_t), kIn },
+                           { datagrams, c->d_rep, FT8GPU_DATAGRAM_STRIDE, kOut }, { lengths, c->d_rep_len, sizeof(int32_t), kOut } };
+    return for_each_chunk(c, nframes, flags, a, [&](int n, void *const *p) {
+        HIP_TRY(launch_report((const struct decoder_results *)p[0], (const int32_t *)p[1], n, pre, (const uint32_t *)p[2],
+                              (uint8_t *)p[3], (int32_t *)p[4], c->stream));
+        return 0;
+    });
 }
 
 int ft8gpu_synth_frames(ft8gpu_ctx *c, const ft8gpu_synth_signal *signals, int nframes, int nsig,
@@ -139,12 +136,7 @@ int ft8gpu_synth_frames_at(ft8gpu_ctx *c, const ft8gpu_synth_signal *signals, in
     if (nsig < 0 || nsig > 64) return ft8_fail("nsig_per_frame %d out of range [0, 64]", nsig);
     if (!iq_dev || (nsig > 0 && !signals)) return ft8_fail("NULL array argument");
     const size_t bytes = (size_t)nframes * (nsig > 0 ? nsig : 1) * sizeof(ft8gpu_synth_signal);
-    if (bytes > c->sigs_cap) {
-        if (c->d_sigs) (void)hipFree(c->d_sigs);
-        c->d_sigs = nullptr;
-        HIP_TRY(hipMalloc(&c->d_sigs, bytes));
-        c->sigs_cap = bytes;
-    }
+    if (grow_buffer((void **)&c->d_sigs, &c->sigs_cap, bytes)) return -1;
     if (nsig > 0) HIP_TRY(hipMemcpyAsync(c->d_sigs, signals, (size_t)nframes * nsig * sizeof(ft8gpu_synth_signal), hipMemcpyHostToDevice, c->stream));
     HIP_TRY(launch_synth(c->d_sigs, nframes, nsig, noise_sigma, seed, first_frame, iq_dev, c->stream));
     HIP_TRY(hipStreamSynchronize(c->stream));

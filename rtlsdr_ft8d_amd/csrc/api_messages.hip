@@ -51,19 +51,11 @@ int ft8gpu_noise_baseline(ft8gpu_ctx *c, const uint8_t *mag, int nframes, uint8_
     if (nframes == 0) return 0;
     if (!mag || !base) return ft8_fail("NULL array argument");
     if (ensure_messages_buffers(c)) return -1;
-    const size_t per = 2 * kNumBin;
-    for (int f0 = 0; f0 < nframes; f0 += c->max_frames) {
-        const int n = (nframes - f0 < c->max_frames) ? nframes - f0 : c->max_frames;
-        if (flags & FT8GPU_DEVICE_PTRS) {
-            HIP_TRY(launch_noise_baseline(mag + (size_t)f0 * kMagArray, base + (size_t)f0 * per, n, c->stream));
-        } else {
-            HIP_TRY(hipMemcpyAsync(c->d_mag, mag + (size_t)f0 * kMagArray, (size_t)n * kMagArray, hipMemcpyHostToDevice, c->stream));
-            HIP_TRY(launch_noise_baseline(c->d_mag, c->d_base, n, c->stream));
-            HIP_TRY(hipMemcpyAsync(base + (size_t)f0 * per, c->d_base, (size_t)n * per, hipMemcpyDeviceToHost, c->stream));
-            HIP_TRY(hipStreamSynchronize(c->stream));
-        }
-    }
-    return 0;
+    const StageArg a[] = { { mag, c->d_mag, kMagArray, kIn }, { base, c->d_base, 2 * kNumBin, kOut } };
+    return for_each_chunk(c, nframes, flags, a, [&](int n, void *const *p) {
+        HIP_TRY(launch_noise_baseline((const uint8_t *)p[0], (uint8_t *)p[1], n, c->stream));
+        return 0;
+    });
 }
 
 int ft8gpu_collect_messages(ft8gpu_ctx *c, const uint8_t *mag, const ft8gpu_candidate *cands, const int32_t *counts,
@@ -73,33 +65,18 @@ int ft8gpu_collect_messages(ft8gpu_ctx *c, const uint8_t *mag, const ft8gpu_cand
     if (!mag || !cands || !counts || !status || !msgs || !n_msgs) return ft8_fail("NULL array argument");
     if (ensure_messages_buffers(c)) return -1;
     const int mc = c->params.max_candidates;
-    const bool dev = flags & FT8GPU_DEVICE_PTRS;
-    if (!dev && !c->d_msgs) HIP_TRY(hipMalloc(&c->d_msgs, (size_t)c->max_frames * kMaxMessages * sizeof(ft8gpu_message)));
-    for (int f0 = 0; f0 < nframes; f0 += c->max_frames) {
-        const int n = (nframes - f0 < c->max_frames) ? nframes - f0 : c->max_frames;
-        const uint8_t *dm = dev ? mag + (size_t)f0 * kMagArray : c->d_mag;
-        const ft8gpu_candidate *dc = dev ? cands + (size_t)f0 * mc : c->d_cands;
-        const int32_t *dn = dev ? counts + f0 : c->d_counts;
-        const ft8gpu_decode_status *dst = dev ? status + (size_t)f0 * mc : c->d_status;
-        ft8gpu_message *dmsg = dev ? msgs + (size_t)f0 * kMaxMessages : c->d_msgs;
-        int32_t *dnm = dev ? n_msgs + f0 : c->d_nres;
-        if (!dev) {
-            HIP_TRY(hipMemcpyAsync(c->d_mag, mag + (size_t)f0 * kMagArray, (size_t)n * kMagArray, hipMemcpyHostToDevice, c->stream));
-            HIP_TRY(hipMemcpyAsync(c->d_cands, cands + (size_t)f0 * mc, (size_t)n * mc * sizeof(ft8gpu_candidate), hipMemcpyHostToDevice, c->stream));
-            HIP_TRY(hipMemcpyAsync(c->d_counts, counts + f0, n * sizeof(int32_t), hipMemcpyHostToDevice, c->stream));
-            HIP_TRY(hipMemcpyAsync(c->d_status, status + (size_t)f0 * mc, (size_t)n * mc * sizeof(ft8gpu_decode_status), hipMemcpyHostToDevice, c->stream));
-            // slots past a frame's count keep the caller's bytes
-            HIP_TRY(hipMemcpyAsync(c->d_msgs, msgs + (size_t)f0 * kMaxMessages, (size_t)n * kMaxMessages * sizeof(ft8gpu_message), hipMemcpyHostToDevice, c->stream));
-        }
-        HIP_TRY(launch_noise_baseline(dm, c->d_base, n, c->stream));
-        HIP_TRY(launch_messages(dm, c->d_base, dc, dn, dst, c->d_msgtab, n, mc, c->params.min_score, dmsg, dnm, c->stream));
-        if (!dev) {
-            HIP_TRY(hipMemcpyAsync(msgs + (size_t)f0 * kMaxMessages, c->d_msgs, (size_t)n * kMaxMessages * sizeof(ft8gpu_message), hipMemcpyDeviceToHost, c->stream));
-            HIP_TRY(hipMemcpyAsync(n_msgs + f0, c->d_nres, n * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
-            HIP_TRY(hipStreamSynchronize(c->stream));
-        }
-    }
-    return 0;
+    if (!(flags & FT8GPU_DEVICE_PTRS) && !c->d_msgs) HIP_TRY(hipMalloc(&c->d_msgs, (size_t)c->max_frames * kMaxMessages * sizeof(ft8gpu_message)));
+    // slots past a frame's count keep the caller's bytes; c->d_base is scratch in both forms
+    const StageArg a[] = { { mag, c->d_mag, kMagArray, kIn }, { cands, c->d_cands, mc * sizeof(ft8gpu_candidate), kIn },
+                           { counts, c->d_counts, sizeof(int32_t), kIn }, { status, c->d_status, mc * sizeof(ft8gpu_decode_status), kIn },
+                           { msgs, c->d_msgs, kMaxMessages * sizeof(ft8gpu_message), kInOut }, { n_msgs, c->d_nres, sizeof(int32_t), kOut } };
+    return for_each_chunk(c, nframes, flags, a, [&](int n, void *const *p) {
+        HIP_TRY(launch_noise_baseline((const uint8_t *)p[0], c->d_base, n, c->stream));
+        HIP_TRY(launch_messages((const uint8_t *)p[0], c->d_base, (const ft8gpu_candidate *)p[1], (const int32_t *)p[2],
+                                (const ft8gpu_decode_status *)p[3], c->d_msgtab, n, mc, c->params.min_score, (ft8gpu_message *)p[4],
+                                (int32_t *)p[5], c->stream));
+        return 0;
+    });
 }
 
 }  // extern "C"

@@ -20,8 +20,7 @@ static int run_shards(ft8gpu_ctx *const *ctxs, int ndev, const float *const *iq_
     auto work = [&](int g) {
         struct decoder_results *d = decodes + (size_t)first[g] * kMaxMessages;
         int32_t *n = n_results + first[g];
-        rc[g] = iq_on_device ? decode_dev_to_host(ctxs[g], iq_of[g], count[g], d, n)
-                             : ft8gpu_decode_batch(ctxs[g], iq_of[g], count[g], d, n, FT8GPU_HOST_PTRS);
+        rc[g] = decode_batch(ctxs[g], iq_of[g], count[g], d, n, iq_on_device ? kIqOnDevice : FT8GPU_HOST_PTRS);
         if (rc[g]) why[g] = ft8_err_buffer();                       // the error text is thread-local: hand it to the caller's thread
     };
     // shards 1.. on the persistent workers, shard 0 on the calling thread

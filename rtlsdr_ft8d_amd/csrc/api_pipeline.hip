@@ -163,8 +163,9 @@ static constexpr int kHostChunk = 512;      // frames per upload chunk of a host
 
 namespace {
 
-// the pipeline over a batch of any size, host or device pointers: Rec is struct decoder_results (the reference's spot
-// list) or ft8gpu_message (every unique message); both leave the slots they do not write as the caller had them
+// the pipeline over a batch of any size, host or device pointers (kIqOnDevice: iq on the device, records on the host):
+// Rec is struct decoder_results (the reference's spot list) or ft8gpu_message (every unique message); both leave the
+// slots they do not write as the caller had them
 template <class Rec>
 int decode_frames(ft8gpu_ctx *c, const float *iq, int nframes, Rec *recs, int32_t *counts, int flags, Rec *d_stage, int32_t *d_counts,
                   int (*run)(ft8gpu_ctx *, const float *, int, Rec *, int32_t *)) {
@@ -174,26 +175,31 @@ int decode_frames(ft8gpu_ctx *c, const float *iq, int nframes, Rec *recs, int32_
         if (flags & FT8GPU_DEVICE_PTRS) {
             if (run(c, iq + f0 * frame_floats, n, recs + (size_t)f0 * kMaxMessages, counts + f0)) return -1;
         } else {
-            if (!c->d_iq) HIP_TRY(hipMalloc(&c->d_iq, (size_t)c->max_frames * frame_floats * sizeof(float)));
+            const bool iq_dev = flags & kIqOnDevice;
+            if (!iq_dev && !c->d_iq) HIP_TRY(hipMalloc(&c->d_iq, (size_t)c->max_frames * frame_floats * sizeof(float)));
             // slots the path does not write must keep the caller's bytes (rtlsdr_ft8d.c:1509-1520)
             HIP_TRY(hipMemcpyAsync(d_stage, recs + (size_t)f0 * kMaxMessages,
                                    (size_t)n * kMaxMessages * sizeof(Rec), hipMemcpyHostToDevice, c->stream));
-            // the upload is 384 KB per frame and takes longer than the decode: pipeline it in chunks on a
-            // copy stream so that the kernels of chunk k run under the upload of chunk k+1
-            const int chunk = (n > kHostChunk && !(c->debug_flags & FT8GPU_DBG_NO_OVERLAP)) ? kHostChunk : n;
-            int k = 0;
-            for (int g0 = 0; g0 < n; g0 += chunk, k++) {
-                const int m = (n - g0 < chunk) ? n - g0 : chunk;
-                if (chunk < n && !c->copy) HIP_TRY(hipStreamCreateWithFlags(&c->copy, hipStreamNonBlocking));
-                hipStream_t up = (chunk < n) ? c->copy : c->stream;
-                HIP_TRY(hipMemcpyAsync(c->d_iq + g0 * frame_floats, iq + (f0 + g0) * frame_floats, m * frame_floats * sizeof(float),
-                                       hipMemcpyHostToDevice, up));
-                if (up != c->stream) {
-                    hipEvent_t e = c->copied[k % ft8gpu_ctx::kCopyEvents];
-                    HIP_TRY(hipEventRecord(e, up));
-                    HIP_TRY(hipStreamWaitEvent(c->stream, e, 0));
+            if (iq_dev) {                              // frames already on the GPU (the multi-GPU entries)
+                if (run(c, iq + f0 * frame_floats, n, d_stage, d_counts)) return -1;
+            } else {
+                // the upload is 384 KB per frame and takes longer than the decode: pipeline it in chunks on a
+                // copy stream so that the kernels of chunk k run under the upload of chunk k+1
+                const int chunk = (n > kHostChunk && !(c->debug_flags & FT8GPU_DBG_NO_OVERLAP)) ? kHostChunk : n;
+                int k = 0;
+                for (int g0 = 0; g0 < n; g0 += chunk, k++) {
+                    const int m = (n - g0 < chunk) ? n - g0 : chunk;
+                    if (chunk < n && !c->copy) HIP_TRY(hipStreamCreateWithFlags(&c->copy, hipStreamNonBlocking));
+                    hipStream_t up = (chunk < n) ? c->copy : c->stream;
+                    HIP_TRY(hipMemcpyAsync(c->d_iq + g0 * frame_floats, iq + (f0 + g0) * frame_floats, m * frame_floats * sizeof(float),
+                                           hipMemcpyHostToDevice, up));
+                    if (up != c->stream) {
+                        hipEvent_t e = c->copied[k % ft8gpu_ctx::kCopyEvents];
+                        HIP_TRY(hipEventRecord(e, up));
+                        HIP_TRY(hipStreamWaitEvent(c->stream, e, 0));
+                    }
+                    if (run(c, c->d_iq + g0 * frame_floats, m, d_stage + (size_t)g0 * kMaxMessages, d_counts + g0)) return -1;
                 }
-                if (run(c, c->d_iq + g0 * frame_floats, m, d_stage + (size_t)g0 * kMaxMessages, d_counts + g0)) return -1;
             }
             HIP_TRY(hipMemcpyAsync(recs + (size_t)f0 * kMaxMessages, d_stage,
                                    (size_t)n * kMaxMessages * sizeof(Rec), hipMemcpyDeviceToHost, c->stream));
@@ -206,12 +212,16 @@ int decode_frames(ft8gpu_ctx *c, const float *iq, int nframes, Rec *recs, int32_
 
 }  // namespace
 
-extern "C" int ft8gpu_decode_batch(ft8gpu_ctx *c, const float *iq, int nframes, struct decoder_results *decodes,
-                        int32_t *n_results, int flags) {
+int decode_batch(ft8gpu_ctx *c, const float *iq, int nframes, struct decoder_results *decodes, int32_t *n_results, int flags) {
     CHECK_COMMON(c, nframes);
     if (nframes == 0) return 0;
     if (!iq || !decodes || !n_results) return ft8_fail("NULL array argument");
     return decode_frames(c, iq, nframes, decodes, n_results, flags, c->d_decodes, c->d_nres, run_pipeline);
+}
+
+extern "C" int ft8gpu_decode_batch(ft8gpu_ctx *c, const float *iq, int nframes, struct decoder_results *decodes,
+                        int32_t *n_results, int flags) {
+    return decode_batch(c, iq, nframes, decodes, n_results, flags & FT8GPU_DEVICE_PTRS);
 }
 
 extern "C" int ft8gpu_decode_messages(ft8gpu_ctx *c, const float *iq, int nframes, ft8gpu_message *msgs, int32_t *n_msgs, int flags) {
@@ -221,25 +231,5 @@ extern "C" int ft8gpu_decode_messages(ft8gpu_ctx *c, const float *iq, int nframe
     if (ensure_messages_buffers(c)) return -1;
     if (!(flags & FT8GPU_DEVICE_PTRS) && !c->d_msgs)
         HIP_TRY(hipMalloc(&c->d_msgs, (size_t)c->max_frames * kMaxMessages * sizeof(ft8gpu_message)));
-    return decode_frames(c, iq, nframes, msgs, n_msgs, flags, c->d_msgs, c->d_nres, run_pipeline_messages);
-}
-
-// frames resident on the context's GPU, records to host arrays (used by the multi-GPU entry)
-int decode_dev_to_host(ft8gpu_ctx *c, const float *d_iq, int nframes, struct decoder_results *decodes, int32_t *n_results) {
-    CHECK_COMMON(c, nframes);
-    if (nframes == 0) return 0;
-    if (!d_iq || !decodes || !n_results) return ft8_fail("NULL array argument");
-    const size_t frame_floats = 2 * (size_t)kNSamples;
-    for (int f0 = 0; f0 < nframes; f0 += c->max_frames) {
-        const int n = (nframes - f0 < c->max_frames) ? nframes - f0 : c->max_frames;
-        // slots of non-CQ messages must keep the caller's bytes (rtlsdr_ft8d.c:1509-1520)
-        HIP_TRY(hipMemcpyAsync(c->d_decodes, decodes + (size_t)f0 * kMaxMessages,
-                               (size_t)n * kMaxMessages * sizeof(struct decoder_results), hipMemcpyHostToDevice, c->stream));
-        if (run_pipeline(c, d_iq + f0 * frame_floats, n, c->d_decodes, c->d_nres)) return -1;
-        HIP_TRY(hipMemcpyAsync(decodes + (size_t)f0 * kMaxMessages, c->d_decodes,
-                               (size_t)n * kMaxMessages * sizeof(struct decoder_results), hipMemcpyDeviceToHost, c->stream));
-        HIP_TRY(hipMemcpyAsync(n_results + f0, c->d_nres, n * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
-        HIP_TRY(hipStreamSynchronize(c->stream));
-    }
-    return 0;
+    return decode_frames(c, iq, nframes, msgs, n_msgs, flags & FT8GPU_DEVICE_PTRS, c->d_msgs, c->d_nres, run_pipeline_messages);
 }

@@ -92,6 +92,44 @@ struct Entry {
 
 inline int force_ieee(const ft8gpu_ctx *c) { return (c->debug_flags & FT8GPU_DBG_FORCE_IEEE_DIV) ? 1 : 0; }
 
+// One array argument of a stage entry: the caller's array (frame f at user + f * frame_bytes) and the context's staging
+// buffer of the host form.  kIn is uploaded, kOut downloaded, kInOut both; kOutZeroed is cleared, then downloaded.
+// user == nullptr: the argument is absent and the launch gets nullptr.
+enum StageDir { kIn, kOut, kInOut, kOutZeroed };
+struct StageArg { const void *user; void *stage; size_t frame_bytes; StageDir dir; };
+
+// The frames [0, nframes) in chunks of at most max_frames: launch(n, p) runs the stage on the chunk [f0, f0 + n) with
+// p[i] = user + f0 * frame_bytes (FT8GPU_DEVICE_PTRS) or the staging buffer (host form: uploaded before the launch,
+// downloaded and synchronised after it).  launch returns 0, or -1 with the error set.
+template <size_t N, class Launch>
+int for_each_chunk(ft8gpu_ctx *c, int nframes, int flags, const StageArg (&a)[N], Launch launch) {
+    const bool dev = flags & FT8GPU_DEVICE_PTRS;
+    for (int f0 = 0; f0 < nframes; f0 += c->max_frames) {
+        const int n = (nframes - f0 < c->max_frames) ? nframes - f0 : c->max_frames;
+        char *user[N];
+        void *p[N];
+        for (size_t i = 0; i < N; ++i) {
+            user[i] = a[i].user ? (char *)a[i].user + (size_t)f0 * a[i].frame_bytes : nullptr;
+            p[i] = (dev || !user[i]) ? user[i] : a[i].stage;
+        }
+        if (!dev) {
+            for (size_t i = 0; i < N; ++i) {
+                if (!user[i]) continue;
+                if (a[i].dir == kIn || a[i].dir == kInOut)
+                    HIP_TRY(hipMemcpyAsync(p[i], user[i], n * a[i].frame_bytes, hipMemcpyHostToDevice, c->stream));
+                if (a[i].dir == kOutZeroed) HIP_TRY(hipMemsetAsync(p[i], 0, n * a[i].frame_bytes, c->stream));
+            }
+        }
+        if (launch(n, p)) return -1;
+        if (dev) continue;
+        for (size_t i = 0; i < N; ++i)
+            if (user[i] && a[i].dir != kIn)
+                HIP_TRY(hipMemcpyAsync(user[i], p[i], n * a[i].frame_bytes, hipMemcpyDeviceToHost, c->stream));
+        HIP_TRY(hipStreamSynchronize(c->stream));
+    }
+    return 0;
+}
+
 // api_context.hip
 int probe_streams(ft8gpu_ctx *c);             // (re)establishes c->overlap_ok for the current main stream
 // api_pipeline.hip: the whole path on device pointers; all intermediates in the context's HBM buffers
@@ -100,7 +138,9 @@ int run_pipeline(ft8gpu_ctx *c, const float *d_iq, int n, struct decoder_results
 int run_pipeline_messages(ft8gpu_ctx *c, const float *d_iq, int n, ft8gpu_message *d_msgs, int32_t *d_nmsgs);
 // api_messages.hip: allocates d_base / d_msgtab on the first messages call
 int ensure_messages_buffers(ft8gpu_ctx *c);
-// frames resident on the context's GPU, records to host arrays (used by the multi-GPU entries)
-int decode_dev_to_host(ft8gpu_ctx *c, const float *d_iq, int nframes, struct decoder_results *decodes, int32_t *n_results);
+// ft8gpu_decode_batch with one more form: kIqOnDevice, frames resident on the context's GPU and records to host arrays
+// (used by the multi-GPU entries; not part of the ABI, whose entry passes on FT8GPU_DEVICE_PTRS only)
+constexpr int kIqOnDevice = 2;
+int decode_batch(ft8gpu_ctx *c, const float *iq, int nframes, struct decoder_results *decodes, int32_t *n_results, int flags);
 // api_glue.hip: (re)allocates *buf when `need` exceeds *cap (the caller has synchronised the stream)
 int grow_buffer(void **buf, size_t *cap, size_t need);

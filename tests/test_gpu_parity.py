@@ -458,6 +458,110 @@ def test_batch_larger_than_context_and_device_pointers(oracle, frames):
         assert n[k] == rn and dec[k].tobytes() == rdec.tobytes()
 
 
+def test_stage_entries_chunked_host_and_device_forms_agree(oracle, frames):
+    """every stage entry over 8 frames, three ways: the host form on a 3-frame context (chunks 3, 3, 2), the device form
+    on the same context, and the device form on a context that holds all 8 frames.  Every output starts as the byte
+    pattern 0xA5 (the Python wrappers would zero it), so a slot that an entry leaves alone, or fills from the wrong chunk,
+    shows.  The three results are byte-identical, with one exception: the host form of decode_candidates returns zeros
+    in the status slots past counts[f] (its staging buffer is cleared), where the device form leaves the caller's bytes."""
+    import ctypes as C
+    import torch
+    import rtlsdr_ft8d_amd as ft8
+    lib = ft8.load_library()
+    B, FILL = 8, 0xA5
+    iq = np.stack([f for _, f in frames[:6] + frames[14:16]])       # CQ-heavy synthetic frames and on-air style traffic
+    info = ft8.ReportInfo(rcall=b"N0CALL", rloc=b"FN20", app_version=b"rtlsdr-ft8d_v0.3.6", dial_freq=14074000,
+                          unixtime=1700000000, sequence=1, random_id=7)
+
+    class Out:
+        def __init__(self, shape, dtype):
+            self.shape, self.dtype = shape, np.dtype(dtype)
+
+    def call(d, dev, entry, *args):
+        """numpy arrays are inputs (uploaded for the device form), Out slots are outputs that start as FILL (and are
+        in-out where the entry reads them); anything else is passed as it is"""
+        outs, cargs, keep = [], [], []
+        for a in args:
+            if isinstance(a, Out):
+                nbytes = int(np.prod(a.shape)) * a.dtype.itemsize
+                if dev:
+                    t = torch.full((nbytes,), FILL, dtype=torch.uint8, device="cuda")
+                    outs.append((t, a))
+                    cargs.append(t.data_ptr())
+                else:
+                    h = np.full(nbytes, FILL, np.uint8).view(a.dtype).reshape(a.shape)
+                    outs.append((h, a))
+                    cargs.append(h.ctypes.data)
+            elif isinstance(a, np.ndarray):
+                h = np.ascontiguousarray(a).reshape(-1).view(np.uint8)
+                t = torch.from_numpy(h.copy()).cuda() if dev else h
+                keep.append(t)
+                cargs.append(t.data_ptr() if dev else t.ctypes.data)
+            else:
+                cargs.append(a)
+        rc = getattr(lib, "ft8gpu_" + entry)(d.h, *cargs, ft8.DEVICE_PTRS if dev else ft8.HOST_PTRS)
+        assert rc == 0, lib.ft8gpu_last_error()
+        torch.cuda.synchronize()
+        return [(o.cpu().numpy() if dev else o).view(a.dtype).reshape(a.shape) for o, a in outs]
+
+    for cap, unixtimes in ((120, None), (7, np.arange(B, dtype=np.uint32) + 1700000000)):
+        with ft8.Decoder(device=0, max_frames=3, max_candidates=cap) as d3, ft8.Decoder(device=0, max_frames=B, max_candidates=cap) as d8:
+            for d in (d3, d8):
+                d.set_stream(torch.cuda.current_stream().cuda_stream)
+
+            def three(entry, *args):
+                return call(d3, False, entry, *args), call(d3, True, entry, *args), call(d8, True, entry, *args)
+
+            def same(entry, *args):
+                host, dev3, dev8 = three(entry, *args)
+                for form, r in (("device form, chunked", dev3), ("device form, one chunk", dev8)):
+                    for k, (a, b) in enumerate(zip(host, r)):
+                        assert a.tobytes() == b.tobytes(), f"{entry} cap {cap}: output {k} of the {form} differs from the host form"
+                return host
+
+            (mag,) = same("waterfall", iq, B, Out((B, MAG), np.uint8))
+            cands, counts = same("find_sync", mag, B, Out((B, cap), ft8.CAND_DTYPE), Out((B,), np.int32))
+            same("score_map", mag, B, Out((B, 2, 2, 36, 249), np.int16))
+            live = np.arange(cap)[None, :] < counts[:, None]
+            status = {}
+            for dbg in (0, ft8.DBG_PIPELINE_FORM):
+                d3.set_debug_flags(dbg)
+                d8.set_debug_flags(dbg)
+                (host,), (dev3,), (dev8,) = three("decode_candidates", mag, cands, counts, B, Out((B, cap), ft8.STATUS_DTYPE))
+                assert dev3.tobytes() == dev8.tobytes(), f"decode_candidates cap {cap} flags {dbg}"
+                assert host[live].tobytes() == dev3[live].tobytes(), f"decode_candidates cap {cap} flags {dbg}"
+                # the stated exception: past counts[f] the host form returns its cleared staging, the device form the caller's bytes
+                assert host[~live].tobytes() == bytes(host[~live].nbytes)
+                assert dev3[~live].tobytes() == bytes([FILL]) * dev3[~live].nbytes
+                status[dbg] = host
+            d3.set_debug_flags(0)
+            d8.set_debug_flags(0)
+            decodes, nres = same("collect_spots", cands, counts, status[0], B, Out((B, 50), ft8.RESULT_DTYPE), Out((B,), np.int32))
+            same("noise_baseline", mag, B, Out((B, 2, 256), np.uint8))
+            same("collect_messages", mag, cands, counts, status[0], B, Out((B, 50), ft8.MESSAGE_DTYPE), Out((B,), np.int32))
+            same("pskreporter_datagrams", decodes, nres, B, C.byref(info), unixtimes, Out((B, ft8.DATAGRAM_STRIDE), np.uint8),
+                 Out((B,), np.int32))
+
+        # ... and agree with the oracle: waterfall, candidate lists, status records (both forms of the kernel), spots
+        params = oracle.default_params(max_candidates=cap)
+        for k in range(B):
+            assert np.array_equal(mag[k], oracle.waterfall(iq[k, 0], iq[k, 1])), f"frame {k}"
+            ref = oracle.find_sync(mag[k], cap, 10)
+            assert counts[k] == len(ref) and np.array_equal(cands[k, :counts[k]], ref), f"frame {k}"
+            _compare_status(f"frame {k}", status[0][k], _oracle_status(oracle, mag[k], cands[k, :counts[k]], 20))
+            a, b = status[0][k, :counts[k]], status[ft8.DBG_PIPELINE_FORM][k, :counts[k]]
+            for name in ("iters", "crc_extracted", "crc_calculated", "unpack_status", "ok", "a91", "text"):
+                assert np.array_equal(a[name], b[name]), f"frame {k}: {name}"
+            assert np.array_equal(a["ldpc_errors"] == 0, b["ldpc_errors"] == 0)
+            rdec = np.full(50 * ft8.RESULT_DTYPE.itemsize, FILL, np.uint8).view(ft8.RESULT_DTYPE)
+            rn = C.c_int32(0)
+            oracle.lib().ft8o_subsystem_from_waterfall(oracle._u8(np.ascontiguousarray(mag[k])), C.byref(params),
+                                                       rdec.ctypes.data, C.byref(rn))
+            assert nres[k] == rn.value and decodes[k].tobytes() == rdec.tobytes(), f"frame {k}: spots"
+        if cap == 120:
+            assert nres.sum() >= 5 and counts.min() < cap      # real spots, and frames with slots past their count
+
+
 def test_device_synth_frames_decode_and_match_oracle(oracle):
     """the on-device generator used by bench.py: frames come back to the host and the oracle must
     agree with the GPU decode of the very same samples (full-size batches are checked the same way
