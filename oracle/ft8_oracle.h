@@ -28,8 +28,9 @@
  *       which pins pack77, CRC-14, the LDPC generator, the Gray map and the Costas layout;
  *   (2) the -t self-test pass condition rtlsdr_ft8d.c:966-971 (decode of the synthesised
  *       frame yields call "K1JT" / loc "FN20" in slot 0).
- * Both are checked in tests/test_oracle.py against tests/golden/.  The reference cannot be
- * compiled here (no ft8_lib sources, no fftw3.h, no rtl-sdr.h), so there is no oracle/_ref.
+ * Both are checked in tests/test_oracle.py against tests/golden/.  The reference's own code outside ft8_lib
+ * (RX chain, waterfall, candidate loop, records, file I/O, printSpots, -t / -r) is executed beside this oracle by
+ * tests/test_reference_exec.py, through the test programs `make -C oracle ref` links into oracle/_ref.
  *
  * FFT: the reference calls fftwf (FFTW_ESTIMATE plan, rtlsdr_ft8d.c:326); FFTW is absent and
  * its codelet choice is machine dependent, so no implementation can be bit-identical to it.

@@ -6,7 +6,8 @@ this repository's drop-in headers.
 `candidate_t`, `message_t`, `decode_status_t`, the constants), so with `-I include` the reference's own
 `ft8_subsystem()` (`:1387-1524`, call sites `:1439-1494`) builds around GPU `ft8_find_sync` / `ft8_decode`.  The
 reference is not part of this repository: `make -C oracle ref` compiles it where it lies into oracle/_ref/ (the syntax
-check, the header tree gcc reports and the object file; nothing is copied, linked or run).  These tests run that recipe
+check, the header tree gcc reports and the object file checked here; nothing is copied).  The same recipe also links it,
+with stand-ins for librtlsdr, libcurl and FFTW, into the programs tests/test_reference_exec.py runs.  These tests run that recipe
 against the headers of this tree whenever a checkout of the reference is at hand (oracle_lib.reference_dir) and
 otherwise read what build() left there; `rtl-sdr.h`, `fftw3.h` and `curl/curl.h` are absent from the image and are
 replaced by declaration-only stand-ins (tests/stub_sys/README.md).  Skipped only where neither is there."""
