@@ -282,6 +282,34 @@ int ft8gpu_collect_messages(ft8gpu_ctx *ctx, const uint8_t *mag, const ft8gpu_ca
 /* per-frame noise floor of the SNR estimate: base[f][fs][j] = the 47th smallest (index 46) of the 184 bytes
  * mag[f][b][ts][fs][j] over b < 92, ts < 2 (the 25th percentile over time).  base: [nframes][2][256] */
 int ft8gpu_noise_baseline(ft8gpu_ctx *ctx, const uint8_t *mag, int nframes, uint8_t *base, int flags);
+/* ---- multi-pass decoding: decode again after the decoded signals are masked out of the waterfall ----------------------
+ * (DESIGN.md "Multi-pass decoding").  Pass 1 is ft8gpu_decode_messages, unchanged: waterfall W1, its noise baseline B
+ * (ft8gpu_noise_baseline), records [0, n1).  Pass p+1 masks W(p): for every symbol k of every record first written in
+ * pass p, the cell mag[(to+k)*1024 + ts*512 + fs*256 + fo + tone_k] with 0 <= to+k < 92 takes the baseline B[fs][fo + tone_k]
+ * ((to, ts, fo, fs) = the record's cand with ts, fs taken mod 2 and fo clamped to [0, 248]; tone_k re-encoded from a91).
+ * It then runs find_sync, the candidate heap and the LDPC decode on the masked waterfall with the context's params, and
+ * appends, in candidate order, every unique message (hash, text) that is not yet among the frame's records, up to 50 in
+ * all.  An appended record is built as ft8gpu_decode_messages builds one (cand_index indexes this pass's candidate list);
+ * its snr_db is measured on the masked waterfall against the pass-1 baseline.  A frame that gained nothing in pass p, or
+ * holds 50 records, is not decoded again.  Slots [0, n1) are those of ft8gpu_decode_messages; counts never shrink. */
+#define FT8GPU_MAX_PASSES 4
+/* passes in [1, FT8GPU_MAX_PASSES]; msgs [nframes][50], n_msgs [nframes] as ft8gpu_decode_messages (slots >= n_msgs[f]
+ * untouched); n_by_pass [nframes][passes]: the count after each pass (NULL: not written).  Host or device pointers,
+ * chunked by max_frames.  The host reads one int per later pass (the number of frames still decoding) and stops early at 0.
+ * ft8gpu_enable_timing records the first pass. */
+int ft8gpu_decode_messages_passes(ft8gpu_ctx *ctx, const float *iq, int nframes, int passes, ft8gpu_message *msgs,
+                                  int32_t *n_msgs, int32_t *n_by_pass, int flags);
+/* stage entry of the mask: mag_out[f] = mag[f] with the cells of records [first[f], n_msgs[f]) (clamped to [0, 50]) set to
+ * the baseline.  mag / mag_out [nframes][94208] (mag_out may be mag), base [nframes][2][256], msgs [nframes][50],
+ * first / n_msgs [nframes] */
+int ft8gpu_mask_messages(ft8gpu_ctx *ctx, const uint8_t *mag, const uint8_t *base, const ft8gpu_message *msgs,
+                         const int32_t *first, const int32_t *n_msgs, int nframes, uint8_t *mag_out, int flags);
+/* stage entry of the append: mag = the pass's waterfall, base = the pass-1 baseline, cands / counts / status = the pass's
+ * stage outputs ([nframes][max_candidates]); msgs / n_msgs are in-out: the frame's records so far (n_msgs[f] clamped to
+ * [0, 50]), and the new ones appended behind them */
+int ft8gpu_append_messages(ft8gpu_ctx *ctx, const uint8_t *mag, const uint8_t *base, const ft8gpu_candidate *cands,
+                           const int32_t *counts, const ft8gpu_decode_status *status, int nframes, ft8gpu_message *msgs,
+                           int32_t *n_msgs, int flags);
 /* one line per message, "%3d %4.1f %4d ~  %s\n" of snr_db, dt_s, (int)freq_hz, text (NUL-terminated, truncated to cap);
  * returns the untruncated length.  Host-side text formatting, no GPU involved. */
 int ft8gpu_format_messages(const ft8gpu_message *msgs, int32_t n, char *out, size_t cap);

@@ -76,6 +76,7 @@ ABI_SYMBOLS = [
     "ft8gpu_set_debug_flags", "ft8gpu_selftest_bp_math", "ft8gpu_selftest_norm_math", "ft8gpu_gather_spots", "ft8gpu_gather_shutdown",
     "ft8gpu_shard_workers", "ft8gpu_decode_batch_multi", "ft8gpu_decode_batch_multi_dev",
     "ft8gpu_decode_messages", "ft8gpu_collect_messages", "ft8gpu_noise_baseline", "ft8gpu_format_messages",
+    "ft8gpu_decode_messages_passes", "ft8gpu_mask_messages", "ft8gpu_append_messages",
     "ft8_find_sync", "ft8_decode", "ft8_encode", "pack77",            # ft8_lib level (include/ft8_lib/ft8/*.h)
     "initFFTW", "freeFFTW", "ft8_subsystem", "ft8gpu_read_raw_iq", "ft8gpu_read_c2", "ft8gpu_write_raw_iq",
 ]
@@ -201,6 +202,10 @@ def _declare(L):
         L.ft8gpu_collect_messages.argtypes = [vp, vp, vp, vp, vp, C.c_int, vp, vp, C.c_int]
         L.ft8gpu_noise_baseline.argtypes = [vp, vp, C.c_int, vp, C.c_int]
         L.ft8gpu_format_messages.argtypes = [vp, C.c_int32, vp, C.c_size_t]
+    if hasattr(L, "ft8gpu_decode_messages_passes"):       # absent from older builds loaded by load_library_at
+        L.ft8gpu_decode_messages_passes.argtypes = [vp, vp, C.c_int, C.c_int, vp, vp, vp, C.c_int]
+        L.ft8gpu_mask_messages.argtypes = [vp, vp, vp, vp, vp, vp, C.c_int, vp, C.c_int]
+        L.ft8gpu_append_messages.argtypes = [vp, vp, vp, vp, vp, vp, C.c_int, vp, vp, C.c_int]
     L.ft8gpu_rx_decimate.argtypes = [vp, vp, C.c_int, C.c_size_t, vp, C.c_int, C.c_int]
     L.ft8gpu_pskreporter_datagrams.argtypes = [vp, vp, vp, C.c_int, C.POINTER(ReportInfo), vp, vp, vp, C.c_int]
     L.ft8gpu_format_spots.argtypes = [vp, C.c_int32, C.c_uint32, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, vp, C.c_size_t]
@@ -455,7 +460,67 @@ class Decoder:
         self._ck(self.lib.ft8gpu_noise_baseline(self.h, mag.ctypes.data, B, base.ctypes.data, HOST_PTRS))
         return base
 
+    def decode_messages_passes(self, iq, passes=2, msgs=None):
+        """multi-pass decoding (ft8gpu_decode_messages_passes) -> (msgs [B][50] MESSAGE_DTYPE, n_msgs [B],
+        n_by_pass [B][passes], the count after each pass); slots past n_msgs[f] keep what `msgs` held (zeros when None)"""
+        iq = np.ascontiguousarray(iq, np.float32)
+        B = iq.shape[0]
+        assert iq.shape[1:] == (2, NSAMPLES)
+        if msgs is None:
+            msgs = np.zeros((B, MAX_MESSAGES), MESSAGE_DTYPE)
+        assert msgs.dtype == MESSAGE_DTYPE and msgs.shape == (B, MAX_MESSAGES) and msgs.flags["C_CONTIGUOUS"]
+        n = np.zeros(B, np.int32)
+        nbp = np.zeros((B, max(int(passes), 1)), np.int32)
+        self._ck(self.lib.ft8gpu_decode_messages_passes(self.h, iq.ctypes.data, B, int(passes), msgs.ctypes.data, n.ctypes.data,
+                                                      nbp.ctypes.data, HOST_PTRS))
+        return msgs, n, nbp
+
+    def mask_messages(self, mag, base, msgs, first, n_msgs):
+        """ft8gpu_mask_messages: mag [B][94208] with the cells of records [first[f], n_msgs[f]) set to the baseline"""
+        mag = np.ascontiguousarray(mag, np.uint8).reshape(-1, MAG_ARRAY)
+        B = mag.shape[0]
+        base = np.ascontiguousarray(base, np.uint8)
+        msgs = np.ascontiguousarray(msgs)
+        first = np.ascontiguousarray(first, np.int32)
+        n_msgs = np.ascontiguousarray(n_msgs, np.int32)
+        assert base.size == B * 512 and msgs.dtype == MESSAGE_DTYPE and msgs.shape == (B, MAX_MESSAGES)
+        assert first.shape == (B,) and n_msgs.shape == (B,)
+        out = np.zeros((B, MAG_ARRAY), np.uint8)
+        self._ck(self.lib.ft8gpu_mask_messages(self.h, mag.ctypes.data, base.ctypes.data, msgs.ctypes.data, first.ctypes.data,
+                                             n_msgs.ctypes.data, B, out.ctypes.data, HOST_PTRS))
+        return out
+
+    def append_messages(self, mag, base, cands, counts, status, msgs, n_msgs):
+        """ft8gpu_append_messages: the pass's new messages appended behind the records so far -> (msgs, n_msgs), new arrays"""
+        mag = np.ascontiguousarray(mag, np.uint8).reshape(-1, MAG_ARRAY)
+        B = mag.shape[0]
+        base = np.ascontiguousarray(base, np.uint8)
+        cands = np.ascontiguousarray(cands)
+        counts = np.ascontiguousarray(counts, np.int32)
+        status = np.ascontiguousarray(status)
+        assert base.size == B * 512 and cands.shape == (B, self.max_candidates) and status.shape == (B, self.max_candidates)
+        assert counts.shape == (B,) and cands.dtype == CAND_DTYPE and status.dtype == STATUS_DTYPE
+        msgs = np.array(msgs, dtype=MESSAGE_DTYPE, copy=True, order="C")
+        n = np.array(n_msgs, dtype=np.int32, copy=True, order="C")
+        assert msgs.shape == (B, MAX_MESSAGES) and n.shape == (B,)
+        self._ck(self.lib.ft8gpu_append_messages(self.h, mag.ctypes.data, base.ctypes.data, cands.ctypes.data, counts.ctypes.data,
+                                               status.ctypes.data, B, msgs.ctypes.data, n.ctypes.data, HOST_PTRS))
+        return msgs, n
+
     # ---- device-pointer API (inputs and outputs resident in HBM) --------------------------------
+    def decode_messages_passes_dev(self, iq_dev, nframes, passes, msgs_dev, n_msgs_dev, n_by_pass_dev=None):
+        """n_by_pass_dev: [nframes][passes] int32, or None"""
+        self._ck(self.lib.ft8gpu_decode_messages_passes(self.h, _ptr(iq_dev), nframes, int(passes), _ptr(msgs_dev), _ptr(n_msgs_dev),
+                                                      None if n_by_pass_dev is None else _ptr(n_by_pass_dev), DEVICE_PTRS))
+
+    def mask_messages_dev(self, mag_dev, base_dev, msgs_dev, first_dev, n_msgs_dev, nframes, mag_out_dev):
+        self._ck(self.lib.ft8gpu_mask_messages(self.h, _ptr(mag_dev), _ptr(base_dev), _ptr(msgs_dev), _ptr(first_dev), _ptr(n_msgs_dev),
+                                             nframes, _ptr(mag_out_dev), DEVICE_PTRS))
+
+    def append_messages_dev(self, mag_dev, base_dev, cands_dev, counts_dev, status_dev, nframes, msgs_dev, n_msgs_dev):
+        self._ck(self.lib.ft8gpu_append_messages(self.h, _ptr(mag_dev), _ptr(base_dev), _ptr(cands_dev), _ptr(counts_dev),
+                                               _ptr(status_dev), nframes, _ptr(msgs_dev), _ptr(n_msgs_dev), DEVICE_PTRS))
+
     def decode_messages_dev(self, iq_dev, nframes, msgs_dev, n_msgs_dev):
         self._ck(self.lib.ft8gpu_decode_messages(self.h, _ptr(iq_dev), nframes, _ptr(msgs_dev), _ptr(n_msgs_dev), DEVICE_PTRS))
 

@@ -58,6 +58,16 @@ struct ft8gpu_ctx {
     uint8_t *d_base = nullptr;             // messages path, lazily allocated on its first call: noise baseline [max_frames][512]
     MsgTables *d_msgtab = nullptr;         //   its constant tables
     ft8gpu_message *d_msgs = nullptr;      //   host-pointer staging of the records [max_frames][50]
+    uint8_t *d_mag2 = nullptr;             // multi-pass, lazily allocated: the compact waterfall of a later pass [max_frames][94208]
+    int32_t *d_map = nullptr;              //   its slot -> frame map [max_frames], the counts before the pass [max_frames],
+    int32_t *d_nprev = nullptr;            //   the number of active frames (1) and its host copy (pinned)
+    int32_t *d_nactive = nullptr;
+    int32_t *h_nactive = nullptr;
+    ft8gpu_candidate *d_cands2 = nullptr;  //   the pass's candidates / counts / statuses [max_frames][cap2]
+    int32_t *d_counts2 = nullptr;
+    ft8gpu_decode_status *d_status2 = nullptr;
+    int cap2 = 0;
+    int32_t *d_nbp = nullptr;              //   host-pointer staging of the per-pass counts [max_frames][FT8GPU_MAX_PASSES]
     ft8gpu_synth_signal *d_sigs = nullptr;
     size_t sigs_cap = 0;
     void *d_rx_sums = nullptr, *d_rx_p2 = nullptr;     // RX front end scratch
@@ -138,6 +148,8 @@ int run_pipeline(ft8gpu_ctx *c, const float *d_iq, int n, struct decoder_results
 int run_pipeline_messages(ft8gpu_ctx *c, const float *d_iq, int n, ft8gpu_message *d_msgs, int32_t *d_nmsgs);
 // api_messages.hip: allocates d_base / d_msgtab on the first messages call
 int ensure_messages_buffers(ft8gpu_ctx *c);
+// api_multipass.hip: frees the multi-pass buffers (ft8gpu_destroy)
+void free_multipass_buffers(ft8gpu_ctx *c);
 // ft8gpu_decode_batch with one more form: kIqOnDevice, frames resident on the context's GPU and records to host arrays
 // (used by the multi-GPU entries; not part of the ABI, whose entry passes on FT8GPU_DEVICE_PTRS only)
 constexpr int kIqOnDevice = 2;

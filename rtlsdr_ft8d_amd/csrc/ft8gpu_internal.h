@@ -77,6 +77,14 @@ hipError_t launch_noise_baseline(const uint8_t *mag, uint8_t *base, int nframes,
 hipError_t launch_messages(const uint8_t *mag, const uint8_t *base, const ft8gpu_candidate *cands, const int32_t *counts,
                            const ft8gpu_decode_status *status, const MsgTables *tab, int nframes, int max_candidates,
                            int min_score, ft8gpu_message *msgs, int32_t *n_msgs, hipStream_t s);
+// multipass.hip: decoding again on the waterfall with the decoded messages masked out (DESIGN.md "Multi-pass decoding")
+hipError_t launch_mask(const uint8_t *mag, const uint8_t *base, const ft8gpu_message *msgs, const int32_t *first,
+                       const int32_t *n_msgs, const MsgTables *tab, int nframes, int compact, uint8_t *out,
+                       int32_t *map, int32_t *n_active, hipStream_t s);
+hipError_t launch_append(const uint8_t *mag, const uint8_t *base, const ft8gpu_candidate *cands, const int32_t *counts,
+                         const ft8gpu_decode_status *status, const MsgTables *tab, const int32_t *map, int nslots,
+                         int max_candidates, int min_score, ft8gpu_message *msgs, int32_t *n_msgs, hipStream_t s);
+hipError_t launch_pass_counts(const int32_t *n_msgs, int32_t *nbp, int nframes, int passes, int col0, hipStream_t s);
 hipError_t launch_synth(const ft8gpu_synth_signal *sig_dev, int nframes, int nsig, float noise_sigma,
                         uint64_t seed, uint64_t first_frame, float *iq, hipStream_t s);
 hipError_t run_bp_math_selftest(uint64_t out[7], hipStream_t s);   // bp_selftest.hip: exhaustive check of bp_math.h
