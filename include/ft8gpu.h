@@ -358,12 +358,45 @@ int ft8gpu_synth_frames_at(ft8gpu_ctx *ctx, const ft8gpu_synth_signal *signals, 
 /* ---- RX front end: rtlsdr_callback(), rtlsdr_ft8d.c:76-202 ------------
  * Whole raw RTL-SDR captures (unsigned 8-bit I,Q interleaved at 2.4 Msps) -> the 15 s / ~3200 sps
  * float frames the decoder consumes: fs/4 mixer, CIC (N = 2, comb delay 2, effective ratio 751),
- * 57-tap compensation FIR, scaling; every capture starts from the reset filter state.  Samples past
+ * 57-tap compensation FIR, scaling; every capture starts from the reset filter state (ft8gpu_rx_stream
+ * below carries the state from one buffer into the next, as the reference's daemon does).  Samples past
  * npairs/751 are zero as after the decoder thread's tail zeroing (:243-246); normalise != 0 applies
  * its peak normalisation to 0.5 (:248-263), after which `iq` can go straight into ft8gpu_decode_batch.
  * raw: [ncaptures][2*npairs] bytes, npairs a multiple of 8, 16-byte aligned; iq: [ncaptures][2][48000]. */
 int ft8gpu_rx_decimate(ft8gpu_ctx *ctx, const uint8_t *raw, int ncaptures, size_t npairs,
                        float *iq, int normalise, int flags);
+
+/* The same front end on a continuous stream.  rtlsdr_callback() keeps its filter state in function statics and the
+ * daemon never resets them: every 15 s buffer after the first starts from what the previous one left (36 000 000 pairs
+ * mod 751 = 64, so the decimation grid of the second buffer is shifted, and every sample of it differs from a run
+ * from reset).  ft8gpu_rx_state holds those statics, field for field: the two integrators per channel, the last comb
+ * outputs, the comb delays, decimationIndex and the 56-float FIR histories (516 bytes, no padding). */
+typedef struct {
+    int32_t  Ix1, Ix2, Qx1, Qx2;                 /* integrators (wrapping 32-bit) */
+    int32_t  Iy1, It1y, It1z, Qy1, Qt1y, Qt1z;   /* first comb: last output, delays */
+    int32_t  Iy2, It2y, It2z, Qy2, Qt2y, Qt2z;   /* second comb */
+    uint32_t decimationIndex;                    /* pairs consumed since the last output, 0..750 */
+    float    firI[56], firQ[56];                 /* the last 56 comb outputs, oldest first */
+} ft8gpu_rx_state;
+
+/* all zero, as at program start */
+void ft8gpu_rx_state_reset(ft8gpu_rx_state *st);
+
+/* raw: [nstreams][nslots][2*npairs] bytes: nstreams independent receivers, each with nslots consecutive buffers of
+ * npairs pairs (a positive multiple of 8; raw 16-byte aligned).  nstreams * nslots <= max_frames.  Buffers of different
+ * length are served by successive calls with nslots = 1.
+ * state: [nstreams], read at entry and written at exit: slot s + 1 of a stream continues from the state slot s left,
+ * and the next call continues from `state`.  After the call state[k] equals, byte for byte, the reference's statics
+ * after rtlsdr_callback() has consumed the same bytes from the same entry state.  Every byte is consumed (unlike
+ * ft8gpu_rx_decimate, which stops after 48000 blocks).  An entry decimationIndex above 750 is refused.
+ * iq: [nstreams][nslots][2][48000]: per slot the outputs the reference stores for it -- the decimation events inside
+ * the slot's bytes, the first 48000 of them (:195-200) -- zeros behind them (:243-246), and with normalise != 0 the
+ * per-slot peak normalisation (:248-263).  n_out: [nstreams][nslots] stored counts (iqIndex), or NULL.
+ * flags: FT8GPU_HOST_PTRS / FT8GPU_DEVICE_PTRS for every array argument, state and n_out included.  The device form
+ * reads the entry decimationIndex values back (one stream synchronisation) before it enqueues anything.
+ * From a reset state and with nslots = 1 the frames are byte-identical to ft8gpu_rx_decimate's. */
+int ft8gpu_rx_stream(ft8gpu_ctx *ctx, const uint8_t *raw, int nstreams, int nslots, size_t npairs,
+                     ft8gpu_rx_state *state, float *iq, uint32_t *n_out, int normalise, int flags);
 
 /* ---- spot reporting wire formats ------------------------------------
  * The bytes postSpots() (rtlsdr_ft8d.c:365-590) assembles for report.pskreporter.info:4739 (IPFIX:

@@ -30,6 +30,10 @@ STATUS_DTYPE = np.dtype([("ldpc_errors", "<i2"), ("iters", "<i2"), ("crc_extract
 SIGNAL_DTYPE = np.dtype([("tones", "u1", (79,)), ("pad", "u1"), ("f0_hz", "<f4"), ("t0_s", "<f4"),
                          ("amplitude", "<f4")])
 # ft8gpu_message: every unique message of a frame with SNR estimate, time offset and frequency (ft8gpu_decode_messages)
+# ft8gpu_rx_state: the statics of rtlsdr_callback() (rtlsdr_ft8d.c:76-202), 516 bytes without padding
+RX_STATE_DTYPE = np.dtype([(n, "<i4") for n in ("Ix1", "Ix2", "Qx1", "Qx2", "Iy1", "It1y", "It1z", "Qy1", "Qt1y", "Qt1z",
+                                                "Iy2", "It2y", "It2z", "Qy2", "Qt2y", "Qt2z")]
+                          + [("decimationIndex", "<u4"), ("firI", "<f4", (56,)), ("firQ", "<f4", (56,))])
 MESSAGE_DTYPE = np.dtype({"names": ["text", "snr_db", "score", "freq_hz", "dt_s", "hash", "cand_index", "cand", "a91", "pad"],
                           "formats": ["S25", "i1", "<i2", "<f4", "<f4", "<u2", "<u2", CAND_DTYPE, ("u1", (12,)), ("u1", (4,))],
                           "offsets": [0, 25, 26, 28, 32, 36, 38, 40, 48, 60], "itemsize": 64})
@@ -71,6 +75,7 @@ ABI_SYMBOLS = [
     "ft8gpu_decode_batch", "ft8gpu_waterfall", "ft8gpu_find_sync", "ft8gpu_score_map",
     "ft8gpu_decode_candidates", "ft8gpu_collect_spots", "ft8gpu_pack77_std", "ft8gpu_encode",
     "ft8gpu_synth_frames", "ft8gpu_synth_frames_at", "ft8gpu_rx_decimate", "ft8gpu_pskreporter_datagrams", "ft8gpu_format_spots",
+    "ft8gpu_rx_stream", "ft8gpu_rx_state_reset",
     "ft8gpu_dev_alloc", "ft8gpu_dev_free", "ft8gpu_memcpy_h2d", "ft8gpu_memcpy_d2h", "ft8gpu_host_alloc", "ft8gpu_host_free",
     "ft8gpu_overlap_active", "ft8gpu_overlap_reason", "ft8gpu_build_id", "ft8gpu_pack77",
     "ft8gpu_set_debug_flags", "ft8gpu_selftest_bp_math", "ft8gpu_selftest_norm_math", "ft8gpu_gather_spots", "ft8gpu_gather_shutdown",
@@ -207,6 +212,10 @@ def _declare(L):
         L.ft8gpu_mask_messages.argtypes = [vp, vp, vp, vp, vp, vp, C.c_int, vp, C.c_int]
         L.ft8gpu_append_messages.argtypes = [vp, vp, vp, vp, vp, vp, C.c_int, vp, vp, C.c_int]
     L.ft8gpu_rx_decimate.argtypes = [vp, vp, C.c_int, C.c_size_t, vp, C.c_int, C.c_int]
+    if hasattr(L, "ft8gpu_rx_stream"):                    # absent from older builds loaded by load_library_at
+        L.ft8gpu_rx_stream.argtypes = [vp, vp, C.c_int, C.c_int, C.c_size_t, vp, vp, vp, C.c_int, C.c_int]
+        L.ft8gpu_rx_state_reset.argtypes = [vp]
+        L.ft8gpu_rx_state_reset.restype = None
     L.ft8gpu_pskreporter_datagrams.argtypes = [vp, vp, vp, C.c_int, C.POINTER(ReportInfo), vp, vp, vp, C.c_int]
     L.ft8gpu_format_spots.argtypes = [vp, C.c_int32, C.c_uint32, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, vp, C.c_size_t]
     L.ft8gpu_dev_alloc.argtypes = [vp, C.c_size_t]
@@ -556,6 +565,34 @@ class Decoder:
 
     def rx_decimate_dev(self, raw_dev, ncaptures, npairs, iq_dev, normalise=True):
         self._ck(self.lib.ft8gpu_rx_decimate(self.h, _ptr(raw_dev), ncaptures, npairs, _ptr(iq_dev), int(normalise), DEVICE_PTRS))
+
+    def rx_stream(self, raw, state=None, normalise=True, iq=None, n_out=None):
+        """The RX front end with the filter state carried from slot to slot, as the reference's daemon runs it.
+        raw: uint8 [nstreams][nslots][2*npairs] host array (consecutive buffers of each receiver); state: RX_STATE_DTYPE
+        [nstreams] as a previous call returned it, or None for the reset state; iq / n_out: arrays to write into.
+        -> (float32 [nstreams][nslots][2][48000], uint32 [nstreams][nslots] stored counts, the exit state [nstreams])"""
+        raw = np.ascontiguousarray(raw, np.uint8)
+        nstreams, nslots, nbytes = raw.shape
+        if state is None:
+            state = np.zeros(nstreams, RX_STATE_DTYPE)
+        else:
+            state = np.array(state, RX_STATE_DTYPE, copy=True, ndmin=1)   # the caller's entry state stays as it is
+            assert state.shape == (nstreams,)
+        if iq is None:
+            iq = np.zeros((nstreams, nslots, 2, NSAMPLES), np.float32)
+        if n_out is None:
+            n_out = np.zeros((nstreams, nslots), np.uint32)
+        assert iq.dtype == np.float32 and iq.shape == (nstreams, nslots, 2, NSAMPLES) and iq.flags.c_contiguous
+        assert n_out.dtype == np.uint32 and n_out.shape == (nstreams, nslots) and n_out.flags.c_contiguous
+        self._ck(self.lib.ft8gpu_rx_stream(self.h, raw.ctypes.data, nstreams, nslots, nbytes // 2, state.ctypes.data,
+                                           iq.ctypes.data, n_out.ctypes.data, int(normalise), HOST_PTRS))
+        return iq, n_out, state
+
+    def rx_stream_dev(self, raw_dev, nstreams, nslots, npairs, state_dev, iq_dev, n_out_dev=None, normalise=True):
+        """all arrays in HBM: raw [nstreams][nslots][2*npairs] uint8, state [nstreams] 516-byte records (updated in place),
+        iq [nstreams][nslots][2][48000] float32, n_out [nstreams][nslots] uint32 or None"""
+        self._ck(self.lib.ft8gpu_rx_stream(self.h, _ptr(raw_dev), nstreams, nslots, npairs, _ptr(state_dev), _ptr(iq_dev),
+                                           _ptr(n_out_dev) if n_out_dev is not None else None, int(normalise), DEVICE_PTRS))
 
     def pskreporter_datagrams(self, decodes, n_results, info, unixtimes=None):
         """decodes: [n][50] RESULT_DTYPE, n_results: [n] -> (uint8 [n][DATAGRAM_STRIDE], int32 [n] lengths)"""

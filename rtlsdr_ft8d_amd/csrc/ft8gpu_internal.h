@@ -92,6 +92,10 @@ hipError_t run_norm_math_selftest(uint64_t out[7], hipStream_t s); // bp_selftes
 hipError_t decode_tables_init(hipStream_t s);   // uploads the LDPC edge tables used by the BP kernel
 hipError_t launch_rx(const uint8_t *raw, int ncaptures, size_t npairs, void *scratch_sums, void *scratch_base,
                      float *iq, int normalise, hipStream_t s);
+// rx_stream.hip: the same stage with the filter state carried (ft8gpu_rx_stream); scratch sizes from rx_stream_scratch
+void rx_stream_scratch(int nstreams, int nslots, size_t npairs, size_t *sums_bytes, size_t *p2_bytes);
+hipError_t launch_rx_stream(const uint8_t *raw, int nstreams, int nslots, size_t npairs, ft8gpu_rx_state *state,
+                            void *scratch_sums, void *scratch_p2, float *iq, uint32_t *n_out, int normalise, hipStream_t s);
 
 // f-4: everything of a PSKreporter datagram that does not depend on the frame (header, receiver and
 // sender templates, receiver record), assembled on the host once per call and passed by value
