@@ -310,6 +310,63 @@ int ft8gpu_mask_messages(ft8gpu_ctx *ctx, const uint8_t *mag, const uint8_t *bas
 int ft8gpu_append_messages(ft8gpu_ctx *ctx, const uint8_t *mag, const uint8_t *base, const ft8gpu_candidate *cands,
                            const int32_t *counts, const ft8gpu_decode_status *status, int nframes, ft8gpu_message *msgs,
                            int32_t *n_msgs, int flags);
+/* ---- ordered-statistics decoding (OSD) of the candidates belief propagation gives up on --------------------------------
+ * (DESIGN.md "Ordered-statistics decoding"; not in the reference, whose ft8_decode, rtlsdr_ft8d.c:1476, stops at BP.)
+ * A candidate whose status record has ok == 0 and ldpc_errors != 0 is decoded again from llr[0..173], the normalised soft
+ * bits BP starts from; a non-finite value means no attempt (result 6).  The rule is exact:
+ *   h[i] = llr[i] > 0;  w[i] = 255 if |llr[i]| >= 32.0f, else (int)(|llr[i]| * 8.0f)
+ *   positions sorted by the bit pattern of |llr[i]| as uint32, descending, ties by ascending i
+ *   G = the 91 x 174 generator (row k = the codeword of the message whose only set bit is k).  Walking its columns in the
+ *   sorted order, a column independent of the pivots so far becomes a pivot, up to 91; full reduction; R_k = the reduced
+ *   row with a 1 in the k-th pivot column (k = 0 the most reliable)
+ *   pattern 0 = c0 = XOR of the R_k whose pivot position has h = 1; order >= 1 adds 1 + k = c0 ^ R_k (k = 0..90); order 2
+ *   adds 92 + rank(i, j) = c0 ^ R_i ^ R_j, i < j in lexicographic order (4187 patterns in all)
+ *   metric = sum of w over the positions where a pattern differs from h, nhard = their number; the best pattern has the
+ *   smallest metric, ties go to the smallest index
+ * Only the best pattern is judged; the first failing check names the result: 5 all-zero, 2 nhard > max_hard_errors,
+ * 3 CRC-14 mismatch, 4 unpack77 < 0, else 1 = accepted.  On acceptance the status record becomes that of a BP success
+ * (ok = 1, ldpc_errors = 0, CRC fields, unpack_status, a91, text; iters as it was); otherwise it is unchanged. */
+typedef struct {
+    uint8_t  result;         /* 0 not attempted, 1 accepted, 2..5 the failing check, 6 non-finite soft bits (nothing searched) */
+    uint8_t  nhard;          /* the best pattern's values, accepted or not */
+    uint16_t pattern;
+    int32_t  metric;
+} ft8gpu_osd_info;
+/* Recommended max_hard_errors, from profiles/osd_gain.json (96 frames of 20 signals at -22..0 dB): at 27, order 1 keeps 17
+ * of the 32 messages OSD gains without a gate and order 2 keeps 30 of 45, and 232 / 955 of about 7100 failing candidates have
+ * a wrong best pattern within the gate -- each passes the CRC with probability 2^-14: 1.5e-4 / 6.1e-4 expected false
+ * decodes per frame.  At 31 those are 1.1e-3 / 2.4e-3 (DESIGN.md has the sweep). */
+#define FT8GPU_OSD_MAX_HARD_ERRORS 27
+/* stage entry: mag [nframes][94208], cands / status_in / status_out / info [nframes][max_candidates], counts [nframes].
+ * order in [0, 2], max_hard_errors in [0, 83].  Records below counts[f] are written (a candidate that does not qualify:
+ * status_out = status_in, info all zero), records at and behind it are not touched.  status_out may be status_in. */
+int ft8gpu_osd_candidates(ft8gpu_ctx *ctx, const uint8_t *mag, const ft8gpu_candidate *cands, const int32_t *counts,
+                          const ft8gpu_decode_status *status_in, int nframes, int order, int max_hard_errors,
+                          ft8gpu_decode_status *status_out, ft8gpu_osd_info *info, int flags);
+/* The whole path with OSD behind every pass.  Each pass runs as in ft8gpu_decode_messages_passes (sync, heap, LDPC, collect
+ * or append); then OSD runs on that pass's failures and the append step adds, in candidate order, the unique messages it
+ * gained (pad[0] of such a record = the pattern's nhard, >= 1; BP records keep 0).  The mask of the next pass uses all
+ * records so far.  n_by_stage [nframes][passes][2] (NULL: not written): the count after BP and after OSD of each pass.
+ * osd_order -1: no OSD, the records are those of ft8gpu_decode_messages_passes.  With passes = 1 the slots below the BP
+ * count are those of ft8gpu_decode_messages. */
+typedef struct {
+    int32_t passes;                 /* 1 .. FT8GPU_MAX_PASSES */
+    int32_t osd_order;              /* -1 (no OSD), 0, 1, 2 */
+    int32_t osd_max_hard_errors;    /* 0 .. 83; FT8GPU_OSD_MAX_HARD_ERRORS is the recommended value */
+} ft8gpu_deep_params;
+int ft8gpu_decode_messages_deep(ft8gpu_ctx *ctx, const float *iq, int nframes, const ft8gpu_deep_params *params,
+                                ft8gpu_message *msgs, int32_t *n_msgs, int32_t *n_by_stage, int flags);
+#ifndef __cplusplus
+_Static_assert(sizeof(ft8gpu_osd_info) == 8 && offsetof(ft8gpu_osd_info, nhard) == 1 && offsetof(ft8gpu_osd_info, pattern) == 2 &&
+               offsetof(ft8gpu_osd_info, metric) == 4, "ft8gpu_osd_info layout");
+_Static_assert(sizeof(ft8gpu_deep_params) == 12 && offsetof(ft8gpu_deep_params, osd_order) == 4 &&
+               offsetof(ft8gpu_deep_params, osd_max_hard_errors) == 8, "ft8gpu_deep_params layout");
+#else
+static_assert(sizeof(ft8gpu_osd_info) == 8 && offsetof(ft8gpu_osd_info, nhard) == 1 && offsetof(ft8gpu_osd_info, pattern) == 2 &&
+              offsetof(ft8gpu_osd_info, metric) == 4, "ft8gpu_osd_info layout");
+static_assert(sizeof(ft8gpu_deep_params) == 12 && offsetof(ft8gpu_deep_params, osd_order) == 4 &&
+              offsetof(ft8gpu_deep_params, osd_max_hard_errors) == 8, "ft8gpu_deep_params layout");
+#endif
 /* one line per message, "%3d %4.1f %4d ~  %s\n" of snr_db, dt_s, (int)freq_hz, text (NUL-terminated, truncated to cap);
  * returns the untruncated length.  Host-side text formatting, no GPU involved. */
 int ft8gpu_format_messages(const ft8gpu_message *msgs, int32_t n, char *out, size_t cap);

@@ -37,12 +37,20 @@ RX_STATE_DTYPE = np.dtype([(n, "<i4") for n in ("Ix1", "Ix2", "Qx1", "Qx2", "Iy1
 MESSAGE_DTYPE = np.dtype({"names": ["text", "snr_db", "score", "freq_hz", "dt_s", "hash", "cand_index", "cand", "a91", "pad"],
                           "formats": ["S25", "i1", "<i2", "<f4", "<f4", "<u2", "<u2", CAND_DTYPE, ("u1", (12,)), ("u1", (4,))],
                           "offsets": [0, 25, 26, 28, 32, 36, 38, 40, 48, 60], "itemsize": 64})
-assert RESULT_DTYPE.itemsize == 28 and CAND_DTYPE.itemsize == 8 and MESSAGE_DTYPE.itemsize == 64
+# ft8gpu_osd_info: what ordered-statistics decoding found for a candidate (ft8gpu_osd_candidates)
+OSD_INFO_DTYPE = np.dtype([("result", "u1"), ("nhard", "u1"), ("pattern", "<u2"), ("metric", "<i4")])
+OSD_MAX_HARD_ERRORS = 27    # FT8GPU_OSD_MAX_HARD_ERRORS, the recommended gate
+assert RESULT_DTYPE.itemsize == 28 and CAND_DTYPE.itemsize == 8 and MESSAGE_DTYPE.itemsize == 64 and OSD_INFO_DTYPE.itemsize == 8
 assert STATUS_DTYPE.itemsize == 48 and SIGNAL_DTYPE.itemsize == 92
 
 
 class Params(C.Structure):
     _fields_ = [("min_score", C.c_int32), ("max_candidates", C.c_int32), ("ldpc_iters", C.c_int32)]
+
+
+class DeepParams(C.Structure):
+    """ft8gpu_deep_params: passes 1..4, osd_order -1 (no OSD) .. 2, osd_max_hard_errors 0..83"""
+    _fields_ = [("passes", C.c_int32), ("osd_order", C.c_int32), ("osd_max_hard_errors", C.c_int32)]
 
 
 class Timings(C.Structure):
@@ -82,6 +90,7 @@ ABI_SYMBOLS = [
     "ft8gpu_shard_workers", "ft8gpu_decode_batch_multi", "ft8gpu_decode_batch_multi_dev",
     "ft8gpu_decode_messages", "ft8gpu_collect_messages", "ft8gpu_noise_baseline", "ft8gpu_format_messages",
     "ft8gpu_decode_messages_passes", "ft8gpu_mask_messages", "ft8gpu_append_messages",
+    "ft8gpu_osd_candidates", "ft8gpu_decode_messages_deep",
     "ft8_find_sync", "ft8_decode", "ft8_encode", "pack77",            # ft8_lib level (include/ft8_lib/ft8/*.h)
     "initFFTW", "freeFFTW", "ft8_subsystem", "ft8gpu_read_raw_iq", "ft8gpu_read_c2", "ft8gpu_write_raw_iq",
 ]
@@ -211,6 +220,9 @@ def _declare(L):
         L.ft8gpu_decode_messages_passes.argtypes = [vp, vp, C.c_int, C.c_int, vp, vp, vp, C.c_int]
         L.ft8gpu_mask_messages.argtypes = [vp, vp, vp, vp, vp, vp, C.c_int, vp, C.c_int]
         L.ft8gpu_append_messages.argtypes = [vp, vp, vp, vp, vp, vp, C.c_int, vp, vp, C.c_int]
+    if hasattr(L, "ft8gpu_osd_candidates"):               # absent from older builds loaded by load_library_at
+        L.ft8gpu_osd_candidates.argtypes = [vp, vp, vp, vp, vp, C.c_int, C.c_int, C.c_int, vp, vp, C.c_int]
+        L.ft8gpu_decode_messages_deep.argtypes = [vp, vp, C.c_int, C.POINTER(DeepParams), vp, vp, vp, C.c_int]
     L.ft8gpu_rx_decimate.argtypes = [vp, vp, C.c_int, C.c_size_t, vp, C.c_int, C.c_int]
     if hasattr(L, "ft8gpu_rx_stream"):                    # absent from older builds loaded by load_library_at
         L.ft8gpu_rx_stream.argtypes = [vp, vp, C.c_int, C.c_int, C.c_size_t, vp, vp, vp, C.c_int, C.c_int]
@@ -516,7 +528,51 @@ class Decoder:
                                                status.ctypes.data, B, msgs.ctypes.data, n.ctypes.data, HOST_PTRS))
         return msgs, n
 
+    def osd_candidates(self, mag, cands, counts, status_in, order=1, max_hard_errors=OSD_MAX_HARD_ERRORS, status_out=None, info=None):
+        """ft8gpu_osd_candidates -> (status_out [B][cap] STATUS_DTYPE, info [B][cap] OSD_INFO_DTYPE), new arrays; records at and
+        behind counts[f] keep what status_out / info held (zeros when None)"""
+        mag = np.ascontiguousarray(mag, np.uint8).reshape(-1, MAG_ARRAY)
+        B = mag.shape[0]
+        cands = np.ascontiguousarray(cands)
+        counts = np.ascontiguousarray(counts, np.int32)
+        status_in = np.ascontiguousarray(status_in).view(np.uint8).reshape(B, self.max_candidates, 48)
+        assert cands.shape == (B, self.max_candidates) and cands.dtype == CAND_DTYPE and counts.shape == (B,)
+        out = np.zeros((B, self.max_candidates, 48), np.uint8) if status_out is None else \
+            np.array(status_out, copy=True, order="C").view(np.uint8).reshape(B, self.max_candidates, 48)
+        inf = np.zeros((B, self.max_candidates), OSD_INFO_DTYPE) if info is None else \
+            np.array(info, copy=True, order="C").view(OSD_INFO_DTYPE).reshape(B, self.max_candidates)
+        self._ck(self.lib.ft8gpu_osd_candidates(self.h, mag.ctypes.data, cands.ctypes.data, counts.ctypes.data, status_in.ctypes.data,
+                                              B, int(order), int(max_hard_errors), out.ctypes.data, inf.ctypes.data, HOST_PTRS))
+        return out.view(STATUS_DTYPE).reshape(B, self.max_candidates), inf
+
+    def decode_messages_deep(self, iq, passes=1, osd_order=1, osd_max_hard_errors=OSD_MAX_HARD_ERRORS, msgs=None):
+        """ft8gpu_decode_messages_deep -> (msgs [B][50] MESSAGE_DTYPE, n_msgs [B], n_by_stage [B][passes][2]: the count after BP
+        and after OSD of each pass); slots past n_msgs[f] keep what `msgs` held (zeros when None)"""
+        iq = np.ascontiguousarray(iq, np.float32)
+        B = iq.shape[0]
+        assert iq.shape[1:] == (2, NSAMPLES)
+        if msgs is None:
+            msgs = np.zeros((B, MAX_MESSAGES), MESSAGE_DTYPE)
+        assert msgs.dtype == MESSAGE_DTYPE and msgs.shape == (B, MAX_MESSAGES) and msgs.flags["C_CONTIGUOUS"]
+        n = np.zeros(B, np.int32)
+        nbs = np.zeros((B, max(int(passes), 1), 2), np.int32)
+        p = DeepParams(int(passes), int(osd_order), int(osd_max_hard_errors))
+        self._ck(self.lib.ft8gpu_decode_messages_deep(self.h, iq.ctypes.data, B, C.byref(p), msgs.ctypes.data, n.ctypes.data,
+                                                    nbs.ctypes.data, HOST_PTRS))
+        return msgs, n, nbs
+
     # ---- device-pointer API (inputs and outputs resident in HBM) --------------------------------
+    def osd_candidates_dev(self, mag_dev, cands_dev, counts_dev, status_in_dev, nframes, order, max_hard_errors, status_out_dev, info_dev):
+        """status_out_dev may be status_in_dev; info_dev: [nframes][max_candidates] 8-byte records"""
+        self._ck(self.lib.ft8gpu_osd_candidates(self.h, _ptr(mag_dev), _ptr(cands_dev), _ptr(counts_dev), _ptr(status_in_dev), nframes,
+                                              int(order), int(max_hard_errors), _ptr(status_out_dev), _ptr(info_dev), DEVICE_PTRS))
+
+    def decode_messages_deep_dev(self, iq_dev, nframes, passes, osd_order, osd_max_hard_errors, msgs_dev, n_msgs_dev, n_by_stage_dev=None):
+        """n_by_stage_dev: [nframes][passes][2] int32, or None"""
+        p = DeepParams(int(passes), int(osd_order), int(osd_max_hard_errors))
+        self._ck(self.lib.ft8gpu_decode_messages_deep(self.h, _ptr(iq_dev), nframes, C.byref(p), _ptr(msgs_dev), _ptr(n_msgs_dev),
+                                                    None if n_by_stage_dev is None else _ptr(n_by_stage_dev), DEVICE_PTRS))
+
     def decode_messages_passes_dev(self, iq_dev, nframes, passes, msgs_dev, n_msgs_dev, n_by_pass_dev=None):
         """n_by_pass_dev: [nframes][passes] int32, or None"""
         self._ck(self.lib.ft8gpu_decode_messages_passes(self.h, _ptr(iq_dev), nframes, int(passes), _ptr(msgs_dev), _ptr(n_msgs_dev),

@@ -284,6 +284,7 @@ void ft8gpu_destroy(ft8gpu_ctx *c) {
                      c->d_rep, c->d_rep_len, c->d_rep_time, c->d_probe, c->d_base, c->d_msgtab, c->d_msgs };
     for (void *b : bufs) if (b) (void)hipFree(b);
     free_multipass_buffers(c);
+    free_osd_buffers(c);
     if (c->side) (void)hipStreamSynchronize(c->side);
     for (auto &slot : c->ev) for (auto &e : slot) if (e) (void)hipEventDestroy(e);
     for (auto &e : c->dep) if (e) (void)hipEventDestroy(e);

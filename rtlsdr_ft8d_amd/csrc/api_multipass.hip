@@ -3,8 +3,6 @@
 // "Multi-pass decoding").
 #include "ft8gpu_ctx.h"
 
-namespace {
-
 // the compact waterfall, the map, the counts before a pass and a candidate / status set of the context's cap, on the first
 // multi-pass call (ft8gpu_create's footprint is unchanged); the candidate set follows the cap when ft8gpu_set_params grows it
 int ensure_multipass_buffers(ft8gpu_ctx *c) {
@@ -29,6 +27,8 @@ int ensure_multipass_buffers(ft8gpu_ctx *c) {
     }
     return 0;
 }
+
+namespace {
 
 // passes 2.. on one chunk of n frames already through pass 1 (run_pipeline_messages): c->d_mag holds W1, c->d_base its
 // baseline, msgs / n_msgs the records so far.  nbp (nullable): [n][passes].

@@ -68,6 +68,12 @@ struct ft8gpu_ctx {
     ft8gpu_decode_status *d_status2 = nullptr;
     int cap2 = 0;
     int32_t *d_nbp = nullptr;              //   host-pointer staging of the per-pass counts [max_frames][FT8GPU_MAX_PASSES]
+    bool osd_tables = false;               // OSD, lazily on its first call: the constant tables are uploaded,
+    ft8gpu_osd_info *d_osd_info = nullptr; //   the info records [max_frames][osd_cap] and the host form's staging of status_out,
+    ft8gpu_decode_status *d_osd_out = nullptr;
+    int osd_cap = 0;
+    int32_t *d_nosd = nullptr;             //   the counts before the OSD append [max_frames], host staging of n_by_stage
+    int32_t *d_nbs = nullptr;              //   [max_frames][FT8GPU_MAX_PASSES][2]
     ft8gpu_synth_signal *d_sigs = nullptr;
     size_t sigs_cap = 0;
     void *d_rx_sums = nullptr, *d_rx_p2 = nullptr;     // RX front end scratch
@@ -148,8 +154,11 @@ int run_pipeline(ft8gpu_ctx *c, const float *d_iq, int n, struct decoder_results
 int run_pipeline_messages(ft8gpu_ctx *c, const float *d_iq, int n, ft8gpu_message *d_msgs, int32_t *d_nmsgs);
 // api_messages.hip: allocates d_base / d_msgtab on the first messages call
 int ensure_messages_buffers(ft8gpu_ctx *c);
-// api_multipass.hip: frees the multi-pass buffers (ft8gpu_destroy)
+// api_multipass.hip: frees the multi-pass buffers (ft8gpu_destroy); allocates them on the first multi-pass call
 void free_multipass_buffers(ft8gpu_ctx *c);
+int ensure_multipass_buffers(ft8gpu_ctx *c);
+// api_osd.hip: frees the OSD buffers (ft8gpu_destroy)
+void free_osd_buffers(ft8gpu_ctx *c);
 // ft8gpu_decode_batch with one more form: kIqOnDevice, frames resident on the context's GPU and records to host arrays
 // (used by the multi-GPU entries; not part of the ABI, whose entry passes on FT8GPU_DEVICE_PTRS only)
 constexpr int kIqOnDevice = 2;

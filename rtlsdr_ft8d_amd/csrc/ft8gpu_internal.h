@@ -85,6 +85,15 @@ hipError_t launch_append(const uint8_t *mag, const uint8_t *base, const ft8gpu_c
                          const ft8gpu_decode_status *status, const MsgTables *tab, const int32_t *map, int nslots,
                          int max_candidates, int min_score, ft8gpu_message *msgs, int32_t *n_msgs, hipStream_t s);
 hipError_t launch_pass_counts(const int32_t *n_msgs, int32_t *nbp, int nframes, int passes, int col0, hipStream_t s);
+// osd.hip: ordered-statistics decoding of the candidates BP gives up on (DESIGN.md "Ordered-statistics decoding");
+// osd_tables_init uploads the generator's column masks and the CRC table on the first OSD call
+hipError_t osd_tables_init(hipStream_t s);
+hipError_t launch_osd(const uint8_t *mag, const ft8gpu_candidate *cands, const int32_t *counts,
+                      const ft8gpu_decode_status *status_in, ft8gpu_decode_status *status_out, ft8gpu_osd_info *info,
+                      int nframes, int max_candidates, int order, int max_hard_errors, hipStream_t s);
+// pad[0] = nhard for the records [n_before[f], n_msgs[f]) of the frames behind the pass's slots (map == nullptr: slot = frame)
+hipError_t launch_osd_tag(const ft8gpu_osd_info *info, const int32_t *map, const int32_t *n_before, const int32_t *n_msgs,
+                          int nslots, int max_candidates, ft8gpu_message *msgs, hipStream_t s);
 hipError_t launch_synth(const ft8gpu_synth_signal *sig_dev, int nframes, int nsig, float noise_sigma,
                         uint64_t seed, uint64_t first_frame, float *iq, hipStream_t s);
 hipError_t run_bp_math_selftest(uint64_t out[7], hipStream_t s);   // bp_selftest.hip: exhaustive check of bp_math.h

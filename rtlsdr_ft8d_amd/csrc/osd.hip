@@ -1,0 +1,475 @@
+// osd.hip -- ordered-statistics decoding of the candidates belief propagation gives up on (DESIGN.md "Ordered-statistics
+// decoding").  Not part of the reference's path: a second chance for a candidate whose status record says ok == 0 and
+// ldpc_errors != 0.  The rule is exact (integers and float comparisons), restated in tests/ft8_spec_osd.py:
+//   soft bits as the LDPC kernel forms them (ft8_extract_likelihood, ftx_normalize_logl of ft8_lib decode.c, reached
+//   through ft8_decode, rtlsdr_ft8d.c:1476); hard decision h, 8-bit weights; positions sorted by |llr| bits descending;
+//   the 91 first independent columns of the generator in that order are the basis; reduced echelon form; the patterns
+//   c0, c0 ^ R_k, c0 ^ R_i ^ R_j; the one with the smallest (metric, index) is judged: all-zero, hard errors, CRC, unpack77.
+//
+// One wave64 per candidate, four per workgroup, the launch geometry of the LDPC kernel.  A wave whose candidate does not
+// qualify copies the record and leaves.  Everything else is wave-local:
+//   * sort: 174 keys in LDS, every lane counts the keys that precede its three (a rank, no exchange network);
+//   * the generator with its COLUMNS in sorted order: lane k fetches the column mask (91 row bits) of the position ranked k,
+//     and 91 x 3 ballots turn the column masks into rows -- lane l then holds rows l and 64 + l as three 64-bit words each,
+//     in registers, indexed by compile-time constants only (no scratch segment);
+//   * elimination walks the sorted columns in order: a ballot finds a row without a pivot that has the bit, six v_readlane
+//     broadcast it, every other row with the bit takes the XOR.  It stops at the 91st pivot;
+//   * metric of a pattern = sum of weights over its difference from h.  The weights are kept as eight bit planes (ballots),
+//     so a metric is 24 and / popcount pairs on 64-bit words instead of 174 table steps;
+//   * search: the reduced rows go to LDS by pivot ordinal; order 1 is two rows per lane, order 2 walks i on the scalar side
+//     and spreads j over the lanes.  (metric << 13 | index) through one butterfly minimum is the best pattern with the
+//     rule's tie break;
+//   * the best pattern returns to codeword order through the ranks, and the epilogue is the LDPC kernel's: CRC-14 by
+//     linearity, unpack77 on two 64-bit words, the 48-byte record composed in LDS.
+#include "ft8gpu_internal.h"
+#include "ft8_tables.h"
+#include "unpack_dev.h"
+#include "bp_math.h"
+#include <stddef.h>
+
+namespace {
+
+struct OsdTables {
+    uint32_t col[kLdpcN][4];      // column c of the generator as a row mask: rows 0..31, 32..63, 64..90, 0
+    uint16_t crc_bit[77];         // CRC-14 (over 82 bits) of the message whose only set bit is payload bit i
+};
+
+__device__ OsdTables d_osd;
+__constant__ uint8_t c_osd_gray[8] = { 0, 1, 3, 2, 5, 6, 4, 7 };
+
+constexpr int kRowStride = 7;                          // dwords between reduced rows in LDS (odd: conflict-free per lane)
+constexpr int kOffPerm = 192, kOffRows = 384, kOffCw = kOffRows + kLdpcK * kRowStride + 3, kOffRec = kOffCw + 8;
+constexpr int kOsdLds = kOffRec + 12;
+static_assert(kOffCw % 2 == 0 && kOffRec % 4 == 0, "LDS areas keep their alignment");
+
+__device__ __forceinline__ void wave_lds_sync() {
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+}
+
+__device__ __forceinline__ int wave_sum(int v) {
+#pragma unroll
+    for (int m = 1; m < 64; m <<= 1) v += __shfl_xor(v, m);
+    return __builtin_amdgcn_readfirstlane(v);
+}
+__device__ __forceinline__ uint32_t wave_xor(uint32_t v) {
+#pragma unroll
+    for (int m = 1; m < 64; m <<= 1) v ^= (uint32_t)__shfl_xor((int)v, m);
+    return (uint32_t)__builtin_amdgcn_readfirstlane((int)v);
+}
+__device__ __forceinline__ uint64_t wave_xor64(uint64_t v) {
+    return (uint64_t)wave_xor((uint32_t)v) | ((uint64_t)wave_xor((uint32_t)(v >> 32)) << 32);
+}
+__device__ __forceinline__ uint32_t wave_min(uint32_t v) {
+#pragma unroll
+    for (int m = 1; m < 64; m <<= 1) v = min(v, (uint32_t)__shfl_xor((int)v, m));
+    return (uint32_t)__builtin_amdgcn_readfirstlane((int)v);
+}
+__device__ __forceinline__ uint64_t readlane64(uint64_t v, int l) {
+    const uint32_t lo = (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)v, l);
+    const uint32_t hi = (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)(v >> 32), l);
+    return (uint64_t)lo | ((uint64_t)hi << 32);
+}
+
+// a reduced row from LDS (six dwords at an odd stride)
+__device__ __forceinline__ void load_row(const uint32_t *rows, int k, uint64_t x[3]) {
+    const uint32_t *p = rows + k * kRowStride;
+#pragma unroll
+    for (int j = 0; j < 3; ++j) x[j] = (uint64_t)p[2 * j] | ((uint64_t)p[2 * j + 1] << 32);
+}
+
+// sum of the weights over the set bits of x: weights as eight bit planes
+__device__ __forceinline__ uint32_t metric_of(const uint64_t x[3], const uint64_t (&P)[8][3]) {
+    uint32_t m = 0;
+#pragma unroll
+    for (int b = 0; b < 8; ++b)
+        m += (uint32_t)(__popcll(x[0] & P[b][0]) + __popcll(x[1] & P[b][1]) + __popcll(x[2] & P[b][2])) << b;
+    return m;
+}
+
+constexpr uint32_t kKeyNone = 0xFFFFFFFFu;
+constexpr int kPatShift = 13;                          // 4187 patterns < 2^13; metric <= 174 * 255 < 2^16
+
+__global__ __launch_bounds__(256)
+void ft8_osd_kernel(const uint8_t *__restrict__ mag, const ft8gpu_candidate *__restrict__ cands,
+                    const int32_t *__restrict__ counts, const ft8gpu_decode_status *status_in,
+                    ft8gpu_decode_status *status_out, ft8gpu_osd_info *info, int nframes, int max_candidates,
+                    int order, int max_hard_errors, unsigned blocks_per_frame) {
+    __shared__ __attribute__((aligned(16))) uint32_t s_mem[4][kOsdLds];
+
+    const int lane = threadIdx.x & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const int frame = (int)(blockIdx.x / blocks_per_frame);
+    const int ci = (int)(blockIdx.x - (unsigned)frame * blocks_per_frame) * 4 + wave;
+    if (frame >= nframes || ci >= max_candidates) return;
+    if (ci >= counts[frame]) return;                                  // wave-uniform: records behind the count are not touched
+
+    const size_t rec_index = (size_t)frame * max_candidates + ci;
+    const uint32_t *in32 = reinterpret_cast<const uint32_t *>(status_in + rec_index);
+    uint32_t *out32 = reinterpret_cast<uint32_t *>(status_out + rec_index);
+    uint32_t *info32 = reinterpret_cast<uint32_t *>(info + rec_index);
+    static_assert(sizeof(ft8gpu_decode_status) == 48 && sizeof(ft8gpu_osd_info) == 8, "record sizes");
+
+    // ---- which candidates: ok == 0 and ldpc_errors != 0 (status_out may be status_in: read first) -------------------
+    const uint32_t mine = lane < 12 ? in32[lane] : 0u;
+    const uint32_t dw0 = (uint32_t)__builtin_amdgcn_readlane((int)mine, 0);
+    const uint32_t dw2 = (uint32_t)__builtin_amdgcn_readlane((int)mine, 2);
+    const bool attempt = ((dw2 >> 8) & 0xFFu) == 0u && (dw0 & 0xFFFFu) != 0u;
+    if (!attempt) {
+        if (lane < 12 && out32 != in32) out32[lane] = mine;
+        if (lane < 2) info32[lane] = 0u;
+        return;
+    }
+
+    uint32_t *s = s_mem[wave];
+    float *llr = reinterpret_cast<float *>(s);
+    uint32_t *perm = s + kOffPerm;
+    uint32_t *rows = s + kOffRows;
+
+    const ft8gpu_candidate cand = cands[rec_index];
+
+    // ---- ft8_extract_likelihood, ftx_normalize_logl: the LDPC kernel's arithmetic (decode.hip) ------------------------
+    if (lane < 58) {
+        const int k = lane;
+        const int sym = k + ((k < 29) ? 7 : 14);
+        const int block = cand.time_offset + sym;
+        int l0 = 0, l1 = 0, l2 = 0;
+        if (block >= 0 && block < kNumBlocks) {
+            const int index = ((cand.time_offset * 2 + cand.time_sub) * 2 + cand.freq_sub) * kNumBin + cand.freq_offset;
+            const uint8_t *ps = mag + (size_t)frame * kMagArray + index + sym * kBlockStride;
+            int s2[8];
+#pragma unroll
+            for (int j = 0; j < 8; ++j) s2[j] = ps[c_osd_gray[j]];
+            l0 = max(max(s2[4], s2[5]), max(s2[6], s2[7])) - max(max(s2[0], s2[1]), max(s2[2], s2[3]));
+            l1 = max(max(s2[2], s2[3]), max(s2[6], s2[7])) - max(max(s2[0], s2[1]), max(s2[4], s2[5]));
+            l2 = max(max(s2[1], s2[3]), max(s2[5], s2[7])) - max(max(s2[0], s2[2]), max(s2[4], s2[6]));
+        }
+        llr[3 * k + 0] = (float)l0;
+        llr[3 * k + 1] = (float)l1;
+        llr[3 * k + 2] = (float)l2;
+    }
+    wave_lds_sync();
+
+    float cw[3];
+    bool has[3];
+    int isum = 0, isum2 = 0;
+#pragma unroll
+    for (int r = 0; r < 3; ++r) {
+        const int n = lane + 64 * r;
+        has[r] = n < kLdpcN;
+        cw[r] = has[r] ? llr[n] : 0.0f;
+        const int v = (int)cw[r];
+        isum += v;
+        isum2 += v * v;
+    }
+    const float sum = (float)wave_sum(isum);
+    const float sum2 = (float)wave_sum(isum2);
+    const float inv_n = 1.0f / 174;
+    const float variance = (sum2 - (sum * sum * inv_n)) * inv_n;
+    const float norm_factor = bpm::llr_norm_factor(variance);
+    bool finite = true;
+#pragma unroll
+    for (int r = 0; r < 3; ++r) {
+        cw[r] = has[r] ? cw[r] * norm_factor : 0.0f;
+        finite = finite && (__float_as_uint(cw[r]) & 0x7F800000u) != 0x7F800000u;
+    }
+    if (!__all(finite)) {                                             // wave-uniform: nothing is searched
+        if (lane < 12 && out32 != in32) out32[lane] = mine;
+        if (lane < 2) info32[lane] = lane == 0 ? 6u : 0u;
+        return;
+    }
+
+    // ---- order: rank of each position among the keys (|llr| bits descending, ties by ascending position) -----------
+    wave_lds_sync();                                                  // every lane has read the raw values
+    uint32_t key[3];
+#pragma unroll
+    for (int r = 0; r < 3; ++r) {
+        key[r] = __float_as_uint(cw[r]) & 0x7FFFFFFFu;
+        if (has[r]) s[lane + 64 * r] = __float_as_uint(cw[r]);
+    }
+    wave_lds_sync();
+    int rank[3] = { 0, 0, 0 };
+    for (int j = 0; j < kLdpcN; ++j) {
+        const uint32_t kj = s[j] & 0x7FFFFFFFu;                       // same address in every lane: a broadcast read
+#pragma unroll
+        for (int r = 0; r < 3; ++r) rank[r] += (kj > key[r] || (kj == key[r] && j < lane + 64 * r)) ? 1 : 0;
+    }
+#pragma unroll
+    for (int r = 0; r < 3; ++r)
+        if (has[r]) perm[rank[r]] = (uint32_t)(lane + 64 * r);
+    wave_lds_sync();
+
+    // ---- the sorted view: lane k & 63, slot k >> 6 holds sorted position k -----------------------------------------
+    uint64_t Hs[3], P[8][3];                                          // hard decisions and weight planes, wave-uniform
+    uint64_t CL[3];                                                   // column masks of the generator: rows 0..63
+    uint32_t CH[3];                                                   //                                 rows 64..90
+#pragma unroll
+    for (int q = 0; q < 3; ++q) {
+        const int k = lane + 64 * q;
+        const bool valid = k < kLdpcN;
+        const int n = valid ? (int)perm[k] : 0;
+        const uint32_t bits = s[n];
+        const float a = __uint_as_float(bits & 0x7FFFFFFFu);
+        const bool hbit = valid && (bits >> 31) == 0u && (bits & 0x7FFFFFFFu) != 0u;       // llr > 0
+        int w = a >= 32.0f ? 255 : (int)(a * 8.0f);
+        w = valid ? w : 0;
+        Hs[q] = __ballot(hbit);
+#pragma unroll
+        for (int b = 0; b < 8; ++b) P[b][q] = __ballot((w >> b) & 1);
+        const uint32_t *col = d_osd.col[n];
+        CL[q] = valid ? ((uint64_t)col[0] | ((uint64_t)col[1] << 32)) : 0ull;
+        CH[q] = valid ? col[2] : 0u;
+    }
+
+    // ---- rows from column masks: row r of slot q is the ballot of bit r ----------------------------------------------
+    uint64_t R0[3] = { 0ull, 0ull, 0ull }, R1[3] = { 0ull, 0ull, 0ull };   // rows lane and 64 + lane (lanes 0..26)
+    for (int r = 0; r < 64; ++r) {
+#pragma unroll
+        for (int q = 0; q < 3; ++q) {
+            const uint64_t bal = __ballot((int)((CL[q] >> r) & 1ull));
+            if (lane == r) R0[q] = bal;
+        }
+    }
+    for (int r = 0; r < kLdpcK - 64; ++r) {
+#pragma unroll
+        for (int q = 0; q < 3; ++q) {
+            const uint64_t bal = __ballot((int)((CH[q] >> r) & 1u));
+            if (lane == r) R1[q] = bal;
+        }
+    }
+
+    // ---- elimination over the sorted columns, full reduction; pivot ordinals and pivot columns per row ----------------
+    bool used0 = false, used1 = false;
+    int ord0 = 0, ord1 = 0, pk0 = 0, pk1 = 0;
+    int npiv = 0;
+#pragma unroll
+    for (int q = 0; q < 3; ++q) {
+        for (int b = 0; b < 64 && npiv < kLdpcK; ++b) {
+            const bool bit0 = ((R0[q] >> b) & 1ull) != 0ull, bit1 = ((R1[q] >> b) & 1ull) != 0ull;
+            const uint64_t m0 = __ballot(bit0 && !used0), m1 = __ballot(bit1 && !used1);
+            if ((m0 | m1) == 0ull) continue;                          // depends on the pivots so far (or k >= 174: all zero)
+            uint64_t piv[3];
+            bool me0 = false, me1 = false;
+            if (m0 != 0ull) {
+                const int p = __builtin_ctzll(m0);
+#pragma unroll
+                for (int j = 0; j < 3; ++j) piv[j] = readlane64(R0[j], p);
+                me0 = lane == p;
+            } else {
+                const int p = __builtin_ctzll(m1);
+#pragma unroll
+                for (int j = 0; j < 3; ++j) piv[j] = readlane64(R1[j], p);
+                me1 = lane == p;
+            }
+            if (me0) { used0 = true; ord0 = npiv; pk0 = 64 * q + b; }
+            if (me1) { used1 = true; ord1 = npiv; pk1 = 64 * q + b; }
+            const bool x0 = bit0 && !me0, x1 = bit1 && !me1;
+#pragma unroll
+            for (int j = 0; j < 3; ++j) {
+                R0[j] ^= x0 ? piv[j] : 0ull;
+                R1[j] ^= x1 ? piv[j] : 0ull;
+            }
+            ++npiv;
+        }
+    }
+    // (the generator has rank 91: every row is a pivot row now)
+
+    // ---- reduced rows to LDS by pivot ordinal; c0 = XOR of the rows whose pivot position has h = 1 ---------------------
+    const bool has1 = lane < kLdpcK - 64;
+    {
+        uint32_t *p0 = rows + ord0 * kRowStride;
+#pragma unroll
+        for (int j = 0; j < 3; ++j) { p0[2 * j] = (uint32_t)R0[j]; p0[2 * j + 1] = (uint32_t)(R0[j] >> 32); }
+        if (has1) {
+            uint32_t *p1 = rows + ord1 * kRowStride;
+#pragma unroll
+            for (int j = 0; j < 3; ++j) { p1[2 * j] = (uint32_t)R1[j]; p1[2 * j + 1] = (uint32_t)(R1[j] >> 32); }
+        }
+    }
+    const uint64_t hw0 = pk0 < 64 ? Hs[0] : (pk0 < 128 ? Hs[1] : Hs[2]);
+    const uint64_t hw1 = pk1 < 64 ? Hs[0] : (pk1 < 128 ? Hs[1] : Hs[2]);
+    const bool inc0 = ((hw0 >> (pk0 & 63)) & 1ull) != 0ull;
+    const bool inc1 = has1 && ((hw1 >> (pk1 & 63)) & 1ull) != 0ull;
+    uint64_t D[3];                                                    // c0 ^ h: where pattern 0 differs from the hard decision
+#pragma unroll
+    for (int j = 0; j < 3; ++j) D[j] = wave_xor64((inc0 ? R0[j] : 0ull) ^ (inc1 ? R1[j] : 0ull)) ^ Hs[j];
+    wave_lds_sync();
+
+    // ---- search --------------------------------------------------------------------------------------------------------
+    uint32_t best = lane == 0 ? (metric_of(D, P) << kPatShift) : kKeyNone;
+    if (order >= 1) {
+#pragma unroll
+        for (int r = 0; r < 2; ++r) {
+            const int k = lane + 64 * r;
+            if (k < kLdpcK) {
+                uint64_t x[3];
+                load_row(rows, k, x);
+#pragma unroll
+                for (int j = 0; j < 3; ++j) x[j] ^= D[j];
+                best = min(best, (metric_of(x, P) << kPatShift) | (uint32_t)(1 + k));
+            }
+        }
+    }
+    if (order >= 2) {
+        int base = 1 + kLdpcK;                                        // index of the pair (i, i + 1)
+        for (int i = 0; i < kLdpcK - 1; ++i) {
+            uint64_t di[3];
+            load_row(rows, i, di);                                    // broadcast
+#pragma unroll
+            for (int j = 0; j < 3; ++j) di[j] ^= D[j];
+            for (int jj = i + 1 + lane; jj < kLdpcK; jj += 64) {
+                uint64_t x[3];
+                load_row(rows, jj, x);
+#pragma unroll
+                for (int j = 0; j < 3; ++j) x[j] ^= di[j];
+                best = min(best, (metric_of(x, P) << kPatShift) | (uint32_t)(base + (jj - i - 1)));
+            }
+            base += kLdpcK - 1 - i;
+        }
+    }
+    best = wave_min(best);
+    const int pattern = (int)(best & ((1u << kPatShift) - 1u));
+    const uint32_t metric = best >> kPatShift;
+
+    // ---- the best pattern again, in sorted order, then back to codeword order through the ranks ----------------------
+    uint64_t X[3] = { D[0], D[1], D[2] };
+    if (pattern >= 1) {                                               // wave-uniform
+        int i = pattern - 1, j2 = -1;
+        if (pattern > kLdpcK) {
+            int q = pattern - 1 - kLdpcK;
+            i = 0;
+            while (q >= kLdpcK - 1 - i) { q -= kLdpcK - 1 - i; ++i; }
+            j2 = i + 1 + q;
+        }
+        uint64_t x[3];
+        load_row(rows, i, x);
+#pragma unroll
+        for (int j = 0; j < 3; ++j) X[j] ^= x[j];
+        if (j2 >= 0) {
+            load_row(rows, j2, x);
+#pragma unroll
+            for (int j = 0; j < 3; ++j) X[j] ^= x[j];
+        }
+    }
+    const int nhard = __popcll(X[0]) + __popcll(X[1]) + __popcll(X[2]);
+    uint32_t *cwl = s + kOffCw;
+    if (lane < 3) {
+        const uint64_t c = lane == 0 ? (X[0] ^ Hs[0]) : (lane == 1 ? (X[1] ^ Hs[1]) : (X[2] ^ Hs[2]));
+        cwl[2 * lane] = (uint32_t)c;
+        cwl[2 * lane + 1] = (uint32_t)(c >> 32);
+    }
+    wave_lds_sync();
+    bool cbit[3];
+#pragma unroll
+    for (int r = 0; r < 3; ++r) cbit[r] = has[r] && ((cwl[rank[r] >> 5] >> (rank[r] & 31)) & 1u) != 0u;
+    const uint64_t B0 = __ballot(cbit[0]), B1 = __ballot(cbit[1]), B2 = __ballot(cbit[2]);
+
+    // ---- judge the best pattern: all-zero, hard errors, CRC, unpack77 -------------------------------------------------
+    uint32_t *rec32 = s + kOffRec;
+    char *rec = reinterpret_cast<char *>(rec32);
+    const uint64_t w0 = __brevll(B0);                                 // codeword bits 0..63, MSB first
+    const uint64_t w1 = __brevll(B1) & 0xFFFFFFE000000000ull;         // bits 64..90
+    int result;
+    if ((B0 | B1 | B2) == 0ull) result = 5;
+    else if (nhard > max_hard_errors) result = 2;
+    else {
+        uint32_t c = ((B0 >> lane) & 1ull) ? d_osd.crc_bit[lane] : 0u;
+        if (lane < 13 && ((B1 >> lane) & 1ull)) c ^= d_osd.crc_bit[64 + lane];
+        const uint32_t crc_calc = wave_xor(c);
+        const uint32_t crc_extracted = (uint32_t)(w1 >> 37) & 0x3FFFu;
+        if (crc_extracted != crc_calc) result = 3;
+        else {
+            // the record of a BP success (decode.hip), iters as it was
+            static_assert(offsetof(ft8gpu_decode_status, a91) == 10 && offsetof(ft8gpu_decode_status, text) == 22, "record layout");
+            if (lane < 12) {
+                const uint32_t hi0 = (uint32_t)(w0 >> 32), lo0 = (uint32_t)w0, hi1 = (uint32_t)(w1 >> 32);
+                uint32_t v = 0;
+                if (lane == 0) v = dw0 & 0xFFFF0000u;
+                else if (lane == 1) v = crc_extracted | (crc_calc << 16);
+                else if (lane == 2) v = (__builtin_bswap32(hi0) & 0xFFFFu) << 16;
+                else if (lane == 3) v = (__builtin_bswap32(hi0) >> 16) | (__builtin_bswap32(lo0) << 16);
+                else if (lane == 4) v = (__builtin_bswap32(lo0) >> 16) | (__builtin_bswap32(hi1) << 16);
+                else if (lane == 5) v = __builtin_bswap32(hi1) >> 16;
+                rec32[lane] = v;
+            }
+            wave_lds_sync();
+            int rc = 0;
+            if (lane == 0) {
+                rc = ft8dev::unpack77(w0, w1 & 0xFFF8000000000000ull, rec + offsetof(ft8gpu_decode_status, text));
+                rec[offsetof(ft8gpu_decode_status, unpack_status)] = (char)rc;
+                rec[offsetof(ft8gpu_decode_status, ok)] = 1;
+            }
+            rc = __builtin_amdgcn_readfirstlane(rc);
+            wave_lds_sync();
+            result = rc < 0 ? 4 : 1;
+        }
+    }
+    if (lane < 12 && (result == 1 || out32 != in32)) out32[lane] = result == 1 ? rec32[lane] : mine;
+    if (lane == 0) {
+        info32[0] = (uint32_t)result | ((uint32_t)nhard << 8) | ((uint32_t)pattern << 16);
+        info32[1] = metric;
+    }
+}
+
+// pad[0] of the message records OSD gained: the hard errors of the pattern behind them.  One wave per slot of the pass.
+__global__ __launch_bounds__(256)
+void ft8_osd_tag_kernel(const ft8gpu_osd_info *__restrict__ info, const int32_t *__restrict__ map,
+                        const int32_t *__restrict__ n_before, const int32_t *__restrict__ n_msgs, int nslots,
+                        int max_candidates, ft8gpu_message *__restrict__ msgs) {
+    const int slot = blockIdx.x * 4 + (threadIdx.x >> 6), r = threadIdx.x & 63;
+    if (slot >= nslots) return;
+    const int frame = map ? map[slot] : slot;
+    int lo = n_before[frame], hi = n_msgs[frame];
+    lo = lo < 0 ? 0 : lo;
+    hi = hi > kMaxMessages ? kMaxMessages : hi;
+    if (r < lo || r >= hi) return;
+    ft8gpu_message *m = msgs + (size_t)frame * kMaxMessages + r;
+    const int ci = m->cand_index;
+    if (ci < max_candidates) m->pad[0] = info[(size_t)slot * max_candidates + ci].nhard;
+}
+
+}  // namespace
+
+hipError_t osd_tables_init(hipStream_t s) {
+    static OsdTables h;
+    for (int c = 0; c < kLdpcN; ++c) {
+        uint32_t m[4] = { 0, 0, 0, 0 };
+        for (int k = 0; k < kLdpcK; ++k) {
+            // row k of the generator: the identity, then parity m covers message bit k when that bit of generator row m is set
+            const int bit = c < kLdpcK ? (c == k) : ((kFT8_generator[c - kLdpcK][k >> 3] >> (7 - (k & 7))) & 1);
+            if (bit) m[k >> 5] |= 1u << (k & 31);
+        }
+        for (int j = 0; j < 4; ++j) h.col[c][j] = m[j];
+    }
+    for (int i = 0; i < 77; ++i) {
+        // CRC-14, polynomial 0x2757, of the 82-bit message (77 payload bits, five zeros) whose only set bit is i
+        uint32_t rem = 0;
+        for (int bit = 0; bit < 82; ++bit) {
+            if (bit == i) rem ^= 0x2000u;
+            rem = (rem & 0x2000u) ? ((rem << 1) ^ 0x2757u) & 0x3FFFu : (rem << 1) & 0x3FFFu;
+        }
+        h.crc_bit[i] = (uint16_t)rem;
+    }
+    return hipMemcpyToSymbolAsync(HIP_SYMBOL(d_osd), &h, sizeof(h), 0, hipMemcpyHostToDevice, s);
+}
+
+hipError_t launch_osd(const uint8_t *mag, const ft8gpu_candidate *cands, const int32_t *counts,
+                      const ft8gpu_decode_status *status_in, ft8gpu_decode_status *status_out, ft8gpu_osd_info *info,
+                      int nframes, int max_candidates, int order, int max_hard_errors, hipStream_t s) {
+    if (nframes < 1) return hipSuccess;
+    const unsigned bpf = (unsigned)(max_candidates + 3) / 4;
+    const unsigned long long nblocks = (unsigned long long)nframes * bpf;
+    if (nblocks >= (1ull << 31)) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(ft8_osd_kernel, dim3((unsigned)nblocks), dim3(256), 0, s, mag, cands, counts, status_in, status_out, info,
+                       nframes, max_candidates, order, max_hard_errors, bpf);
+    return hipGetLastError();
+}
+
+hipError_t launch_osd_tag(const ft8gpu_osd_info *info, const int32_t *map, const int32_t *n_before, const int32_t *n_msgs,
+                          int nslots, int max_candidates, ft8gpu_message *msgs, hipStream_t s) {
+    if (nslots < 1) return hipSuccess;
+    hipLaunchKernelGGL(ft8_osd_tag_kernel, dim3((nslots + 3) / 4), dim3(256), 0, s, info, map, n_before, n_msgs, nslots,
+                       max_candidates, msgs);
+    return hipGetLastError();
+}

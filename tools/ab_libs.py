@@ -2,7 +2,8 @@
 """A/B of two (or more) BUILDS of libft8gpu.so in ONE process and GPU session -- boxes of the pool differ by several
 percent, so only arms that share a box and a session are comparable.  Every arm decodes the same batch; arms are
 interleaved round by round; the records of all arms must be byte-identical.
-  python tools/ab_libs.py --libs tools/ab/libft8gpu_prev.so rtlsdr_ft8d_amd/libft8gpu.so [--config 2|4] [--rounds 3]"""
+  python tools/ab_libs.py --libs tools/ab/libft8gpu_prev.so rtlsdr_ft8d_amd/libft8gpu.so [--config 2|4] [--rounds 3] [--entry batch|messages]
+--entry messages times ft8gpu_decode_messages (64-byte records of every message) instead of ft8gpu_decode_batch."""
 import argparse
 import hashlib
 import json
@@ -21,6 +22,7 @@ def main():
     ap.add_argument("--config", type=int, default=2, choices=(2, 4))
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--rounds", type=int, default=3)
+    ap.add_argument("--entry", choices=("batch", "messages"), default="batch")
     ap.add_argument("--torch-stream", action="store_true", help="run every arm on a torch.cuda.Stream (as bench.py does) instead of the context's own stream")
     args = ap.parse_args()
     import torch
@@ -39,19 +41,20 @@ def main():
     sig, _ = workload.frame_signals(0, B, cfg["nsig"], tones, snr_range=cfg["snr"])
     iq = torch.empty((B, 2, ft8.NSAMPLES), dtype=torch.float32, device="cuda")
     decs[0].synth_frames(sig, B, cfg["nsig"], 1.0, workload.SEED_BASE, iq)
-    spots = torch.zeros((B, 1400), dtype=torch.uint8, device="cuda")
+    spots = torch.zeros((B, 1400 if args.entry == "batch" else 50 * 64), dtype=torch.uint8, device="cuda")
     nres = torch.zeros((B,), dtype=torch.int32, device="cuda")
     torch.cuda.synchronize()
     res = [{"lib": p, "ms": [], "stages": None, "digest": None} for p in args.libs]
+    run = (lambda d: d.decode_batch_dev(iq, B, spots, nres)) if args.entry == "batch" else (lambda d: d.decode_messages_dev(iq, B, spots, nres))
     for _ in range(args.rounds):
         for dec, r in zip(decs, res):
             for _ in range(3):
-                dec.decode_batch_dev(iq, B, spots, nres)
+                run(dec)
             dec.synchronize()
             dec.enable_timing(True)
             t0 = time.perf_counter()
             for _ in range(args.steps):
-                dec.decode_batch_dev(iq, B, spots, nres)
+                run(dec)
             r.setdefault("host_enqueue_ms", []).append(round(1e3 * (time.perf_counter() - t0) / args.steps, 4))
             dec.synchronize()
             r["ms"].append(round(1e3 * (time.perf_counter() - t0) / args.steps, 4))
@@ -61,7 +64,7 @@ def main():
             r["digest"] = hashlib.sha256(spots.cpu().numpy().tobytes() + nres.cpu().numpy().tobytes()).hexdigest()[:16]
     for r in res:
         r["best_ms"] = min(r["ms"])
-    out = {"frames": B, "config": args.config, "steps": args.steps, "arms": res,
+    out = {"frames": B, "config": args.config, "entry": args.entry, "steps": args.steps, "arms": res,
            "all_digests_equal": len({r["digest"] for r in res}) == 1}
     for d in decs:
         d.close()
