@@ -174,9 +174,9 @@ def check(got_msgs, got_n, want_msgs, want_n):
     return None
 
 
-def oracle_stages(oracle, iq, max_candidates=120, min_score=10, nthreads=8):
+def oracle_stages(oracle, iq, max_candidates=120, min_score=10, nthreads=8, iters=20):
     """oracle waterfall / find_sync / decode of B frames [B][2][48000] -> (mag, cands, counts, status uint8 [B][cap][48])"""
     mag = oracle.waterfall_batch(iq, nthreads=nthreads)
     cands, counts = oracle.find_sync_batch(mag, max_candidates, min_score, nthreads=nthreads)
-    status = oracle.decode_candidates_batch(mag, cands, counts, nthreads=nthreads)
+    status = oracle.decode_candidates_batch(mag, cands, counts, iters=iters, nthreads=nthreads)
     return mag, cands, counts, status

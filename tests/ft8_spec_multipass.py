@@ -92,11 +92,11 @@ def append(mag, base, cands, counts, status, msgs, n_msgs, min_score=10):
     return out, n
 
 
-def decode_passes(oracle, iq, passes, max_candidates=120, min_score=10, nthreads=8, msgs=None, stages=None):
+def decode_passes(oracle, iq, passes, max_candidates=120, min_score=10, nthreads=8, msgs=None, stages=None, iters=20):
     """the whole path for B frames [B][2][48000] -> (msgs [B][50], n [B], n_by_pass [B][passes]).
     stages: the first pass's oracle stages (mag, cands, counts, status) when the caller has them already."""
     import rtlsdr_ft8d_amd as ft8
-    mag, cands, counts, status = stages if stages is not None else sm.oracle_stages(oracle, iq, max_candidates, min_score, nthreads)
+    mag, cands, counts, status = stages if stages is not None else sm.oracle_stages(oracle, iq, max_candidates, min_score, nthreads, iters)
     B = mag.shape[0]
     out, n = sm.collect(mag, cands, counts, status, min_score=min_score,
                         msgs=np.zeros((B, MAX_MESSAGES), ft8.MESSAGE_DTYPE) if msgs is None else msgs)
@@ -111,7 +111,7 @@ def decode_passes(oracle, iq, passes, max_candidates=120, min_score=10, nthreads
             a = np.array(active)
             W[a] = mask(W[a], base[a], out[a], prev[a], n[a])
             c2, k2 = oracle.find_sync_batch(W[a], max_candidates, min_score, nthreads=nthreads)
-            s2 = oracle.decode_candidates_batch(W[a], c2, k2, nthreads=nthreads)
+            s2 = oracle.decode_candidates_batch(W[a], c2, k2, iters=iters, nthreads=nthreads)
             prev = n.copy()
             o2, n2 = append(W[a], base[a], c2, k2, s2, out[a], n[a], min_score=min_score)
             out[a], n[a] = o2, n2

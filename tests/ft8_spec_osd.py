@@ -81,8 +81,9 @@ def sort_order(llr):
     return np.lexsort((np.arange(N), -key))              # primary: key descending; ties: index ascending
 
 
-def reduced_basis(order_idx):
-    """(basis positions in reliability order [91], R uint8 [91][174] with R[k] the reduced row of basis position k)"""
+def eliminate(order_idx):
+    """full reduction over the columns in sorted order, the free row with the smallest index as pivot -> (pivot rows [91],
+    their sorted positions [91], the reduced matrix with its columns in sorted order)"""
     A = np.array(generator_matrix()[:, order_idx], copy=True)          # columns in sorted order
     used = np.zeros(K, bool)
     piv_row, piv_col = [], []
@@ -100,9 +101,20 @@ def reduced_basis(order_idx):
         if len(piv_row) == K:
             break
     assert len(piv_row) == K
+    return piv_row, piv_col, A
+
+
+def reduced_basis(order_idx):
+    """(basis positions in reliability order [91], R uint8 [91][174] with R[k] the reduced row of basis position k)"""
+    piv_row, piv_col, A = eliminate(order_idx)
     R = np.zeros((K, N), np.uint8)
     R[:, order_idx] = A[piv_row]                         # back to codeword order
     return np.asarray(order_idx)[piv_col], R
+
+
+@functools.lru_cache(None)
+def _pairs():
+    return np.triu_indices(K, 1)                         # lexicographic i < j
 
 
 def search(llr):
@@ -121,8 +133,13 @@ def search(llr):
     if (int(m1[k1]), 1 + k1) < best:
         best = (int(m1[k1]), 1 + k1)
     out.append(best)
-    iu, ju = np.triu_indices(K, 1)                       # lexicographic i < j
-    m2 = (D1[iu] ^ R[ju]).astype(np.int32) @ w           # [4095]
+    iu, ju = _pairs()
+    # metric of d0 ^ R_i ^ R_j = m0 + S_i + S_j - 2 T_ij with s = w where d0 = 0, -w where d0 = 1 (what a flip there costs),
+    # S_i = the sum of s over R_i, T_ij = the sum of s over R_i & R_j: exact in int64, without the 4095 x 174 differences
+    Rs = R.astype(np.int64) * np.where(d0 == 1, -w, w).astype(np.int64)[None, :]
+    S1 = Rs.sum(axis=1)
+    T = Rs @ R.astype(np.int64).T
+    m2 = m0 + S1[iu] + S1[ju] - 2 * T[iu, ju]             # [4095]
     k2 = int(np.argmin(m2))
     if (int(m2[k2]), 1 + K + k2) < best:
         best = (int(m2[k2]), 1 + K + k2)
@@ -206,7 +223,8 @@ def osd_candidates(oracle, mag, cands, counts, status_in, order, max_hard_errors
     return out, inf
 
 
-def decode_deep(oracle, iq, passes, order, max_hard_errors, max_candidates=120, min_score=10, nthreads=8, msgs=None, searches=None):
+def decode_deep(oracle, iq, passes, order, max_hard_errors, max_candidates=120, min_score=10, nthreads=8, msgs=None, searches=None,
+                iters=20):
     """ft8gpu_decode_messages_deep for B frames [B][2][48000] -> (msgs [B][50], n [B], n_by_stage [B][passes][2]): the pass
     loop of tests/ft8_spec_multipass.py with OSD behind every pass -- OSD on the pass's status records, the append step on
     what it accepted, pad[0] of a gained record = the pattern's nhard.  order -1: no OSD.  searches: a dict that carries the
@@ -214,7 +232,7 @@ def decode_deep(oracle, iq, passes, order, max_hard_errors, max_candidates=120, 
     import rtlsdr_ft8d_amd as ft8
     import ft8_spec_messages as sm
     import ft8_spec_multipass as mp
-    mag, cands, counts, status = sm.oracle_stages(oracle, iq, max_candidates, min_score, nthreads)
+    mag, cands, counts, status = sm.oracle_stages(oracle, iq, max_candidates, min_score, nthreads, iters)
     B = mag.shape[0]
     out, n = sm.collect(mag, cands, counts, status, min_score=min_score,
                         msgs=np.zeros((B, mp.MAX_MESSAGES), ft8.MESSAGE_DTYPE) if msgs is None else msgs)
@@ -247,7 +265,7 @@ def decode_deep(oracle, iq, passes, order, max_hard_errors, max_candidates=120, 
         a = np.array(active)
         W[a] = mp.mask(W[a], base[a], out[a], prev[a], n[a])
         c2, k2 = oracle.find_sync_batch(W[a], max_candidates, min_score, nthreads=nthreads)
-        s2 = oracle.decode_candidates_batch(W[a], c2, k2, nthreads=nthreads)
+        s2 = oracle.decode_candidates_batch(W[a], c2, k2, iters=iters, nthreads=nthreads)
         prev = prev_next
         o2, n2 = mp.append(W[a], base[a], c2, k2, s2, out[a], n[a], min_score=min_score)
         out[a], n[a] = o2, n2

@@ -1,7 +1,7 @@
 """GPU tests of multi-pass decoding (ft8gpu_decode_messages_passes / ft8gpu_mask_messages / ft8gpu_append_messages): the
 stage entries and the whole path against the numpy restatement (tests/ft8_spec_multipass.py) on oracle-made inputs, byte
 for byte with every output pre-filled with 0xA5; passes=1 against ft8gpu_decode_messages; chunking; the gain on crowded
-frames; argument errors."""
+frames; argument errors; four passes."""
 import numpy as np
 import pytest
 
@@ -245,3 +245,26 @@ def test_argument_errors_and_null_counts_table(oracle):
         # NULL arrays are refused
         assert dec.lib.ft8gpu_decode_messages_passes(dec.h, iq.ctypes.data, 3, 2, None, n.ctypes.data, None, ft8.HOST_PTRS) != 0
         assert b"NULL" in dec.lib.ft8gpu_last_error()
+
+
+def test_four_passes_equal_restatement(oracle):
+    """FT8GPU_MAX_PASSES = 4 on the 30-signal frames among single-signal and noise frames: the restatement, host and device
+    form; frames on which pass 3 finds nothing, alone in a call as well -- there the pass loop leaves early and the counts are
+    carried into the passes that did not run"""
+    import torch
+    import rtlsdr_ft8d_amd as ft8
+    iq = _ragged_batch(oracle)
+    B = len(iq)
+    want, wn, wnbp = spec.decode_passes(oracle, iq, 4, msgs=_filled(B))
+    print("n_by_pass", wnbp.tolist())
+    stops = [f for f in range(B) if wnbp[f, 1] > wnbp[f, 0] and wnbp[f, 2] == wnbp[f, 1]]
+    assert stops and (wnbp[:, 1] > wnbp[:, 0]).sum() >= 2 and (wnbp[:, 3] == wnbp[:, 0]).any()
+    with ft8.Decoder(device=0, max_frames=B) as dec:
+        got, n, nbp = dec.decode_messages_passes(iq, 4, _filled(B))
+        assert np.array_equal(n, wn) and np.array_equal(nbp, wnbp), (n, wn, nbp.tolist(), wnbp.tolist())
+        assert got.tobytes() == want.tobytes(), sm.check(got, n, want, wn)
+        dm, dn, dnb = _dev_passes(ft8, dec, torch.from_numpy(iq).cuda(), B, 4)
+        assert np.array_equal(dn, wn) and np.array_equal(dnb, wnbp) and dm.tobytes() == want.tobytes()
+        for f in stops[:3] + [1]:                                      # 1: a noise frame, the loop leaves before pass 2
+            m, k, kb = dec.decode_messages_passes(iq[f:f + 1], 4, _filled(1))
+            assert k[0] == wn[f] and np.array_equal(kb[0], wnbp[f]) and m.tobytes() == want[f:f + 1].tobytes(), f

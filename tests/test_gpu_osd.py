@@ -1,7 +1,8 @@
 """GPU tests of ordered-statistics decoding (ft8gpu_osd_candidates / ft8gpu_decode_messages_deep): the stage entry and the
 whole path against the numpy restatement (tests/ft8_spec_osd.py), byte for byte with every output pre-filled with 0xA5; the
 frozen fixture; the two identity properties of the whole path; chunking; refused arguments; the gain on the 96 crowded
-frames of profiles/osd_gain.json."""
+frames of profiles/osd_gain.json; the parameter edges -- max_candidates 1..5, 480 and 1024, ldpc_iters 1 and 50, four passes,
+a cap grown by ft8gpu_set_params on a live context.  Constructed soft bits: tests/test_gpu_osd_constructed.py."""
 import json
 import os
 
@@ -243,3 +244,149 @@ def test_gain_on_the_crowded_frames_of_the_profile(oracle):
                 print(f"order {order} gate {gate}: planted {h1} -> {h} (+{h - h1}), outside {m}; profile +{rec['new_planted']} / {rec['outside']}")
                 assert (h - h1, m - m1) == (rec["new_planted"], rec["outside"]), (order, gate, h - h1, m - m1, rec)
                 assert h > h1
+
+
+# ---- parameter edges: other caps, other iteration counts, four passes, a cap that grows on a live context ---------------------
+
+EDGE_CAPS = [1, 2, 3, 4, 5, 480, 1024]
+_edge = {}
+
+
+def _edge_frames(oracle):
+    """frames 0..3 of _deep_batch: crowded, noise, dense (30 signals), one weak signal"""
+    if "iq" not in _edge:
+        _edge["iq"] = _deep_batch(oracle)[:4]
+        _edge["iq"].setflags(write=False)
+    return _edge["iq"]
+
+
+def _edge_min_score(cap):
+    return 0 if cap > 5 else 10                                        # at 0 every position of the scan survives: the long lists fill
+
+
+def _edge_searches(cap):
+    """the first pass's pattern searches at a cap, shared by the stage entry's test and the deep path's (same frames, same lists)"""
+    return _edge.setdefault(("searches", cap), {})
+
+
+@pytest.mark.parametrize("cap", EDGE_CAPS)
+def test_stage_entry_at_other_caps(oracle, cap):
+    """ft8gpu_osd_candidates at both ends of the accepted range of max_candidates on a crowded and a noise frame, status_in from
+    the device's own LDPC kernel; above cap 5 min_score is 0 and both lists are full (records up to index cap - 1).  Host form,
+    device form, device form in place."""
+    import torch
+    import rtlsdr_ft8d_amd as ft8
+    ms = _edge_min_score(cap)
+    mag = oracle.waterfall_batch(_edge_frames(oracle)[:2], nthreads=2)
+    cands, counts = oracle.find_sync_batch(mag, cap, ms, nthreads=2)
+    if cap > 5:
+        assert counts.tolist() == [cap, cap]
+    B = 2
+    fill_st = np.full((B, cap, 48), FILL, np.uint8)
+    fill_info = np.full((B, cap * 8), FILL, np.uint8).view(so.INFO_DTYPE).reshape(B, cap)
+    searches = _edge_searches(cap)
+    attempted = 0
+    with ft8.Decoder(device=0, max_frames=B, max_candidates=cap, min_score=ms) as dec:
+        status_in = dec.decode_candidates(mag, cands, counts)
+        ins = [torch.from_numpy(np.ascontiguousarray(a).view(np.uint8)).cuda() for a in (mag, cands, counts, status_in)]
+        for order, gate in ((0, 83), (1, RECOMMENDED), (2, RECOMMENDED), (2, 83)):
+            want_st, want_info = so.osd_candidates(oracle, mag, cands, counts, status_in, order, gate, status_out=fill_st, info=fill_info,
+                                                   searches=searches)
+            got_st, got_info = dec.osd_candidates(mag, cands, counts, status_in, order, gate, status_out=fill_st, info=fill_info)
+            assert got_info.tobytes() == want_info.tobytes() and got_st.tobytes() == want_st.tobytes(), (cap, order, gate)
+            out_d = torch.full((B, cap, 48), FILL, dtype=torch.uint8, device="cuda")
+            info_d = torch.full((B, cap, 8), FILL, dtype=torch.uint8, device="cuda")
+            torch.cuda.synchronize()
+            dec.osd_candidates_dev(*ins, B, order, gate, out_d, info_d)
+            dec.synchronize()
+            assert out_d.cpu().numpy().tobytes() == want_st.tobytes() and info_d.cpu().numpy().tobytes() == want_info.tobytes()
+            inplace = ins[3].clone()
+            torch.cuda.synchronize()
+            dec.osd_candidates_dev(ins[0], ins[1], ins[2], inplace, B, order, gate, inplace, info_d)
+            dec.synchronize()
+            w2, _ = so.osd_candidates(oracle, mag, cands, counts, status_in, order, gate, status_out=status_in, searches=searches)
+            assert inplace.cpu().numpy().tobytes() == w2.tobytes() and info_d.cpu().numpy().tobytes() == want_info.tobytes()
+            attempted += int(sum((want_info[f, :counts[f]]["result"] != 0).sum() for f in range(B)))
+    assert attempted >= (6 * cap if cap > 5 else 1), attempted         # above cap 5 nearly every record of the full lists is attempted
+
+
+def _deep_both_forms(ft8, dec, iq, passes, order, gate, want, wn, wnbs, what):
+    import torch
+    B = len(iq)
+    got, n, nbs = dec.decode_messages_deep(iq, passes, order, gate, _filled_msgs(B))
+    assert np.array_equal(n, wn) and np.array_equal(nbs, wnbs), (what, n, wn, nbs.tolist(), wnbs.tolist())
+    assert got.tobytes() == want.tobytes(), (what, sm.check(got, n, want, wn))
+    dm, dn, dnbs = _dev_deep(ft8, dec, torch.from_numpy(np.array(iq)).cuda(), B, passes, order, gate)
+    assert np.array_equal(dn, wn) and np.array_equal(dnbs, wnbs) and dm.tobytes() == want.tobytes(), what
+
+
+@pytest.mark.parametrize("cap,iters", [(cap, 20) for cap in EDGE_CAPS] + [(120, 1), (120, 50)])
+def test_deep_path_at_other_caps_and_iteration_counts(oracle, cap, iters):
+    """ft8gpu_decode_messages_deep, 2 passes, order 2, the recommended gate: four frames at caps 1..5 and at ldpc_iters 1 and 50,
+    the crowded and the dense frame at cap 480, the crowded frame alone at cap 1024 (full lists: the restatement's searches
+    set the size); host and device form, n_by_stage too"""
+    import rtlsdr_ft8d_amd as ft8
+    ms = _edge_min_score(cap)
+    iq = _edge_frames(oracle)
+    iq = iq[:1] if cap == 1024 else (iq[[0, 2]] if cap == 480 else iq)
+    B = len(iq)
+    searches = _edge_searches(cap) if iters == 20 and cap != 480 else {}      # at 480 frame 1 is another frame than the stage entry's
+    want, wn, wnbs = so.decode_deep(oracle, iq, 2, 2, RECOMMENDED, max_candidates=cap, min_score=ms, msgs=_filled_msgs(B), searches=searches,
+                                    iters=iters)
+    with ft8.Decoder(device=0, max_frames=B, max_candidates=cap, min_score=ms, ldpc_iters=iters) as dec:
+        _deep_both_forms(ft8, dec, iq, 2, 2, RECOMMENDED, want, wn, wnbs, (cap, iters))
+    print(f"cap {cap} iters {iters}: n_by_stage {wnbs.tolist()}")
+    assert wn.sum() >= 1 and (cap < 120 or (wnbs[:, :, 1] > wnbs[:, :, 0]).any())      # at the reference's cap and above, OSD gains
+
+
+def test_deep_path_with_four_passes(oracle):
+    """three dense frames (30 signals), a noise frame, a weak single signal, a crowded frame: pass 3 runs for the frames that
+    gained in pass 2 and finds nothing, so pass 4 does not run and their counts are carried into its stages; the noise and
+    the single-signal frame stop after pass 1.  Every frame alone as well: there the pass loop itself leaves early."""
+    import rtlsdr_ft8d_amd as ft8
+    b = _deep_batch(oracle)
+    iq = b[[2, 7, 10, 1, 3, 0]]
+    B = len(iq)
+    searches = {}
+    want, wn, wnbs = so.decode_deep(oracle, iq, 4, 2, RECOMMENDED, msgs=_filled_msgs(B), searches=searches)
+    print("n_by_stage", wnbs.tolist())
+    after = wnbs[:, :, 1]
+    assert ((after[:, 1] > after[:, 0]) & (after[:, 3] == after[:, 1])).sum() >= 3, "no frame on which pass 3 finds nothing"
+    assert (after[:, 3] == after[:, 0]).any()                          # and one the second pass never runs for
+    with ft8.Decoder(device=0, max_frames=B) as dec:
+        _deep_both_forms(ft8, dec, iq, 4, 2, RECOMMENDED, want, wn, wnbs, "batch")
+        for f in range(B):
+            got, n, nbs = dec.decode_messages_deep(iq[f:f + 1], 4, 2, RECOMMENDED, _filled_msgs(1))
+            assert n[0] == wn[f] and np.array_equal(nbs[0], wnbs[f]) and got.tobytes() == want[f:f + 1].tobytes(), f
+
+
+def test_cap_growth_on_a_live_context(oracle):
+    """one context: an OSD call and a deep call at cap 33, ft8gpu_set_params to 480 (the OSD records and the later passes'
+    candidate set are allocated anew), the same calls, back to 33, the same calls -- each time byte for byte what a fresh
+    context created at that cap gives"""
+    import rtlsdr_ft8d_amd as ft8
+    iq = _edge_frames(oracle)
+    B = len(iq)
+    mag = oracle.waterfall_batch(iq, nthreads=4)
+
+    def calls(dec, cap):
+        cands, counts = oracle.find_sync_batch(mag, cap, 0, nthreads=4)
+        assert (counts == cap).all()
+        status = dec.decode_candidates(mag, cands, counts)
+        fill_st = np.full((B, cap, 48), FILL, np.uint8)
+        fill_info = np.full((B, cap * 8), FILL, np.uint8).view(so.INFO_DTYPE).reshape(B, cap)
+        st, info = dec.osd_candidates(mag, cands, counts, status, 2, RECOMMENDED, status_out=fill_st, info=fill_info)
+        msgs, n, nbs = dec.decode_messages_deep(iq, 2, 2, RECOMMENDED, _filled_msgs(B))
+        assert (info["result"] != 0).sum() > B * cap // 2 and n.sum() >= 20
+        return [a.tobytes() for a in (status, st, info, msgs, n, nbs)]
+
+    fresh = {}
+    for cap in (33, 480):
+        with ft8.Decoder(device=0, max_frames=B, max_candidates=cap, min_score=0) as dec:
+            fresh[cap] = calls(dec, cap)
+    assert fresh[33] != fresh[480]
+    with ft8.Decoder(device=0, max_frames=B, max_candidates=33, min_score=0) as dec:
+        for cap in (33, 480, 33, 480):
+            dec.set_params(max_candidates=cap)
+            got = calls(dec, cap)
+            assert [a == b for a, b in zip(got, fresh[cap])] == [True] * 6, cap
