@@ -367,6 +367,87 @@ static_assert(sizeof(ft8gpu_osd_info) == 8 && offsetof(ft8gpu_osd_info, nhard) =
 static_assert(sizeof(ft8gpu_deep_params) == 12 && offsetof(ft8gpu_deep_params, osd_order) == 4 &&
               offsetof(ft8gpu_deep_params, osd_max_hard_errors) == 8, "ft8gpu_deep_params layout");
 #endif
+/* ---- a-priori (AP) decoding: BP once more with known message bits fixed ---------------------------------------------------
+ * (DESIGN.md "A-priori decoding"; not in the reference, whose ft8_decode, rtlsdr_ft8d.c:1476, runs BP once.  The reference
+ * reports CQ calls only, rtlsdr_ft8d.c:1509-1520, and 32 of the 77 payload bits of "CQ CALL GRID" are the same every time.)
+ * A hypothesis is 77 payload bits with a mask, both numbered as in a91, MSB first.  Bits 77..79 of both arrays are zero,
+ * bits & ~mask == 0, and between 1 and 77 bits are masked; anything else is refused with an error message.  Codeword
+ * positions 0..76 are the payload bits (the code is systematic).
+ * A candidate qualifies as for OSD: its status record has ok == 0 and ldpc_errors != 0 (either form of the LDPC kernel).
+ * llr[0..173] = the normalised soft bits BP starts from, in the LDPC kernel's arithmetic; h[i] = llr[i] > 0;
+ * apmag = max |llr[i]|.  A non-finite llr[i], or apmag == 0: nothing is tried, result 6.
+ * Hypotheses are tried in table order k = 0 .. nhyp - 1:
+ *   llr_k[i] = bits_k[i] ? +apmag : -apmag on the masked positions, llr[i] elsewhere
+ *   ft8_lib's bp_decode(llr_k, ldpc_iters) runs as in the LDPC kernel; nhard = the number of unmasked positions at which
+ *   the word it leaves differs from h; iters = its iteration count (255 for more)
+ *   the first failing check names the hypothesis's result: 7 no codeword within ldpc_iters, 8 the codeword differs from the
+ *   hypothesis on a masked position, 5 all-zero, 2 nhard > max_hard_errors, 3 CRC-14 mismatch, 4 unpack77 < 0, else
+ *   1 = accepted.  (bp_decode leaves at an all-zero word before checking it, so such a word is "no codeword", 7; 5 keeps
+ *   its place for a decoder that would hand one over.)
+ * The first accepted hypothesis wins; later ones are not tried and their results[] stay 0.  On acceptance the status record
+ * becomes that of a BP success, as OSD writes it (ok = 1, ldpc_errors = 0, CRC fields, unpack_status, a91, text; iters as it
+ * was); otherwise it is unchanged.  The rule is defined per (candidate, hypothesis): a wave per pair plus a resolve step would
+ * give the same bytes as the loop inside a wave. */
+#define FT8GPU_AP_MAX_HYPOTHESES 4
+typedef struct { uint8_t mask[10]; uint8_t bits[10]; } ft8gpu_ap_hypothesis;
+typedef struct {
+    uint8_t result;          /* 0 not attempted, 1 accepted, 2..5, 7, 8 the failing check, 6 unusable soft bits (nothing tried) */
+    uint8_t nhard;           /* result, nhard, iters: of hypothesis `hyp` */
+    uint8_t hyp;             /* the accepted hypothesis, or the last one tried */
+    uint8_t iters;
+    uint8_t results[FT8GPU_AP_MAX_HYPOTHESES];    /* the code of every hypothesis tried, 0 for the others */
+} ft8gpu_ap_info;
+/* Recommended max_hard_errors, from profiles/ap_gain.json (tools/ap_gain.py: six workloads of 96 frames, 33 127 failing
+ * candidates).  Under "CQ ? ?" BP converges on 469 words that agree with the hypothesis: 463 planted codewords with 6 .. 35
+ * hard errors (one of 45 that gains nothing), and 6 wrong words with 20, 25, 25, 26, 26, 26 -- inside the range of the right
+ * ones, so the gate separates nothing: on 96 frames of 20 CQ signals it costs 13 of the 42 gained messages at 20 and 2 at 25
+ * while it still admits the wrong words.  40 is the smallest gate of the sweep that loses no message in any row, and it only
+ * cuts the tail.  What keeps false decodes out is that a wrong word must satisfy 83 parity checks, agree with the forced
+ * bits, and then pass the 14-bit CRC: 6 / 2^14 = 4e-4 expected false decodes in those 576 frames. */
+#define FT8GPU_AP_MAX_HARD_ERRORS 40
+/* stage entry: mag [nframes][94208], cands / status_in / status_out / info [nframes][max_candidates], counts [nframes];
+ * host or device pointers by `flags`, hyps [nhyp] always in host memory.  nhyp in [1, 4], max_hard_errors in [0, 174];
+ * ldpc_iters is the context's.  Records below counts[f] are written (a candidate that does not qualify: status_out =
+ * status_in, info all zero), records at and behind it are not touched.  status_out may be status_in.
+ * The reference's CQ spot list with AP: ft8gpu_decode_candidates -> ft8gpu_ap_candidates -> ft8gpu_collect_spots. */
+int ft8gpu_ap_candidates(ft8gpu_ctx *ctx, const uint8_t *mag, const ft8gpu_candidate *cands, const int32_t *counts,
+                         const ft8gpu_decode_status *status_in, int nframes, const ft8gpu_ap_hypothesis *hyps, int nhyp,
+                         int max_hard_errors, ft8gpu_decode_status *status_out, ft8gpu_ap_info *info, int flags);
+/* A hypothesis from a standard type 1 message with `?` for the unknown tokens: "CQ ? ?", "CQ DX ? ?", "CQ POTA ? ?",
+ * "K1ABC ? ?", "K1ABC W9XYZ ?", "? W9XYZ FN42", ...  FIELD1 CALL2 THIRD as ft8gpu_pack77 takes them for i3 = 1 ("CQ nnn" /
+ * "CQ aaaa" count as FIELD1; THIRD is one token).  A known FIELD1 masks bits 0..28, a known CALL2 bits 29..57, a known THIRD
+ * bits 58..73; bits 74..76 (i3 = 1) are always masked.  "CQ ? ?" gives exactly the 32 bits 0..28 and 74..76.
+ * A pattern without `?` masks all 77 bits.  0 = ok, -1 = not such a pattern (a token the packer refuses, a /P call, more
+ * or fewer than three fields).  Host C. */
+int ft8gpu_ap_from_text(const char *pattern, ft8gpu_ap_hypothesis *out);
+/* The whole path with AP and OSD behind every pass: each pass runs as in ft8gpu_decode_messages_deep; then AP runs in place
+ * on the pass's status records and the append step adds the unique messages it gained, in candidate order (pad[1] of such a
+ * record = 1 + the accepted hypothesis); then OSD runs in place on what AP left undecoded (pad[0] as in the deep entry).
+ * n_by_stage [nframes][passes][3] (NULL: not written): the count after BP, after AP and after OSD of each pass.
+ * nhyp = 0: no AP -- the launches and the message bytes of ft8gpu_decode_messages_deep.  osd_order -1: no OSD. */
+typedef struct {
+    int32_t passes;                 /* 1 .. FT8GPU_MAX_PASSES */
+    int32_t nhyp;                   /* 0 (no AP) .. FT8GPU_AP_MAX_HYPOTHESES */
+    int32_t ap_max_hard_errors;     /* 0 .. 174; FT8GPU_AP_MAX_HARD_ERRORS is the recommended value */
+    int32_t osd_order;              /* -1 (no OSD), 0, 1, 2 */
+    int32_t osd_max_hard_errors;    /* 0 .. 83 */
+    ft8gpu_ap_hypothesis hyps[FT8GPU_AP_MAX_HYPOTHESES];
+} ft8gpu_ap_params;
+int ft8gpu_decode_messages_ap(ft8gpu_ctx *ctx, const float *iq, int nframes, const ft8gpu_ap_params *params,
+                              ft8gpu_message *msgs, int32_t *n_msgs, int32_t *n_by_stage, int flags);
+#ifndef __cplusplus
+_Static_assert(sizeof(ft8gpu_ap_hypothesis) == 20 && offsetof(ft8gpu_ap_hypothesis, bits) == 10, "ft8gpu_ap_hypothesis layout");
+_Static_assert(sizeof(ft8gpu_ap_info) == 8 && offsetof(ft8gpu_ap_info, nhard) == 1 && offsetof(ft8gpu_ap_info, hyp) == 2 &&
+               offsetof(ft8gpu_ap_info, iters) == 3 && offsetof(ft8gpu_ap_info, results) == 4, "ft8gpu_ap_info layout");
+_Static_assert(sizeof(ft8gpu_ap_params) == 100 && offsetof(ft8gpu_ap_params, osd_order) == 12 && offsetof(ft8gpu_ap_params, hyps) == 20,
+               "ft8gpu_ap_params layout");
+#else
+static_assert(sizeof(ft8gpu_ap_hypothesis) == 20 && offsetof(ft8gpu_ap_hypothesis, bits) == 10, "ft8gpu_ap_hypothesis layout");
+static_assert(sizeof(ft8gpu_ap_info) == 8 && offsetof(ft8gpu_ap_info, nhard) == 1 && offsetof(ft8gpu_ap_info, hyp) == 2 &&
+              offsetof(ft8gpu_ap_info, iters) == 3 && offsetof(ft8gpu_ap_info, results) == 4, "ft8gpu_ap_info layout");
+static_assert(sizeof(ft8gpu_ap_params) == 100 && offsetof(ft8gpu_ap_params, osd_order) == 12 && offsetof(ft8gpu_ap_params, hyps) == 20,
+              "ft8gpu_ap_params layout");
+#endif
 /* one line per message, "%3d %4.1f %4d ~  %s\n" of snr_db, dt_s, (int)freq_hz, text (NUL-terminated, truncated to cap);
  * returns the untruncated length.  Host-side text formatting, no GPU involved. */
 int ft8gpu_format_messages(const ft8gpu_message *msgs, int32_t n, char *out, size_t cap);

@@ -40,7 +40,13 @@ MESSAGE_DTYPE = np.dtype({"names": ["text", "snr_db", "score", "freq_hz", "dt_s"
 # ft8gpu_osd_info: what ordered-statistics decoding found for a candidate (ft8gpu_osd_candidates)
 OSD_INFO_DTYPE = np.dtype([("result", "u1"), ("nhard", "u1"), ("pattern", "<u2"), ("metric", "<i4")])
 OSD_MAX_HARD_ERRORS = 27    # FT8GPU_OSD_MAX_HARD_ERRORS, the recommended gate
+# ft8gpu_ap_info / ft8gpu_ap_hypothesis: a-priori decoding (ft8gpu_ap_candidates)
+AP_INFO_DTYPE = np.dtype([("result", "u1"), ("nhard", "u1"), ("hyp", "u1"), ("iters", "u1"), ("results", "u1", (4,))])
+AP_HYP_DTYPE = np.dtype([("mask", "u1", (10,)), ("bits", "u1", (10,))])
+AP_MAX_HYPOTHESES = 4       # FT8GPU_AP_MAX_HYPOTHESES
+AP_MAX_HARD_ERRORS = 40     # FT8GPU_AP_MAX_HARD_ERRORS, the recommended gate
 assert RESULT_DTYPE.itemsize == 28 and CAND_DTYPE.itemsize == 8 and MESSAGE_DTYPE.itemsize == 64 and OSD_INFO_DTYPE.itemsize == 8
+assert AP_INFO_DTYPE.itemsize == 8 and AP_HYP_DTYPE.itemsize == 20
 assert STATUS_DTYPE.itemsize == 48 and SIGNAL_DTYPE.itemsize == 92
 
 
@@ -51,6 +57,18 @@ class Params(C.Structure):
 class DeepParams(C.Structure):
     """ft8gpu_deep_params: passes 1..4, osd_order -1 (no OSD) .. 2, osd_max_hard_errors 0..83"""
     _fields_ = [("passes", C.c_int32), ("osd_order", C.c_int32), ("osd_max_hard_errors", C.c_int32)]
+
+
+class ApHypothesis(C.Structure):
+    """ft8gpu_ap_hypothesis: 77 payload bits with a mask, numbered as in a91 (MSB first)"""
+    _fields_ = [("mask", C.c_uint8 * 10), ("bits", C.c_uint8 * 10)]
+
+
+class ApParams(C.Structure):
+    """ft8gpu_ap_params: passes 1..4, nhyp 0 (no AP) .. 4, ap_max_hard_errors 0..174, osd_order -1 (no OSD) .. 2,
+    osd_max_hard_errors 0..83, hyps[4]"""
+    _fields_ = [("passes", C.c_int32), ("nhyp", C.c_int32), ("ap_max_hard_errors", C.c_int32), ("osd_order", C.c_int32),
+                ("osd_max_hard_errors", C.c_int32), ("hyps", ApHypothesis * 4)]
 
 
 class Timings(C.Structure):
@@ -91,6 +109,7 @@ ABI_SYMBOLS = [
     "ft8gpu_decode_messages", "ft8gpu_collect_messages", "ft8gpu_noise_baseline", "ft8gpu_format_messages",
     "ft8gpu_decode_messages_passes", "ft8gpu_mask_messages", "ft8gpu_append_messages",
     "ft8gpu_osd_candidates", "ft8gpu_decode_messages_deep",
+    "ft8gpu_ap_candidates", "ft8gpu_ap_from_text", "ft8gpu_decode_messages_ap",
     "ft8_find_sync", "ft8_decode", "ft8_encode", "pack77",            # ft8_lib level (include/ft8_lib/ft8/*.h)
     "initFFTW", "freeFFTW", "ft8_subsystem", "ft8gpu_read_raw_iq", "ft8gpu_read_c2", "ft8gpu_write_raw_iq",
 ]
@@ -223,6 +242,10 @@ def _declare(L):
     if hasattr(L, "ft8gpu_osd_candidates"):               # absent from older builds loaded by load_library_at
         L.ft8gpu_osd_candidates.argtypes = [vp, vp, vp, vp, vp, C.c_int, C.c_int, C.c_int, vp, vp, C.c_int]
         L.ft8gpu_decode_messages_deep.argtypes = [vp, vp, C.c_int, C.POINTER(DeepParams), vp, vp, vp, C.c_int]
+    if hasattr(L, "ft8gpu_ap_candidates"):                # absent from older builds loaded by load_library_at
+        L.ft8gpu_ap_candidates.argtypes = [vp, vp, vp, vp, vp, C.c_int, vp, C.c_int, C.c_int, vp, vp, C.c_int]
+        L.ft8gpu_ap_from_text.argtypes = [C.c_char_p, vp]
+        L.ft8gpu_decode_messages_ap.argtypes = [vp, vp, C.c_int, C.POINTER(ApParams), vp, vp, vp, C.c_int]
     L.ft8gpu_rx_decimate.argtypes = [vp, vp, C.c_int, C.c_size_t, vp, C.c_int, C.c_int]
     if hasattr(L, "ft8gpu_rx_stream"):                    # absent from older builds loaded by load_library_at
         L.ft8gpu_rx_stream.argtypes = [vp, vp, C.c_int, C.c_int, C.c_size_t, vp, vp, vp, C.c_int, C.c_int]
@@ -285,6 +308,32 @@ def pack77(msg):
     if rc != 0:
         raise ValueError(f"cannot pack {msg!r} as an FT8 message")
     return out
+
+
+def ap_from_text(pattern):
+    """ft8gpu_ap_from_text: a type 1 message with `?` for the unknown tokens ("CQ ? ?", "CQ DX ? ?", "K1ABC W9XYZ ?") -> one
+    AP_HYP_DTYPE record"""
+    out = np.zeros(1, AP_HYP_DTYPE)
+    rc = load_library().ft8gpu_ap_from_text(pattern.encode(), out.ctypes.data)
+    if rc != 0:
+        raise ValueError(f"{pattern!r} is no a-priori pattern of a standard message")
+    return out[0]
+
+
+def _ap_hyps(hyps):
+    """patterns (str) or AP_HYP_DTYPE records -> a contiguous AP_HYP_DTYPE array"""
+    hyps = [hyps] if isinstance(hyps, (str, np.void)) else hyps
+    out = np.zeros(len(hyps), AP_HYP_DTYPE)
+    for k, h in enumerate(hyps):
+        out[k] = ap_from_text(h) if isinstance(h, str) else h
+    return out
+
+
+def _ap_params(passes, hyps, ap_max_hard_errors, osd_order, osd_max_hard_errors):
+    hyps = _ap_hyps(hyps)
+    p = ApParams(int(passes), len(hyps), int(ap_max_hard_errors), int(osd_order), int(osd_max_hard_errors))
+    C.memmove(C.addressof(p.hyps), hyps.ctypes.data, min(hyps.nbytes, C.sizeof(p.hyps)))
+    return p
 
 
 def encode(payload):
@@ -561,7 +610,58 @@ class Decoder:
                                                     nbs.ctypes.data, HOST_PTRS))
         return msgs, n, nbs
 
+    def ap_candidates(self, mag, cands, counts, status_in, hyps=("CQ ? ?",), max_hard_errors=AP_MAX_HARD_ERRORS, status_out=None,
+                      info=None):
+        """ft8gpu_ap_candidates -> (status_out [B][cap] STATUS_DTYPE, info [B][cap] AP_INFO_DTYPE), new arrays; records at and
+        behind counts[f] keep what status_out / info held (zeros when None).  hyps: patterns or AP_HYP_DTYPE records"""
+        mag = np.ascontiguousarray(mag, np.uint8).reshape(-1, MAG_ARRAY)
+        B = mag.shape[0]
+        cands = np.ascontiguousarray(cands)
+        counts = np.ascontiguousarray(counts, np.int32)
+        status_in = np.ascontiguousarray(status_in).view(np.uint8).reshape(B, self.max_candidates, 48)
+        assert cands.shape == (B, self.max_candidates) and cands.dtype == CAND_DTYPE and counts.shape == (B,)
+        out = np.zeros((B, self.max_candidates, 48), np.uint8) if status_out is None else \
+            np.array(status_out, copy=True, order="C").view(np.uint8).reshape(B, self.max_candidates, 48)
+        inf = np.zeros((B, self.max_candidates), AP_INFO_DTYPE) if info is None else \
+            np.array(info, copy=True, order="C").view(AP_INFO_DTYPE).reshape(B, self.max_candidates)
+        hyps = _ap_hyps(hyps)
+        self._ck(self.lib.ft8gpu_ap_candidates(self.h, mag.ctypes.data, cands.ctypes.data, counts.ctypes.data, status_in.ctypes.data,
+                                               B, hyps.ctypes.data, len(hyps), int(max_hard_errors), out.ctypes.data, inf.ctypes.data,
+                                               HOST_PTRS))
+        return out.view(STATUS_DTYPE).reshape(B, self.max_candidates), inf
+
+    def decode_messages_ap(self, iq, passes=1, hyps=("CQ ? ?",), ap_max_hard_errors=AP_MAX_HARD_ERRORS, osd_order=-1,
+                           osd_max_hard_errors=OSD_MAX_HARD_ERRORS, msgs=None):
+        """ft8gpu_decode_messages_ap -> (msgs [B][50] MESSAGE_DTYPE, n_msgs [B], n_by_stage [B][passes][3]: the count after BP,
+        after AP and after OSD of each pass); slots past n_msgs[f] keep what `msgs` held (zeros when None).  hyps = (): no AP"""
+        iq = np.ascontiguousarray(iq, np.float32)
+        B = iq.shape[0]
+        assert iq.shape[1:] == (2, NSAMPLES)
+        if msgs is None:
+            msgs = np.zeros((B, MAX_MESSAGES), MESSAGE_DTYPE)
+        assert msgs.dtype == MESSAGE_DTYPE and msgs.shape == (B, MAX_MESSAGES) and msgs.flags["C_CONTIGUOUS"]
+        n = np.zeros(B, np.int32)
+        nbs = np.zeros((B, max(int(passes), 1), 3), np.int32)
+        p = _ap_params(passes, hyps, ap_max_hard_errors, osd_order, osd_max_hard_errors)
+        self._ck(self.lib.ft8gpu_decode_messages_ap(self.h, iq.ctypes.data, B, C.byref(p), msgs.ctypes.data, n.ctypes.data,
+                                                    nbs.ctypes.data, HOST_PTRS))
+        return msgs, n, nbs
+
     # ---- device-pointer API (inputs and outputs resident in HBM) --------------------------------
+    def ap_candidates_dev(self, mag_dev, cands_dev, counts_dev, status_in_dev, nframes, hyps, max_hard_errors, status_out_dev, info_dev):
+        """status_out_dev may be status_in_dev; info_dev: [nframes][max_candidates] 8-byte records; hyps stay on the host"""
+        hyps = _ap_hyps(hyps)
+        self._ck(self.lib.ft8gpu_ap_candidates(self.h, _ptr(mag_dev), _ptr(cands_dev), _ptr(counts_dev), _ptr(status_in_dev), nframes,
+                                               hyps.ctypes.data, len(hyps), int(max_hard_errors), _ptr(status_out_dev), _ptr(info_dev),
+                                               DEVICE_PTRS))
+
+    def decode_messages_ap_dev(self, iq_dev, nframes, passes, hyps, ap_max_hard_errors, osd_order, osd_max_hard_errors, msgs_dev,
+                               n_msgs_dev, n_by_stage_dev=None):
+        """n_by_stage_dev: [nframes][passes][3] int32, or None"""
+        p = _ap_params(passes, hyps, ap_max_hard_errors, osd_order, osd_max_hard_errors)
+        self._ck(self.lib.ft8gpu_decode_messages_ap(self.h, _ptr(iq_dev), nframes, C.byref(p), _ptr(msgs_dev), _ptr(n_msgs_dev),
+                                                    None if n_by_stage_dev is None else _ptr(n_by_stage_dev), DEVICE_PTRS))
+
     def osd_candidates_dev(self, mag_dev, cands_dev, counts_dev, status_in_dev, nframes, order, max_hard_errors, status_out_dev, info_dev):
         """status_out_dev may be status_in_dev; info_dev: [nframes][max_candidates] 8-byte records"""
         self._ck(self.lib.ft8gpu_osd_candidates(self.h, _ptr(mag_dev), _ptr(cands_dev), _ptr(counts_dev), _ptr(status_in_dev), nframes,

@@ -6,6 +6,8 @@ namespace {
 
 constexpr int kOsdMaxOrder = 2, kOsdMaxHard = kLdpcM;
 
+}  // namespace
+
 // the constant tables, the info records and the host form's staging of status_out, on the first OSD call
 // (ft8gpu_create's footprint is unchanged); the record buffers follow the cap when ft8gpu_set_params grows it
 int ensure_osd_buffers(ft8gpu_ctx *c) {
@@ -36,6 +38,8 @@ int check_osd_args(int order, int max_hard_errors) {
         return ft8_fail("max_hard_errors %d out of range [0, %d]", max_hard_errors, kOsdMaxHard);
     return 0;
 }
+
+namespace {
 
 struct Deep {
     ft8gpu_ctx *c;

@@ -349,6 +349,43 @@ int ft8gpu_pack77_std(const char *msg, uint8_t payload[10]) {
     return 0;
 }
 
+/* ---- a-priori hypotheses from text (ft8gpu_ap_candidates): a type 1 message with `?` for the unknown tokens ---------------
+ * The known tokens are packed by pack_type1 with stand-ins at the unknown places, so a hypothesis's bits are exactly what the
+ * packer gives the same tokens in a whole message; the mask covers the fields that were known, and i3. */
+static void mask_bits(uint8_t m[10], int first, int last) {
+    for (int i = first; i <= last; ++i) m[i >> 3] |= (uint8_t)(0x80u >> (i & 7));
+}
+
+int ft8gpu_ap_from_text(const char *pattern, ft8gpu_ap_hypothesis *out) {
+    if (!pattern || !out) return -1;
+    if (strlen(pattern) > 40) return -1;
+    token tok[kMaxTokens];
+    const int n = split_tokens(pattern, tok);
+    static const char kStandIn[] = "K1ABC";
+    const token stand_in = { kStandIn, 5 };
+    /* FIELD1 is "CQ nnn" / "CQ aaaa" when four tokens start that way, else one token; then CALL2 and THIRD, one token each */
+    const int cq2 = n == 4 && tok_is(&tok[0], "CQ") && pack_cq_modifier(tok[1].p, tok[1].len) >= 0;
+    if (n != (cq2 ? 4 : 3)) return -1;
+    const token *call2 = &tok[cq2 ? 2 : 1], *third = &tok[cq2 ? 3 : 2];
+    const int known1 = !tok_is(&tok[0], "?"), known2 = !tok_is(call2, "?"), known3 = !tok_is(third, "?");
+    token t[kMaxTokens];
+    int k = 0;
+    t[k++] = known1 ? tok[0] : stand_in;
+    if (cq2) t[k++] = tok[1];
+    t[k++] = known2 ? *call2 : stand_in;
+    if (known3) t[k++] = *third;
+    uint8_t p77[10];
+    if (pack_type1(t, k, p77) != 0) return -1;
+    if ((p77[9] >> 3 & 7u) != 1u) return -1;                /* a /P call makes it type 2 */
+    memset(out, 0, sizeof *out);
+    if (known1) mask_bits(out->mask, 0, 28);
+    if (known2) mask_bits(out->mask, 29, 57);
+    if (known3) mask_bits(out->mask, 58, 73);
+    mask_bits(out->mask, 74, 76);
+    for (int j = 0; j < 10; ++j) out->bits[j] = p77[j] & out->mask[j];
+    return 0;
+}
+
 /* ---- CRC-14 + LDPC(174,91) generator + tone mapping: ft8_encode, rtlsdr_ft8d.c:934 -------------- */
 static uint16_t crc14(const uint8_t *msg, int nbits) {
     uint32_t rem = 0;

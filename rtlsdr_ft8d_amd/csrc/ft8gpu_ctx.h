@@ -74,6 +74,12 @@ struct ft8gpu_ctx {
     int osd_cap = 0;
     int32_t *d_nosd = nullptr;             //   the counts before the OSD append [max_frames], host staging of n_by_stage
     int32_t *d_nbs = nullptr;              //   [max_frames][FT8GPU_MAX_PASSES][2]
+    bool ap_tables = false;                // AP, lazily on its first call: the constant tables are uploaded,
+    ft8gpu_ap_info *d_ap_info = nullptr;   //   the info records [max_frames][ap_cap] and the host form's staging of status_out,
+    ft8gpu_decode_status *d_ap_out = nullptr;
+    int ap_cap = 0;
+    int32_t *d_nap = nullptr;              //   the counts before the AP append [max_frames], host staging of n_by_stage
+    int32_t *d_nbs3 = nullptr;             //   [max_frames][FT8GPU_MAX_PASSES][3]
     ft8gpu_synth_signal *d_sigs = nullptr;
     size_t sigs_cap = 0;
     void *d_rx_sums = nullptr, *d_rx_p2 = nullptr;     // RX front end scratch
@@ -157,8 +163,12 @@ int ensure_messages_buffers(ft8gpu_ctx *c);
 // api_multipass.hip: frees the multi-pass buffers (ft8gpu_destroy); allocates them on the first multi-pass call
 void free_multipass_buffers(ft8gpu_ctx *c);
 int ensure_multipass_buffers(ft8gpu_ctx *c);
-// api_osd.hip: frees the OSD buffers (ft8gpu_destroy)
+// api_osd.hip: frees the OSD buffers (ft8gpu_destroy); allocates them on the first OSD call; refuses arguments out of range
 void free_osd_buffers(ft8gpu_ctx *c);
+int ensure_osd_buffers(ft8gpu_ctx *c);
+int check_osd_args(int order, int max_hard_errors);
+// api_ap.hip: frees the AP buffers (ft8gpu_destroy)
+void free_ap_buffers(ft8gpu_ctx *c);
 // ft8gpu_decode_batch with one more form: kIqOnDevice, frames resident on the context's GPU and records to host arrays
 // (used by the multi-GPU entries; not part of the ABI, whose entry passes on FT8GPU_DEVICE_PTRS only)
 constexpr int kIqOnDevice = 2;

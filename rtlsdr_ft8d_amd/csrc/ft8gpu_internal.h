@@ -94,6 +94,16 @@ hipError_t launch_osd(const uint8_t *mag, const ft8gpu_candidate *cands, const i
 // pad[0] = nhard for the records [n_before[f], n_msgs[f]) of the frames behind the pass's slots (map == nullptr: slot = frame)
 hipError_t launch_osd_tag(const ft8gpu_osd_info *info, const int32_t *map, const int32_t *n_before, const int32_t *n_msgs,
                           int nslots, int max_candidates, ft8gpu_message *msgs, hipStream_t s);
+// ap.hip: a-priori decoding of the candidates BP gives up on (DESIGN.md "A-priori decoding"); ap_tables_init uploads its copy
+// of the LDPC edge tables and the CRC table on the first AP call; hyps is host memory (it travels as a kernel argument)
+hipError_t ap_tables_init(hipStream_t s);
+hipError_t launch_ap(const uint8_t *mag, const ft8gpu_candidate *cands, const int32_t *counts,
+                     const ft8gpu_decode_status *status_in, ft8gpu_decode_status *status_out, ft8gpu_ap_info *info,
+                     int nframes, int max_candidates, int ldpc_iters, int force_ieee_div,
+                     const ft8gpu_ap_hypothesis *hyps, int nhyp, int max_hard_errors, hipStream_t s);
+// pad[1] = 1 + hyp for the records [n_before[f], n_msgs[f]) of the frames behind the pass's slots (map == nullptr: slot = frame)
+hipError_t launch_ap_tag(const ft8gpu_ap_info *info, const int32_t *map, const int32_t *n_before, const int32_t *n_msgs,
+                         int nslots, int max_candidates, ft8gpu_message *msgs, hipStream_t s);
 hipError_t launch_synth(const ft8gpu_synth_signal *sig_dev, int nframes, int nsig, float noise_sigma,
                         uint64_t seed, uint64_t first_frame, float *iq, hipStream_t s);
 hipError_t run_bp_math_selftest(uint64_t out[7], hipStream_t s);   // bp_selftest.hip: exhaustive check of bp_math.h
