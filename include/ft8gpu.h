@@ -169,6 +169,18 @@ int  ft8gpu_selftest_bp_math(ft8gpu_ctx *ctx, uint64_t out[7]);
  * rational-function divisions tested, of those not correctly rounded.  (Round 5: HIP's __fsqrt_rn turned out to be the 1-ulp
  * native root.) */
 int  ft8gpu_selftest_norm_math(ft8gpu_ctx *ctx, uint64_t out[7]);
+/* The same kind of proof for the dB quantiser of the waterfall kernel (rtlsdr_ft8d.c:1415-1427; csrc/quant_math.h), which does not
+ * evaluate the reference's log10f expression but a v_log_f32 guess and one compare against a threshold table built at
+ * ft8gpu_create.  One kernel walks every |X|^2 bit pattern the waterfall kernel can produce -- 0x00000000 .. 0x7F800000 (0 .. +inf)
+ * and every NaN of both signs; a sum of two squares is never negative -- through the kernel's own functions and this context's
+ * uploaded table, in both slots of the packed pair and beside partners from elsewhere in the domain, and returns the step function:
+ * step_bits[k] = the k-th pattern b (ascending) with q(b) != q(b - 1), step_val[k] = q(b); at most min(cap, 4096) entries are
+ * written.  out[0..6] = number of steps (the true count, also when it exceeds what was written), q(0), NaN patterns not quantised
+ * to 0, evaluations of one pattern that disagree, results that were the guess, results that were the guess + 1, one offending
+ * pattern (0 = none).  qthr[0..255] = the threshold table as it lies on the device.  Equal step lists and equal q(0) on the
+ * device and in the reference expression mean equal bytes for every float; the tests hold them against the CPU oracle.  About
+ * 6 ms. */
+int  ft8gpu_selftest_quantiser(ft8gpu_ctx *ctx, uint64_t out[7], uint32_t *step_bits, uint8_t *step_val, int32_t cap, float qthr[256]);
 int  ft8gpu_set_params(ft8gpu_ctx *ctx, const ft8gpu_params *params);
 int  ft8gpu_enable_timing(ft8gpu_ctx *ctx, int on);
 int  ft8gpu_get_timings(ft8gpu_ctx *ctx, ft8gpu_timings *out, int32_t *nruns);

@@ -168,6 +168,64 @@ uint8_t ft8o_quantise(float mag2) {
     return (uint8_t)((scaled < 0) ? 0 : ((scaled > 255) ? 255 : scaled)); /* :1427 */
 }
 
+/* The step function of the fenced ft8o_quantise over the float bit patterns first_bits .. last_bits, walked as unsigned
+ * integers (0x00000000 .. 0x7F800000 is 0 .. +inf in ascending order): every pattern b in (first_bits, last_bits] with
+ * q(b) != q(b - 1), in ascending order, as bits_out[k] = b, val_out[k] = q(b).  At most cap entries are written; the return
+ * value is the true number of steps, so a list that did not fit shows.  *n_decreasing = how many of the steps go down.
+ * q(first_bits) itself is ft8o_quantise of that pattern.  The scan is one libm call per pattern (2^31 of them for 0 .. +inf:
+ * seconds on a few cores), split over nthreads.  Returns -1, and writes nothing, while the x86 quantiser mode is on
+ * (ft8o_set_quantiser_x86): the steps are those of the fenced definition only. */
+static inline float ft8o_bits_to_float(uint32_t u) { float f; memcpy(&f, &u, 4); return f; }
+
+int64_t ft8o_quantise_steps(uint32_t first_bits, uint32_t last_bits, uint32_t *bits_out, uint8_t *val_out, int64_t cap, int nthreads,
+                            int64_t *n_decreasing) {
+    if (g_quantiser_x86 || last_bits < first_bits || cap < 0 || (cap > 0 && (!bits_out || !val_out))) return -1;
+    enum { kChunks = 8192 };
+    const uint64_t n = (uint64_t)last_bits - first_bits;                 /* patterns after the first */
+    const uint64_t per = (n + kChunks - 1) / kChunks;
+    int64_t *count = (int64_t *)calloc(2 * kChunks + 1, sizeof(int64_t)), *down = count + kChunks + 1;
+    if (!count) return -1;
+    if (nthreads < 1) nthreads = 1;
+    int64_t total = 0, total_down = 0;
+    {
+        /* pass 1 counts the steps of every chunk, pass 2 walks the few chunks that have any again and writes them in place */
+        for (int pass = 0; pass < 2; pass++) {
+#ifdef _OPENMP
+#pragma omp parallel for num_threads(nthreads) schedule(dynamic, 16)
+#endif
+            for (int c = 0; c < kChunks; c++) {
+                const uint64_t lo = (uint64_t)c * per, hi = lo + per < n ? lo + per : n;       /* offsets lo+1 .. hi from first_bits */
+                if (pass == 1 && (lo >= hi || count[c + 1] == count[c])) continue;
+                int64_t steps = 0, dn = 0, at = pass ? count[c] : 0;
+                if (lo < hi) {
+                    uint8_t prev = ft8o_quantise(ft8o_bits_to_float((uint32_t)(first_bits + lo)));
+                    for (uint64_t o = lo + 1; o <= hi; o++) {
+                        const uint32_t b = (uint32_t)(first_bits + o);
+                        const uint8_t q = ft8o_quantise(ft8o_bits_to_float(b));
+                        if (q != prev) {
+                            steps++;
+                            dn += q < prev;
+                            if (pass && at < cap) { bits_out[at] = b; val_out[at] = q; }
+                            at++;
+                            prev = q;
+                        }
+                    }
+                }
+                if (!pass) { count[c + 1] = steps; down[c] = dn; }
+            }
+            if (!pass) {
+                count[0] = 0;
+                for (int c = 0; c < kChunks; c++) { count[c + 1] += count[c]; total_down += down[c]; }
+                total = count[kChunks];
+            }
+        }
+    }
+    (void)nthreads;
+    free(count);
+    if (n_decreasing) *n_decreasing = total_down;
+    return total;
+}
+
 /* rtlsdr_ft8d.c:1395-1435 */
 void ft8o_waterfall(const float *iSamples, const float *qSamples, uint8_t *mag_power) {
     ft8o_init();

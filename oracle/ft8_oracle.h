@@ -127,6 +127,10 @@ void ft8o_fft1024_f64(const double *re_in, const double *im_in, double *re_out, 
 uint8_t ft8o_quantise(float mag2);                          /* rtlsdr_ft8d.c:1415-1427 for one bin (fenced for non-finite input) */
 uint8_t ft8o_quantise_x86(float mag2);                      /* the same as the reference's x86 build executes it (inf, NaN -> 0) */
 void ft8o_set_quantiser_x86(int on);                        /* ft8o_quantise / ft8o_waterfall follow the x86 form (default: fenced) */
+/* the steps of the fenced ft8o_quantise over the bit patterns first_bits .. last_bits: every b in (first, last] with q(b) != q(b - 1),
+ * ascending; returns the true count (at most cap are written), -1 in the x86 quantiser mode; *n_decreasing = steps that go down */
+int64_t ft8o_quantise_steps(uint32_t first_bits, uint32_t last_bits, uint32_t *bits_out, uint8_t *val_out, int64_t cap, int nthreads,
+                            int64_t *n_decreasing);
 void ft8o_waterfall(const float *iSamples, const float *qSamples, uint8_t *mag_power);
 void ft8o_waterfall_f64(const float *iSamples, const float *qSamples, uint8_t *mag_power);
 /* Optional run-time FFTW leg (the reference's own transform: fftwf_plan_dft_1d(NFFT, in, out, FFTW_FORWARD,

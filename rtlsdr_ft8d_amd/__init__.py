@@ -104,7 +104,7 @@ ABI_SYMBOLS = [
     "ft8gpu_rx_stream", "ft8gpu_rx_state_reset",
     "ft8gpu_dev_alloc", "ft8gpu_dev_free", "ft8gpu_memcpy_h2d", "ft8gpu_memcpy_d2h", "ft8gpu_host_alloc", "ft8gpu_host_free",
     "ft8gpu_overlap_active", "ft8gpu_overlap_reason", "ft8gpu_build_id", "ft8gpu_pack77",
-    "ft8gpu_set_debug_flags", "ft8gpu_selftest_bp_math", "ft8gpu_selftest_norm_math", "ft8gpu_gather_spots", "ft8gpu_gather_shutdown",
+    "ft8gpu_set_debug_flags", "ft8gpu_selftest_bp_math", "ft8gpu_selftest_norm_math", "ft8gpu_selftest_quantiser", "ft8gpu_gather_spots", "ft8gpu_gather_shutdown",
     "ft8gpu_shard_workers", "ft8gpu_decode_batch_multi", "ft8gpu_decode_batch_multi_dev",
     "ft8gpu_decode_messages", "ft8gpu_collect_messages", "ft8gpu_noise_baseline", "ft8gpu_format_messages",
     "ft8gpu_decode_messages_passes", "ft8gpu_mask_messages", "ft8gpu_append_messages",
@@ -218,6 +218,8 @@ def _declare(L):
     if hasattr(L, "ft8gpu_selftest_norm_math"):
         L.ft8gpu_selftest_norm_math.argtypes = [vp, C.POINTER(C.c_uint64)]
         L.ft8gpu_overlap_reason.argtypes = [vp, C.c_char_p, C.c_size_t]
+    if hasattr(L, "ft8gpu_selftest_quantiser"):           # absent from older builds loaded by load_library_at
+        L.ft8gpu_selftest_quantiser.argtypes = [vp, vp, vp, vp, C.c_int32, vp]
     L.ft8gpu_encode.argtypes = [vp, vp]
     L.ft8gpu_encode.restype = None
     L.ft8gpu_synth_frames.argtypes = [vp, vp, C.c_int, C.c_int, C.c_float, C.c_uint64, vp]
@@ -422,6 +424,18 @@ class Decoder:
         out = (C.c_uint64 * 7)()
         self._ck(self.lib.ft8gpu_selftest_norm_math(self.h, out))
         return dict(zip(("inputs", "div_bad", "sqrt_bad", "compose_bad", "first_bad", "rational_inputs", "rational_div_bad"), [int(v) for v in out]))
+
+    def selftest_quantiser(self, cap=4096):
+        """the waterfall kernel's dB quantiser on every float (0 .. +inf and every NaN) with this context's uploaded thresholds:
+        its step function (steps_bits[k] = k-th bit pattern b with q(b) != q(b - 1), steps_val[k] = q(b); n_steps is the true
+        count, also beyond cap), q(0), the counts the proof rests on, and qthr[0..255] as they lie on the device"""
+        out = np.zeros(7, np.uint64)
+        bits, val, thr = np.zeros(cap, np.uint32), np.zeros(cap, np.uint8), np.zeros(256, np.float32)
+        self._ck(self.lib.ft8gpu_selftest_quantiser(self.h, out.ctypes.data, bits.ctypes.data, val.ctypes.data, cap, thr.ctypes.data))
+        d = dict(zip(("n_steps", "q0", "nan_nonzero", "disagree", "from_guess", "from_guess_plus_1", "first_bad"), [int(v) for v in out]))
+        n = min(d["n_steps"], cap, 4096)
+        d.update(steps_bits=bits[:n], steps_val=val[:n], qthr=thr)
+        return d
 
     def enable_timing(self, on=True):
         self._ck(self.lib.ft8gpu_enable_timing(self.h, int(on)))

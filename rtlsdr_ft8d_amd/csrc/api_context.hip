@@ -373,6 +373,14 @@ int ft8gpu_selftest_norm_math(ft8gpu_ctx *c, uint64_t out[7]) {
     return 0;
 }
 
+int ft8gpu_selftest_quantiser(ft8gpu_ctx *c, uint64_t out[7], uint32_t *step_bits, uint8_t *step_val, int32_t cap, float qthr[256]) {
+    if (!out || !step_bits || !step_val || !qthr) return ft8_fail("NULL argument");
+    if (cap < 1) return ft8_fail("ft8gpu_selftest_quantiser: cap %d < 1", (int)cap);
+    CHECK_COMMON(c, 0);
+    HIP_TRY(run_quantiser_selftest(c->d_tab, out, step_bits, step_val, cap, qthr, c->stream));
+    return 0;
+}
+
 int ft8gpu_enable_timing(ft8gpu_ctx *c, int on) {
     CHECK_COMMON(c, 0);
     c->timing = on != 0;

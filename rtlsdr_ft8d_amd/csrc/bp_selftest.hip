@@ -2,8 +2,14 @@
 // fast_tanh / fast_atanh (ft8_lib ldpc.c) are functions of ONE float, so every input the BP kernel's fast path can
 // see is tried: all 2^32 bit patterns, filtered to the domain the kernel's guard establishes, fast form against the
 // compiler's IEEE division, scalar and packed forms alike.  About 40 ms on one MI355X.
+// Also here, for the same reason: the LLR scale factor against exact arithmetic (norm_math_exhaustive) and the waterfall
+// kernel's dB quantiser over every float (quantiser_exhaustive).
 #include "ft8gpu_internal.h"
 #include "bp_math.h"
+#include "quant_math.h"
+#include <algorithm>
+#include <utility>
+#include <vector>
 
 namespace {
 
@@ -128,7 +134,106 @@ __global__ __launch_bounds__(256) void norm_math_exhaustive(NormCounts *out, uin
     if (bad) atomicMax(&out->first_bad, bad);
 }
 
+// ---- the dB quantiser of the waterfall kernel: its step function over every float --------------------------------------
+// quant_math.h's quantise_pair is a function of one float per slot, so every |X|^2 the waterfall kernel can produce is
+// tried: the bit patterns 0x00000000 .. 0x7F800000 (0 .. +inf) in order, and every NaN of both signs.  Negative values and
+// -0 cannot occur: |X|^2 is a sum of two squares (qm::mag2_pair), so the patterns 0x80000000 .. 0xFF800000 are not walked.
+// The thresholds are the context's own uploaded table, read through an LDS copy of all 260 entries as the kernel does.
+// Every pattern b is evaluated three times: in the .x slot beside a partner p taken from elsewhere in the domain by a
+// multiplicative hash, in the .y slot beside that partner, and in the .y slot beside its predecessor b - 1 (which also
+// gives q(b - 1), the value a step is detected against); the partner is evaluated in both slots as well.  All
+// evaluations of one pattern must agree.  What comes back is the step function itself -- every b with q(b) != q(b - 1)
+// and the new value -- for the test to compare with the oracle's: equal step lists and equal q(0) mean equality on
+// every float.
+constexpr int kQuantStepCap = 4096;
+struct QuantCounts {
+    unsigned long long n_steps, nan_nonzero, disagree, from_kl, from_kl1;
+    unsigned int q0, first_bad;
+    unsigned int step_bits[kQuantStepCap];      // in the order the waves found them; sorted on the host
+    unsigned int step_val[kQuantStepCap];
+};
+
+__global__ __launch_bounds__(256) void quantiser_exhaustive(QuantCounts *out, const Ft8Tables *__restrict__ tab, uint32_t first,
+                                                            uint64_t n, int nan_walk) {
+    __shared__ __attribute__((aligned(16))) float s_thr[260];
+    for (int i = threadIdx.x; i < 260; i += 256) s_thr[i] = tab->qthr[i];
+    __syncthreads();
+    unsigned long long nz = 0, dis = 0, c0 = 0, c1 = 0;
+    unsigned int bad = 0;
+    for (uint64_t i = blockIdx.x * (uint64_t)blockDim.x + threadIdx.x; i < n; i += (uint64_t)gridDim.x * blockDim.x) {
+        const uint32_t bits = first + (uint32_t)i;
+        const uint32_t prev = (nan_walk || bits == 0u) ? bits : bits - 1u;
+        const uint32_t part = (bits * 2654435761u) & 0x7FFFFFFFu;                 // 0 .. +inf or a positive NaN: inside the domain
+        const float x = __uint_as_float(bits), xp = __uint_as_float(prev), p = __uint_as_float(part);
+        unsigned ax, ay, bx, by, cx, cy;
+        qm::quantise_pair(qm::f2{ x, p }, s_thr, ax, ay);
+        qm::quantise_pair(qm::f2{ p, x }, s_thr, bx, by);
+        qm::quantise_pair(qm::f2{ xp, x }, s_thr, cx, cy);
+        if (ax != by || ax != cy || ay != bx) { ++dis; bad = bits; }
+        qm::f2 y;
+        int ka, kb;
+        qm::guess_pair(qm::f2{ x, p }, y, ka, kb);                                // which branch of the compare gave ax
+        if (ax == (unsigned)ka) ++c0;
+        else if (ax == (unsigned)ka + 1u) ++c1;
+        else { ++dis; bad = bits; }
+        if (nan_walk) {
+            if (ax != 0u) { ++nz; bad = bits; }
+        } else if (bits == 0u) {
+            out->q0 = ax;
+        } else if (cx != ax) {
+            const unsigned long long slot = atomicAdd(&out->n_steps, 1ull);
+            if (slot < (unsigned long long)kQuantStepCap) { out->step_bits[slot] = bits; out->step_val[slot] = ax; }
+        }
+    }
+    if (nz) atomicAdd(&out->nan_nonzero, nz);
+    if (dis) atomicAdd(&out->disagree, dis);
+    if (c0) atomicAdd(&out->from_kl, c0);
+    if (c1) atomicAdd(&out->from_kl1, c1);
+    if (bad) atomicMax(&out->first_bad, bad);
+}
+
 }  // namespace
+
+// out[0..6]: steps of q over 0 .. +inf (the true count, also beyond the list's capacity), q(0), NaN patterns not quantised to 0,
+//            evaluations of one pattern that disagree (slot, partner, or a result that is neither the guess nor the guess + 1),
+//            results equal to the guess, results equal to the guess + 1, one offending pattern (0 = none)
+// step_bits / step_val: the first min(out[0], cap, kQuantStepCap) steps in ascending order; qthr: thresholds 0..255 as uploaded
+hipError_t run_quantiser_selftest(const Ft8Tables *tab, uint64_t out[7], uint32_t *step_bits, uint8_t *step_val, int cap,
+                                  float qthr[256], hipStream_t s) {
+    QuantCounts *d = nullptr;
+    hipError_t e = hipMalloc(&d, sizeof(QuantCounts));
+    if (e != hipSuccess) return e;
+    std::vector<char> hbuf(sizeof(QuantCounts));
+    QuantCounts &h = *reinterpret_cast<QuantCounts *>(hbuf.data());
+    float thr[256];
+    e = hipMemsetAsync(d, 0, sizeof(QuantCounts), s);
+    // 0 .. +inf in parts of 2^28 patterns, then the NaNs above +inf and above -inf
+    const uint64_t n_ordered = 0x7F800001ull;
+    for (uint64_t lo = 0; lo < n_ordered && e == hipSuccess; lo += (uint64_t)1 << 28) {
+        const uint64_t n = n_ordered - lo < ((uint64_t)1 << 28) ? n_ordered - lo : (uint64_t)1 << 28;
+        hipLaunchKernelGGL(quantiser_exhaustive, dim3(256 * 32), dim3(256), 0, s, d, tab, (uint32_t)lo, n, 0);
+        e = hipGetLastError();
+    }
+    for (uint32_t first : { 0x7F800001u, 0xFF800001u }) {
+        if (e != hipSuccess) break;
+        hipLaunchKernelGGL(quantiser_exhaustive, dim3(256 * 32), dim3(256), 0, s, d, tab, first, (uint64_t)0x7FFFFF, 1);
+        e = hipGetLastError();
+    }
+    if (e == hipSuccess) e = hipMemcpyAsync(&h, d, sizeof h, hipMemcpyDeviceToHost, s);
+    if (e == hipSuccess) e = hipMemcpyAsync(thr, tab->qthr, sizeof thr, hipMemcpyDeviceToHost, s);
+    if (e == hipSuccess) e = hipStreamSynchronize(s);
+    (void)hipFree(d);
+    if (e != hipSuccess) return e;
+    const size_t have = h.n_steps < (unsigned long long)kQuantStepCap ? (size_t)h.n_steps : (size_t)kQuantStepCap;
+    std::vector<std::pair<uint32_t, uint8_t>> steps(have);
+    for (size_t k = 0; k < have; ++k) steps[k] = { h.step_bits[k], (uint8_t)h.step_val[k] };
+    std::sort(steps.begin(), steps.end());
+    for (size_t k = 0; k < have && k < (size_t)cap; ++k) { step_bits[k] = steps[k].first; step_val[k] = steps[k].second; }
+    for (int k = 0; k < 256; ++k) qthr[k] = thr[k];
+    out[0] = h.n_steps; out[1] = h.q0; out[2] = h.nan_nonzero; out[3] = h.disagree; out[4] = h.from_kl; out[5] = h.from_kl1;
+    out[6] = h.first_bad;
+    return hipSuccess;
+}
 
 // out[0..6]: inputs, quotients 24/v not correctly rounded, roots not correctly rounded, llr_norm_factor != sqrtf(24/v), one
 //            offending input (0 = none), divisions of fast_tanh / fast_atanh tested, of those not correctly rounded

@@ -108,6 +108,9 @@ hipError_t launch_synth(const ft8gpu_synth_signal *sig_dev, int nframes, int nsi
                         uint64_t seed, uint64_t first_frame, float *iq, hipStream_t s);
 hipError_t run_bp_math_selftest(uint64_t out[7], hipStream_t s);   // bp_selftest.hip: exhaustive check of bp_math.h
 hipError_t run_norm_math_selftest(uint64_t out[7], hipStream_t s); // bp_selftest.hip: sqrtf(24.0f / v) against exact arithmetic, every float
+// bp_selftest.hip: the waterfall kernel's quantiser (quant_math.h) on every float, against the context's uploaded thresholds
+hipError_t run_quantiser_selftest(const Ft8Tables *tab, uint64_t out[7], uint32_t *step_bits, uint8_t *step_val, int cap,
+                                  float qthr[256], hipStream_t s);
 hipError_t decode_tables_init(hipStream_t s);   // uploads the LDPC edge tables used by the BP kernel
 hipError_t launch_rx(const uint8_t *raw, int ncaptures, size_t npairs, void *scratch_sums, void *scratch_base,
                      float *iq, int normalise, hipStream_t s);

@@ -162,6 +162,20 @@ def waterfall(i, q, f64=False):
     return m
 
 
+def quantise_steps(first_bits, last_bits, nthreads, cap=4096):
+    """the step function of the fenced ft8o_quantise over the float bit patterns first_bits .. last_bits: (bits uint32 [n], values
+    uint8 [n], true number of steps, number of steps that go down); n = min(steps, cap).  One log10f per pattern: the
+    2^31 patterns of 0 .. +inf take seconds on nthreads cores.  Raises in the x86 quantiser mode."""
+    L = lib()
+    L.ft8o_quantise_steps.argtypes = [C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.POINTER(C.c_int64)]
+    L.ft8o_quantise_steps.restype = C.c_int64
+    bits, val, down = np.zeros(cap, np.uint32), np.zeros(cap, np.uint8), C.c_int64(-1)
+    n = L.ft8o_quantise_steps(first_bits, last_bits, bits.ctypes.data, val.ctypes.data, cap, int(nthreads), C.byref(down))
+    if n < 0:
+        raise RuntimeError("ft8o_quantise_steps refused: x86 quantiser mode, or an empty range")
+    return bits[:min(n, cap)].copy(), val[:min(n, cap)].copy(), int(n), down.value
+
+
 def find_sync(mag, max_candidates=120, min_score=10):
     mag = np.ascontiguousarray(mag, np.uint8)
     heap = np.zeros(max_candidates, CAND_DTYPE)

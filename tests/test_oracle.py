@@ -225,6 +225,41 @@ def test_quantiser_fence_is_separate_from_the_reference_expression(oracle):
     assert hit.any() and set(np.unique(fenced[hit])) <= {255} and set(np.unique(x86[hit])) <= {0}
 
 
+def test_quantiser_step_function_over_every_float(oracle):
+    """The product's threshold table (csrc/api_context.hip: build_tables) bisects the reference expression and so rests on
+    "this machine's log10f makes it monotone", which it checks 64 floats either side of each threshold and on samples.
+    Here exhaustively: over all 2^31 bit patterns 0 .. +inf the fenced quantiser never steps down, and steps up exactly
+    255 times, through 1, 2, ... 255 in order; q(0) = 0, q(+inf) = 255, and every NaN of either sign gives 0.
+    (7.4 s on 8 threads: one log10f per pattern.)"""
+    nthreads = min(16, len(os.sched_getaffinity(0)))
+    q = oracle.lib().ft8o_quantise
+    bits, val, n, down = oracle.quantise_steps(0, 0x7F800000, nthreads)
+    assert down == 0
+    assert n == 255 and np.array_equal(val, np.arange(1, 256))
+    assert np.all(np.diff(bits.astype(np.int64)) > 0) and bits[0] > 0 and bits[-1] < 0x7F800000
+    assert q(0.0) == 0 and q(float("inf")) == 255
+    for k in (0, 127, 254):                                              # the list is the function: spot-check it against single calls
+        at, below = (float(np.array([b], np.uint32).view(np.float32)[0]) for b in (bits[k], bits[k] - 1))
+        assert (q(below), q(at)) == (k, k + 1)
+    for first in (0x7F800001, 0xFF800001):                               # all 2^23 - 1 NaNs of each sign: no step, and the first is 0
+        assert oracle.quantise_steps(first, first + 0x7FFFFE, nthreads)[2:] == (0, 0)
+        assert q(float(np.array([first], np.uint32).view(np.float32)[0])) == 0
+    # +inf -> NaN is the one step down of the whole positive half
+    assert [a.tolist() for a in oracle.quantise_steps(0x7F800000, 0x7FFFFFFF, nthreads)[:2]] == [[0x7F800001], [0]]
+    # a list that does not fit shows in the count; the x86 quantiser mode is refused (its steps would be another function's)
+    lo, hi = int(bits[100]) - 5, int(bits[100]) + (3 << 23)             # three binades of |X|^2: 18 steps
+    b10, v10, n10, _ = oracle.quantise_steps(lo, hi, nthreads, cap=10)
+    assert n10 == np.count_nonzero((bits > lo) & (bits <= hi)) > 10
+    assert np.array_equal(b10, bits[100:110]) and np.array_equal(v10, val[100:110])
+    L = oracle.lib()
+    L.ft8o_set_quantiser_x86(1)
+    try:
+        with pytest.raises(RuntimeError, match="x86"):
+            oracle.quantise_steps(0, 1000, 1)
+    finally:
+        L.ft8o_set_quantiser_x86(0)
+
+
 # ---- sync search ------------------------------------------------------------------------------------
 def test_find_sync_heap_semantics(oracle):
     """the retained multiset is the top-N of all scores >= min_score and comes out sorted"""
