@@ -139,10 +139,19 @@ __device__ __forceinline__ float tanh_ref(float x) {
 // (fast form: x2 * 64 is a scaling by a power of two, hence exact, so -735 + x2 * 64 is ONE rounding either way and a
 // fused multiply-add returns the very same float -- one instruction less per pair; the exhaustive self-test compares
 // it with the reference's two-operation form like everything else in this header)
+// -735.0f held in a vector register.  A VOP3P instruction reads at most one scalar register pair, and the fast form's
+// packed fma has two constant operands: written as literals both land in scalar registers and the compiler copies one
+// into a fresh vector pair in front of every use (a v_mov_b64 per atanh_pair).  Coming out of an asm statement the
+// constant cannot be rematerialised: a caller with a loop fetches it once ahead of the loop and hands it to atanh_pair.
+__device__ __forceinline__ float vgpr_m735() {
+    float r;
+    asm("v_mov_b32 %0, 0xc437c000" : "=v"(r));      // -735.0f
+    return r;
+}
 template <bool FAST>
-__device__ __forceinline__ f2 atanh_pair(f2 x) {
+__device__ __forceinline__ f2 atanh_pair(f2 x, float m735 = -735.0f) {
     const f2 x2 = x * x;
-    const f2 inner = FAST ? pk_fma(x2, f2{ 64.0f, 64.0f }, f2{ -735.0f, -735.0f }) : (-735.0f + x2 * 64.0f);
+    const f2 inner = FAST ? pk_fma(x2, f2{ 64.0f, 64.0f }, f2{ m735, m735 }) : (-735.0f + x2 * 64.0f);
     const f2 a = x * (945.0f + x2 * inner);
     const f2 b = (945.0f + x2 * (-1050.0f + x2 * 225.0f));
     return FAST ? div_pair_3(a, b) : div_pair_ieee(a, b);

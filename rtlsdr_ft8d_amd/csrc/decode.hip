@@ -91,6 +91,28 @@ __device__ __forceinline__ float add_f32(float a, float b) {
     return r;
 }
 
+// a * (b.x, b.x) and a * (b.y, b.y) as one v_pk_mul_f32: the broadcast of one half of b is the instruction's op_sel /
+// op_sel_hi operand modifier.  (Register pairs are even-aligned, so a float that a ds_read_b128 left in an odd register
+// can only be broadcast as the upper half of its pair; the compiler copies it into a fresh pair with a v_mov instead.)
+__device__ __forceinline__ f2 mul_bcast_lo(f2 a, f2 b) {
+    f2 r;
+    asm("v_pk_mul_f32 %0, %1, %2 op_sel_hi:[1,0]" : "=v"(r) : "v"(a), "v"(b));
+    return r;
+}
+__device__ __forceinline__ f2 mul_bcast_hi(f2 a, f2 b) {
+    f2 r;
+    asm("v_pk_mul_f32 %0, %1, %2 op_sel:[0,1]" : "=v"(r) : "v"(a), "v"(b));
+    return r;
+}
+
+// a register with unspecified content, for values that are written under a narrowed EXEC mask and whose other lanes
+// nobody reads: no instruction, where an initialiser would cost a v_mov per iteration
+__device__ __forceinline__ float any_f32() {
+    float r;
+    asm volatile("" : "=v"(r));
+    return r;
+}
+
 // Guard key of a value: (bits << 1) - 1 as unsigned.  Zero maps to 0xFFFFFFFF, every other value to
 // twice its magnitude bits minus one, so "minimum key over a set >= key(T)" says: each member is
 // zero or at least T in magnitude.
@@ -105,6 +127,21 @@ __device__ __forceinline__ float add_f32(float a, float b) {
 // Both are far above v_div_scale's 2^-103 rescaling threshold.  Large, infinite and NaN values need
 // no guard: |x| > 4.97 is overridden by fast_tanh's clamp in either division form, the products are
 // bounded, and NaN stays NaN through both forms.  Iteration 0 starts from tov = 0.
+//
+// The products of iteration 0 satisfy the guard by construction, so it is not evaluated for them (exact-zero LLRs
+// -- differences of bytes -- are common, and each would send the quick form on to the exact key test).  Proof:
+//   * in iteration 0 every message is x = cwh + 0 + 0 = cwh = -(k * f) / 2 with an integer |k| <= 255 and
+//     f = sqrtf(24 / variance).  variance = (sum2 - sum^2/174) / 174 <= sum2 / 174 <= 255^2, so f >= sqrt(24)/255 >
+//     0.0192 and x is 0 or |x| >= 0.0096 > 2^-6.71 (f infinite or NaN -- variance 0 or, by rounding, below 0 -- gives
+//     infinite or NaN x: no guard needed, see above);
+//   * t = fast_tanh(x) = x r(x^2) with r(u) = (945 + 105 u + u^2) / (945 + 420 u + 15 u^2): zero only for x = 0.
+//     r falls on u >= 0 (the numerator of r' is -297675 - 26460 u - 1155 u^2), so for |x| <= 4.97 it is at least
+//     r(4.97^2) = 0.2026, hence |t| >= 0.2026 * 0.0096 > 2^-9.01; beyond 4.97 the clamp gives |t| = 1.  The handful of
+//     roundings in f, x and t move these by parts in 2^-22: take |t| > 2^-9.1;
+//   * a row product multiplies at most six such t (rows have six or seven members and skip one); |t| <= 1.0073, so no
+//     partial product leaves the normal range, none is zero unless a factor is, and each of the five roundings loses
+//     at most 2^-24 of the value: P is 0 or |P| > 2^-54.6 (1 - 2^-24)^5 > 2^-55 > 2^-59 = T.
+// (What the guard of iteration k > 0 sees depends on the sums of messages and has no such bound.)
 __device__ __forceinline__ uint32_t guard_key(float v) { return (__float_as_uint(v) << 1) - 1u; }
 constexpr uint32_t kGuardMin = ((127u - 59u) << 24) - 1u;       // guard_key(0x1p-59f)
 
@@ -263,7 +300,9 @@ void ft8_decode_kernel(const uint8_t *__restrict__ mag, const ft8gpu_candidate *
     // seven-member program in which a six-member row multiplies by a stored 1.0f six times.
     const int row6 = d_tab.own6[lane], row7 = d_tab.own7[lane];
     const bool has6 = row6 != kRows - 1, has7 = row7 != kRows - 1;
-    // the spare row only needs finite content (idle lanes of the variable side read and write it)
+    // The spare row holds 1.0f for the whole kernel: lanes without a third variable read their three products from it,
+    // and nothing stores to it after this -- the stores to slot[6..8] run under has[2], and no lane owns row kRows - 1
+    // (has6 / has7).  The guard relies on it: those lanes contribute |1.0f| to its minimum, which changes nothing.
     if (lane < 8) toc[slot_index(kRows - 1, lane)] = 1.0f;
     wave_lds_sync();
 
@@ -295,6 +334,7 @@ void ft8_decode_kernel(const uint8_t *__restrict__ mag, const ft8gpu_candidate *
     // the nine row products of the previous iteration, in the pairing of the states they turn into
     f2 PA[3] = { { 0.0f, 0.0f }, { 0.0f, 0.0f }, { 0.0f, 0.0f } }, PB = { 0.0f, 0.0f };
     float pc = 0.0f;
+    const float m735 = bpm::vgpr_m735();      // fast_atanh's -735.0f, in a vector register for the whole loop (bp_math.h)
 
     // One iteration up to the stores of toc, in the arithmetic form FAST selects (packed rcp/fma division and
     // half-domain sums, or IEEE division and the reference's own domain).  The two forms are complete,
@@ -310,16 +350,19 @@ void ft8_decode_kernel(const uint8_t *__restrict__ mag, const ft8gpu_candidate *
         float c2;
         if (iter > 0) {                                  // wave-uniform
 #pragma unroll
-            for (int r = 0; r < 2; ++r) A[r] = atanh_pair<FAST>(PA[r]);
-            B = atanh_pair<FAST>(PB);
+            for (int r = 0; r < 2; ++r) A[r] = atanh_pair<FAST>(PA[r], m735);
+            B = atanh_pair<FAST>(PB, m735);
             // The 18 lanes without a third variable (n = lane + 128 >= 174) sit its three edges out under the EXEC
             // mask, as do the 45 lanes without a second check row further down.  The instruction count is the same;
             // what it saves is switching power -- the kernel runs power-limited at about 2.0 GHz, and idle lanes
             // multiplying spare-row garbage cost clock: 1.7 % of the step in interleaved A/B runs.
-            A[2] = f2{ 0.0f, 0.0f };
-            c2 = 0.0f;
+            // Their A[2] and c2 only feed X[2], z and the decision bit that has2_mask clears, none of which leaves the
+            // lane (the tanh and its stores below run under has[2] as well), so any register content serves: they keep
+            // whatever the registers hold and nothing is spent on zeroing them.
+            A[2] = f2{ any_f32(), any_f32() };
+            c2 = any_f32();
             if (has[2]) {
-                A[2] = atanh_pair<FAST>(PA[2]);
+                A[2] = atanh_pair<FAST>(PA[2], m735);
                 c2 = atanh_one<FAST>(pc);
             }
         } else {
@@ -329,7 +372,7 @@ void ft8_decode_kernel(const uint8_t *__restrict__ mag, const ft8gpu_candidate *
             c2 = 0.0f;
         }
         // ---- hard decision and Tnm / x for the lane's nine edges
-        // (lanes without a third variable compute on spare-row content and write to the spare row)
+        // (lanes without a third variable compute on unspecified register content; nothing of it is stored)
         f2 X[3], Y;
         float z;
         if (FAST) {
@@ -435,7 +478,7 @@ void ft8_decode_kernel(const uint8_t *__restrict__ mag, const ft8gpu_candidate *
         if (has6) {                                                           // 59 lanes (EXEC mask)
             const float4 lo = planeLO[row6], hi = planeHI[row6];
             const float v0 = lo.x, v1 = lo.y, v2 = lo.z, v3 = lo.w, v4 = hi.x, v5 = hi.y;
-            const f2 o01 = (((f2{ v1, v0 } * v2) * v3) * v4) * v5;           // skip 0 | skip 1
+            const f2 o01 = (mul_bcast_hi(f2{ v1, v0 } * v2, f2{ lo.z, lo.w }) * v4) * v5;   // skip 0 | skip 1: ((. * v2) * v3) ...
             const float p2 = v0 * v1;
             const float p3 = p2 * v2;
             const float p4 = p3 * v3;
@@ -447,13 +490,15 @@ void ft8_decode_kernel(const uint8_t *__restrict__ mag, const ft8gpu_candidate *
         if (has7) {                                                           // 24 lanes
             const float4 lo = planeLO[row7], hi = planeHI[row7];
             const float v0 = lo.x, v1 = lo.y, v2 = lo.z, v3 = lo.w, v4 = hi.x, v5 = hi.y, v6 = hi.z;
-            const f2 o01 = ((((f2{ v1, v0 } * v2) * v3) * v4) * v5) * v6;
+            const f2 h23 = { hi.z, hi.w };                                    // (v6, 1.0f)
+            const f2 o01 = mul_bcast_lo((mul_bcast_hi(f2{ v1, v0 } * v2, f2{ lo.z, lo.w }) * v4) * v5, h23);
             const float p2 = v0 * v1;
             const float p3 = p2 * v2;
             const float p4 = p3 * v3;
-            const float p5 = p4 * v4;
-            const f2 o23 = ((f2{ p2 * v3, p3 } * v4) * v5) * v6;
-            const f2 o45 = f2{ p4 * v5, p5 } * v6;                            // skip 4 | skip 5
+            const f2 p45 = f2{ v5, v4 } * p4;                                 // (p4 * v5, p5)
+            const float p5 = p45.y;
+            const f2 o23 = mul_bcast_lo((f2{ p2 * v3, p3 } * v4) * v5, h23);
+            const f2 o45 = mul_bcast_lo(p45, h23);                           // skip 4 | skip 5
             const float o6 = p5 * v5;
             planeLO[row7] = make_float4(o01.x, o01.y, o23.x, o23.y);
             planeHI[row7] = make_float4(o45.x, o45.y, o6, 1.0f);
@@ -466,26 +511,26 @@ void ft8_decode_kernel(const uint8_t *__restrict__ mag, const ft8gpu_candidate *
         PB = f2{ toc[slot[0]], toc[slot[3]] };
         PA[2] = f2{ toc[slot[8]], toc[slot[7]] };
         pc = toc[slot[6]];
-        // Lanes without a third variable run these three edges on whatever the spare row holds; nothing
-        // they compute leaves the spare row or their own registers (their decision bit is masked), so the
-        // guard ignores them.
+        // Lanes without a third variable read the spare row's 1.0f here (see its initialisation), which cannot lower
+        // the minimum, so the guard needs no select for them.  Iteration 0 is not tested at all (proof at guard_key).
         // Quick form of the guard: the smallest magnitude of the nine products (four v_min3_f32 with |.|
         // modifiers; a NaN operand is skipped).  If it is at least 2^-59 there is neither a tiny value nor a
         // zero and the guard holds; otherwise (exact zeros are common in the first two iterations, rare
         // afterwards) the exact key test below decides.
-        float mabs = min3_abs(pc, PA[2].x, PA[2].y);
-        mabs = has[2] ? mabs : __builtin_inff();
-        mabs = min3_abs(mabs, PB.x, PB.y);
-        mabs = min3_abs(mabs, PA[0].x, PA[0].y);
-        mabs = min3_abs(mabs, PA[1].x, PA[1].y);
-        bool guard_ok = __all(mabs >= 0x1p-59f);
-        if (!guard_ok) {                                              // wave-uniform
-            uint32_t g2 = min(guard_key(pc), min(guard_key(PA[2].x), guard_key(PA[2].y)));
-            g2 = has[2] ? g2 : 0xFFFFFFFFu;
-            uint32_t gmin = min(g2, min(guard_key(PB.x), guard_key(PB.y)));
+        bool guard_ok = true;                                         // iteration 0: by construction (see guard_key)
+        if (iter > 0) {                                               // wave-uniform
+            float mabs = min3_abs(pc, PA[2].x, PA[2].y);
+            mabs = min3_abs(mabs, PB.x, PB.y);
+            mabs = min3_abs(mabs, PA[0].x, PA[0].y);
+            mabs = min3_abs(mabs, PA[1].x, PA[1].y);
+            guard_ok = __all(mabs >= 0x1p-59f);
+            if (!guard_ok) {                                          // wave-uniform
+                uint32_t gmin = min(guard_key(pc), min(guard_key(PA[2].x), guard_key(PA[2].y)));
+                gmin = min(gmin, min(guard_key(PB.x), guard_key(PB.y)));
 #pragma unroll
-            for (int r = 0; r < 2; ++r) gmin = min(gmin, min(guard_key(PA[r].x), guard_key(PA[r].y)));
-            guard_ok = __all(gmin >= kGuardMin);
+                for (int r = 0; r < 2; ++r) gmin = min(gmin, min(guard_key(PA[r].x), guard_key(PA[r].y)));
+                guard_ok = __all(gmin >= kGuardMin);
+            }
         }
         fast_ok = guard_ok && !force_ieee_div;                        // wave-uniform; governs the whole next iteration
         // (the next iteration's toc stores hit only this lane's own slots; LDS is in order per wave)

@@ -166,7 +166,8 @@ def main():
     # the scalar group screen passes, about one iteration in eight) and the exact guard key (integer minima; taken
     # when a row product is zero or below 2^-59: the first two iterations)
     for r, (lab, hdr, ops, text) in zip(rows, [b for b in blocks if b[1] == loop]):
-        only_moves = len(ops) > 0 and all(op.startswith("v_mov") for op in ops)          # zero-initialisation of the messages: iteration 0 only
+        vops = [op for op in ops if not op.startswith("s_")]                               # (a scalar move or a wait may share the block)
+        only_moves = len(vops) > 0 and all(op.startswith("v_mov") for op in vops)        # zero-initialisation of the messages: iteration 0 only
         r["rare"] = bool(r.get("vmem", 0) > 0 or sum(op.startswith("v_min_u32") for op in ops) >= 4 or only_moves)
     if args.v:
         print(f"{'block':12s} {'stream':8s} " + " ".join(f"{k:>9s}" for k in keys) + "  rare")
