@@ -464,6 +464,117 @@ static_assert(sizeof(ft8gpu_ap_params) == 100 && offsetof(ft8gpu_ap_params, osd_
  * returns the untruncated length.  Host-side text formatting, no GPU involved. */
 int ft8gpu_format_messages(const ft8gpu_message *msgs, int32_t n, char *out, size_t cap);
 
+/* ---- hashed call signs: a call hash table per receiver, carried from one 15 s slot into the next ---------------------------
+ * (DESIGN.md "Call hash table"; not in the reference, whose ft8_lib era prints "<...>" for every hashed call.)  A type 1 / 2
+ * message may carry a call as a 22-bit hash, and a type 4 message carries one of its two calls as a 12-bit hash; a receiver
+ * names the sender from the calls it has heard in clear.  ft8gpu_message.text keeps "<...>"; the resolved text is a second
+ * record array beside the messages.  The rule is exact, integers and bytes only:
+ *
+ * Hash.  The call, left-justified in 11 characters and padded with blanks, read as a base-38 number over " 0-9A-Z/" (blank
+ * = 0 .. '/' = 37), times 47055833459 modulo 2^64; the m-bit hash is the top m bits.  h22 is the 22-bit hash, and the 12-bit
+ * hash is h22 >> 10.
+ *
+ * State.  One ft8gpu_callhash_state per receiver, caller-owned, read at entry and written at exit, in host or device memory
+ * like the arrays of the call.  entry[i] holds the last call written with h22 >> 10 == i: `call` left-justified with blanks
+ * at `len` and behind it, len = 0 for an empty entry (a len above 11 reads as 11), h22 its 22-bit hash.  stamp[i] is the value
+ * of `slot` when entry[i] was written, slot the number of slots consumed so far, pad is zero.  ft8gpu_callhash_reset zeroes
+ * all of it.
+ *
+ * Per slot (one frame of the receiver), with the frame's records [0, n), n = n_msgs[f] clamped to [0, 50], and the fields
+ * taken from a91 as unpack77 takes them (i3 = bits 74..76; type 1 / 2: n28a = bits 0..27, n28b = bits 29..56; type 4:
+ * n12 = bits 0..11, n58 = bits 12..69, iflip = bit 70, icq = bit 73).  NTOKENS = 2063592, MAX22 = 4194304.
+ *   Insert phase.  The records in order, within a record the first call field before the second; every call that travels in
+ *   clear is written to entry[h22 >> 10] with stamp = slot, over whatever is there: the last writer in (record, field) order
+ *   wins.  A call in clear is
+ *     - i3 = 1 or 2, a field with n28 >= NTOKENS + MAX22: the standard call as unpack77 prints it, without /R or /P (and
+ *       without the 3DA0 / 3X rewriting of later ft8_lib versions, which this unpacker does not do);
+ *     - i3 = 4: the 11 characters of n58 without leading and trailing blanks, also when icq is set; nothing if none is left.
+ *   Special tokens, hashed fields (resolved or not), free text, telemetry and every other i3 insert nothing.
+ *   Resolve phase, against the table as it stands after the slot's own inserts (a message resolves against a call heard in
+ *   the same slot, whichever record came first).
+ *     - i3 = 1 or 2, a field with NTOKENS <= n28 < NTOKENS + MAX22: h = n28 - NTOKENS is looked up at entry[h >> 10]; it
+ *       resolves iff len != 0, the entry is not expired, and the stored h22 == h;
+ *     - i3 = 4 with icq = 0: entry[n12]; it resolves iff len != 0 and the entry is not expired.
+ *     An entry is expired when max_age != 0 and (uint32_t)(slot - stamp) > max_age (unsigned: the counter may wrap);
+ *     max_age = 0 never expires.
+ *   Then slot increments, also for a slot without records.
+ *
+ * Output.  One ft8gpu_resolved per record, parallel to msgs [nframes][50]; records at index n and above are not touched.
+ *   n_hashed       hashed fields of the record by a91 (0 .. 2);  n_inserted  calls it inserted (0 .. 2, the overwritten too)
+ *   resolved_mask  bit k set iff the k-th hashed field resolved, k counted in text order: for i3 = 1 / 2 the first field
+ *                  before the second, for i3 = 4 the only one;  n_resolved = the number of set bits
+ *   text           msgs.text (its first 25 bytes up to a NUL) with the k-th "<...>" replaced by '<' call[0 .. len) '>' where
+ *                  bit k is set, cut at 39 characters and zero-filled behind the string.  '<' is not in the free-text
+ *                  alphabet and no other field prints one, so "<...>" in a message text comes only from a hashed field, and
+ *                  the k-th one is the k-th hashed field.  The longest text is two 11-character calls and "R FN20": 34. */
+typedef struct {
+    char     call[11];       /*  0  left-justified, blanks at len and behind it */
+    uint8_t  len;            /* 11  0 = empty */
+    uint32_t h22;            /* 12  the 22-bit hash of call */
+} ft8gpu_callhash_entry;
+#define FT8GPU_CALLHASH_ENTRIES 4096
+typedef struct {
+    ft8gpu_callhash_entry entry[FT8GPU_CALLHASH_ENTRIES];   /*     0  direct-mapped by the 12-bit hash = h22 >> 10 */
+    uint32_t stamp[FT8GPU_CALLHASH_ENTRIES];                 /* 65536  the value of `slot` when the entry was written */
+    uint32_t slot;                                           /* 81920  slots consumed so far */
+    uint32_t pad[3];                                         /* 81924  zero */
+} ft8gpu_callhash_state;
+typedef struct {
+    char    text[40];        /*  0 */
+    uint8_t n_hashed;        /* 40 */
+    uint8_t n_resolved;      /* 41 */
+    uint8_t n_inserted;      /* 42 */
+    uint8_t resolved_mask;   /* 43 */
+    uint8_t pad[4];          /* 44  zero */
+} ft8gpu_resolved;
+#ifndef __cplusplus
+_Static_assert(sizeof(ft8gpu_callhash_entry) == 16 && offsetof(ft8gpu_callhash_entry, len) == 11 &&
+               offsetof(ft8gpu_callhash_entry, h22) == 12, "ft8gpu_callhash_entry layout");
+_Static_assert(sizeof(ft8gpu_callhash_state) == 81936 && offsetof(ft8gpu_callhash_state, stamp) == 65536 &&
+               offsetof(ft8gpu_callhash_state, slot) == 81920 && offsetof(ft8gpu_callhash_state, pad) == 81924,
+               "ft8gpu_callhash_state layout");
+_Static_assert(sizeof(ft8gpu_resolved) == 48 && offsetof(ft8gpu_resolved, n_hashed) == 40 && offsetof(ft8gpu_resolved, n_resolved) == 41 &&
+               offsetof(ft8gpu_resolved, n_inserted) == 42 && offsetof(ft8gpu_resolved, resolved_mask) == 43 &&
+               offsetof(ft8gpu_resolved, pad) == 44, "ft8gpu_resolved layout");
+#else
+static_assert(sizeof(ft8gpu_callhash_entry) == 16 && offsetof(ft8gpu_callhash_entry, len) == 11 &&
+              offsetof(ft8gpu_callhash_entry, h22) == 12, "ft8gpu_callhash_entry layout");
+static_assert(sizeof(ft8gpu_callhash_state) == 81936 && offsetof(ft8gpu_callhash_state, stamp) == 65536 &&
+              offsetof(ft8gpu_callhash_state, slot) == 81920 && offsetof(ft8gpu_callhash_state, pad) == 81924,
+              "ft8gpu_callhash_state layout");
+static_assert(sizeof(ft8gpu_resolved) == 48 && offsetof(ft8gpu_resolved, n_hashed) == 40 && offsetof(ft8gpu_resolved, n_resolved) == 41 &&
+              offsetof(ft8gpu_resolved, n_inserted) == 42 && offsetof(ft8gpu_resolved, resolved_mask) == 43 &&
+              offsetof(ft8gpu_resolved, pad) == 44, "ft8gpu_resolved layout");
+#endif
+/* stage entry: msgs [nstreams][nslots][50], n_msgs [nstreams][nslots], resolved [nstreams][nslots][50]: nstreams independent
+ * receivers, each with nslots consecutive slots; state [nstreams], one object per receiver (the states of a call must be
+ * distinct objects: receivers run side by side), 16-byte aligned in the device form.  FT8GPU_HOST_PTRS / FT8GPU_DEVICE_PTRS
+ * for every array, state included.  Any nstreams * nslots: the host form stages whole receivers, or runs of slots of one
+ * receiver, at most max_frames frames at a time, and the result does not depend on the cut -- as nslots slots in one call
+ * leave the bytes that nslots calls of one slot leave.  nslots <= 2^24. */
+int ft8gpu_resolve_calls(ft8gpu_ctx *ctx, const ft8gpu_message *msgs, const int32_t *n_msgs, int nstreams, int nslots,
+                         ft8gpu_callhash_state *state, uint32_t max_age, ft8gpu_resolved *resolved, int flags);
+/* The whole path: ft8gpu_decode_messages (ap_params == NULL) or ft8gpu_decode_messages_ap (n_by_stage NULL) over the
+ * nstreams * nslots frames iq [nstreams][nslots][2][48000], then ft8gpu_resolve_calls on its records.  msgs and n_msgs are
+ * byte for byte what that entry writes.  With ft8gpu_rx_stream in front, a daemon carries two states per receiver from slot
+ * to slot: the filter state and this one. */
+int ft8gpu_decode_messages_resolved(ft8gpu_ctx *ctx, const float *iq, int nstreams, int nslots, const ft8gpu_ap_params *ap_params,
+                                    ft8gpu_callhash_state *state, uint32_t max_age, ft8gpu_message *msgs, int32_t *n_msgs,
+                                    ft8gpu_resolved *resolved, int flags);
+/* Host helpers of the table (plain C, no GPU).  A call is 1 .. 11 characters of " 0-9A-Z/" without a leading or trailing
+ * blank, NUL-terminated; anything else is refused with -1. */
+void ft8gpu_callhash_reset(ft8gpu_callhash_state *state);
+/* the bits-bit hash (1 .. 32) of call */
+int  ft8gpu_call_hash(const char *call, int bits, uint32_t *out);
+/* writes call into state as the insert phase does, with stamp = state->slot: e.g. the operator's own call before the first slot */
+int  ft8gpu_callhash_insert(ft8gpu_callhash_state *state, const char *call);
+/* the resolve phase's lookup of a hash of 12 or 22 bits at state->slot: 1 and the call in out (NUL-terminated), else 0 and
+ * out[0] = 0; -1 for other bits or a hash that does not fit them */
+int  ft8gpu_callhash_lookup(const ft8gpu_callhash_state *state, int bits, uint32_t hash, uint32_t max_age, char out[12]);
+/* ft8gpu_format_messages with the resolved text: "%3d %4.1f %4d ~  %s\n" of msgs[i].snr_db, dt_s, (int)freq_hz and
+ * resolved[i].text, for i < n (at most 50) */
+int  ft8gpu_format_resolved(const ft8gpu_message *msgs, const ft8gpu_resolved *resolved, int32_t n, char *out, size_t cap);
+
 /* ---- tooling: encoder + synthetic frames (pack77 / ft8_encode / CPFSK synth of
  *      decoderSelfTest, rtlsdr_ft8d.c:924-955) --------------------------------------------- */
 /* Message text -> 77 bits in 10 bytes (pack77, :927); 0 = ok, -1 = the text fits no message type.  Tokens are separated

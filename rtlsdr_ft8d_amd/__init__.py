@@ -47,6 +47,14 @@ AP_MAX_HYPOTHESES = 4       # FT8GPU_AP_MAX_HYPOTHESES
 AP_MAX_HARD_ERRORS = 40     # FT8GPU_AP_MAX_HARD_ERRORS, the recommended gate
 assert RESULT_DTYPE.itemsize == 28 and CAND_DTYPE.itemsize == 8 and MESSAGE_DTYPE.itemsize == 64 and OSD_INFO_DTYPE.itemsize == 8
 assert AP_INFO_DTYPE.itemsize == 8 and AP_HYP_DTYPE.itemsize == 20
+# ft8gpu_callhash_entry / ft8gpu_callhash_state / ft8gpu_resolved: the call hash table of a receiver (ft8gpu_resolve_calls)
+CALLHASH_ENTRIES = 4096     # FT8GPU_CALLHASH_ENTRIES
+CALLHASH_ENTRY_DTYPE = np.dtype([("call", "S11"), ("len", "u1"), ("h22", "<u4")])
+CALLHASH_STATE_DTYPE = np.dtype([("entry", CALLHASH_ENTRY_DTYPE, (CALLHASH_ENTRIES,)), ("stamp", "<u4", (CALLHASH_ENTRIES,)),
+                                 ("slot", "<u4"), ("pad", "<u4", (3,))])
+RESOLVED_DTYPE = np.dtype([("text", "S40"), ("n_hashed", "u1"), ("n_resolved", "u1"), ("n_inserted", "u1"),
+                           ("resolved_mask", "u1"), ("pad", "u1", (4,))])
+assert CALLHASH_ENTRY_DTYPE.itemsize == 16 and CALLHASH_STATE_DTYPE.itemsize == 81936 and RESOLVED_DTYPE.itemsize == 48
 assert STATUS_DTYPE.itemsize == 48 and SIGNAL_DTYPE.itemsize == 92
 
 
@@ -110,6 +118,8 @@ ABI_SYMBOLS = [
     "ft8gpu_decode_messages_passes", "ft8gpu_mask_messages", "ft8gpu_append_messages",
     "ft8gpu_osd_candidates", "ft8gpu_decode_messages_deep",
     "ft8gpu_ap_candidates", "ft8gpu_ap_from_text", "ft8gpu_decode_messages_ap",
+    "ft8gpu_resolve_calls", "ft8gpu_decode_messages_resolved", "ft8gpu_callhash_reset", "ft8gpu_call_hash",
+    "ft8gpu_callhash_insert", "ft8gpu_callhash_lookup", "ft8gpu_format_resolved",
     "ft8_find_sync", "ft8_decode", "ft8_encode", "pack77",            # ft8_lib level (include/ft8_lib/ft8/*.h)
     "initFFTW", "freeFFTW", "ft8_subsystem", "ft8gpu_read_raw_iq", "ft8gpu_read_c2", "ft8gpu_write_raw_iq",
 ]
@@ -248,6 +258,15 @@ def _declare(L):
         L.ft8gpu_ap_candidates.argtypes = [vp, vp, vp, vp, vp, C.c_int, vp, C.c_int, C.c_int, vp, vp, C.c_int]
         L.ft8gpu_ap_from_text.argtypes = [C.c_char_p, vp]
         L.ft8gpu_decode_messages_ap.argtypes = [vp, vp, C.c_int, C.POINTER(ApParams), vp, vp, vp, C.c_int]
+    if hasattr(L, "ft8gpu_resolve_calls"):                # absent from older builds loaded by load_library_at
+        L.ft8gpu_resolve_calls.argtypes = [vp, vp, vp, C.c_int, C.c_int, vp, C.c_uint32, vp, C.c_int]
+        L.ft8gpu_decode_messages_resolved.argtypes = [vp, vp, C.c_int, C.c_int, C.POINTER(ApParams), vp, C.c_uint32, vp, vp, vp, C.c_int]
+        L.ft8gpu_callhash_reset.argtypes = [vp]
+        L.ft8gpu_callhash_reset.restype = None
+        L.ft8gpu_call_hash.argtypes = [C.c_char_p, C.c_int, C.POINTER(C.c_uint32)]
+        L.ft8gpu_callhash_insert.argtypes = [vp, C.c_char_p]
+        L.ft8gpu_callhash_lookup.argtypes = [vp, C.c_int, C.c_uint32, C.c_uint32, vp]
+        L.ft8gpu_format_resolved.argtypes = [vp, vp, C.c_int32, vp, C.c_size_t]
     L.ft8gpu_rx_decimate.argtypes = [vp, vp, C.c_int, C.c_size_t, vp, C.c_int, C.c_int]
     if hasattr(L, "ft8gpu_rx_stream"):                    # absent from older builds loaded by load_library_at
         L.ft8gpu_rx_stream.argtypes = [vp, vp, C.c_int, C.c_int, C.c_size_t, vp, vp, vp, C.c_int, C.c_int]
@@ -320,6 +339,58 @@ def ap_from_text(pattern):
     if rc != 0:
         raise ValueError(f"{pattern!r} is no a-priori pattern of a standard message")
     return out[0]
+
+
+def call_hash(call, bits=22):
+    """ft8gpu_call_hash: the bits-bit hash of a call of 1 .. 11 characters of " 0-9A-Z/" """
+    out = C.c_uint32(0)
+    if load_library().ft8gpu_call_hash(call.encode(), int(bits), C.byref(out)) != 0:
+        raise ValueError(f"{call!r} is no call the hash table takes, or bits {bits} is outside 1 .. 32")
+    return out.value
+
+
+def callhash_state(n=1):
+    """n reset call hash tables (CALLHASH_STATE_DTYPE [n], all zero: what ft8gpu_callhash_reset leaves)"""
+    return np.zeros(n, CALLHASH_STATE_DTYPE)
+
+
+def _one_state(state):
+    assert isinstance(state, np.ndarray) and state.dtype == CALLHASH_STATE_DTYPE and state.size == 1 and state.flags["C_CONTIGUOUS"]
+    return state
+
+
+def callhash_reset(state):
+    """ft8gpu_callhash_reset on one state (a CALLHASH_STATE_DTYPE array of one element, in place)"""
+    load_library().ft8gpu_callhash_reset(_one_state(state).ctypes.data)
+
+
+def callhash_insert(state, call):
+    """ft8gpu_callhash_insert: e.g. the operator's own call, before the first slot (in place)"""
+    if load_library().ft8gpu_callhash_insert(_one_state(state).ctypes.data, call.encode()) != 0:
+        raise ValueError(f"{call!r} is no call the hash table takes")
+
+
+def callhash_lookup(state, bits, hash_value, max_age=0):
+    """ft8gpu_callhash_lookup: the call a 12- or 22-bit hash resolves to at the state's slot, or None"""
+    buf = C.create_string_buffer(12)
+    rc = load_library().ft8gpu_callhash_lookup(_one_state(state).ctypes.data, int(bits), int(hash_value), int(max_age), buf)
+    if rc < 0:
+        raise ValueError(f"bits {bits} / hash {hash_value}: not a 12- or 22-bit hash")
+    return buf.value.decode() if rc else None
+
+
+def format_resolved(msgs, resolved, n):
+    """ft8gpu_format_resolved: the lines of format_messages with the resolved text"""
+    L = load_library()
+    msgs, resolved = np.ascontiguousarray(msgs), np.ascontiguousarray(resolved)
+    assert msgs.dtype == MESSAGE_DTYPE and resolved.dtype == RESOLVED_DTYPE
+    n = int(min(n, msgs.size, resolved.size))
+    need = L.ft8gpu_format_resolved(msgs.ctypes.data, resolved.ctypes.data, n, None, 0)
+    if need < 0:
+        raise Ft8GpuError("ft8gpu_format_resolved failed")
+    buf = C.create_string_buffer(need + 1)
+    L.ft8gpu_format_resolved(msgs.ctypes.data, resolved.ctypes.data, n, buf, len(buf))
+    return buf.value.decode()
 
 
 def _ap_hyps(hyps):
@@ -660,6 +731,61 @@ class Decoder:
         self._ck(self.lib.ft8gpu_decode_messages_ap(self.h, iq.ctypes.data, B, C.byref(p), msgs.ctypes.data, n.ctypes.data,
                                                     nbs.ctypes.data, HOST_PTRS))
         return msgs, n, nbs
+
+    def resolve_calls(self, msgs, n_msgs, state=None, max_age=0, resolved=None):
+        """ft8gpu_resolve_calls.  msgs: MESSAGE_DTYPE [nstreams][nslots][50], n_msgs: int32 [nstreams][nslots]; state:
+        CALLHASH_STATE_DTYPE [nstreams] as a previous call returned it, or None for reset tables (the caller's array stays as it
+        is); resolved: an array to write into (records at and above a frame's count keep its bytes; zeros when None)
+        -> (resolved RESOLVED_DTYPE [nstreams][nslots][50], the exit state [nstreams])"""
+        msgs = np.ascontiguousarray(msgs)
+        n_msgs = np.ascontiguousarray(n_msgs, np.int32)
+        nstreams, nslots = n_msgs.shape
+        assert msgs.dtype == MESSAGE_DTYPE and msgs.shape == (nstreams, nslots, MAX_MESSAGES)
+        state = np.zeros(nstreams, CALLHASH_STATE_DTYPE) if state is None else np.array(state, CALLHASH_STATE_DTYPE, copy=True, ndmin=1)
+        assert state.shape == (nstreams,)
+        if resolved is None:
+            resolved = np.zeros((nstreams, nslots, MAX_MESSAGES), RESOLVED_DTYPE)
+        assert resolved.dtype == RESOLVED_DTYPE and resolved.shape == (nstreams, nslots, MAX_MESSAGES) and resolved.flags["C_CONTIGUOUS"]
+        self._ck(self.lib.ft8gpu_resolve_calls(self.h, msgs.ctypes.data, n_msgs.ctypes.data, nstreams, nslots, state.ctypes.data,
+                                               int(max_age), resolved.ctypes.data, HOST_PTRS))
+        return resolved, state
+
+    def resolve_calls_dev(self, msgs_dev, n_msgs_dev, nstreams, nslots, state_dev, max_age, resolved_dev):
+        """all arrays in HBM, 16-byte aligned: msgs [nstreams][nslots][50] 64-byte records, n_msgs [nstreams][nslots] int32,
+        state [nstreams] 81 936-byte tables (updated in place), resolved [nstreams][nslots][50] 48-byte records"""
+        self._ck(self.lib.ft8gpu_resolve_calls(self.h, _ptr(msgs_dev), _ptr(n_msgs_dev), nstreams, nslots, _ptr(state_dev),
+                                               int(max_age), _ptr(resolved_dev), DEVICE_PTRS))
+
+    def decode_messages_resolved(self, iq, state=None, max_age=0, ap=None, msgs=None, resolved=None):
+        """ft8gpu_decode_messages_resolved.  iq: float32 [nstreams][nslots][2][48000]; ap: None (ft8gpu_decode_messages) or the
+        keyword arguments of decode_messages_ap as a dict (passes, hyps, ap_max_hard_errors, osd_order, osd_max_hard_errors)
+        -> (msgs [nstreams][nslots][50], n_msgs [nstreams][nslots], resolved [nstreams][nslots][50], the exit state [nstreams])"""
+        iq = np.ascontiguousarray(iq, np.float32)
+        nstreams, nslots = iq.shape[:2]
+        assert iq.shape[2:] == (2, NSAMPLES)
+        state = np.zeros(nstreams, CALLHASH_STATE_DTYPE) if state is None else np.array(state, CALLHASH_STATE_DTYPE, copy=True, ndmin=1)
+        assert state.shape == (nstreams,)
+        if msgs is None:
+            msgs = np.zeros((nstreams, nslots, MAX_MESSAGES), MESSAGE_DTYPE)
+        if resolved is None:
+            resolved = np.zeros((nstreams, nslots, MAX_MESSAGES), RESOLVED_DTYPE)
+        assert msgs.dtype == MESSAGE_DTYPE and msgs.shape == (nstreams, nslots, MAX_MESSAGES) and msgs.flags["C_CONTIGUOUS"]
+        assert resolved.dtype == RESOLVED_DTYPE and resolved.shape == (nstreams, nslots, MAX_MESSAGES) and resolved.flags["C_CONTIGUOUS"]
+        n = np.zeros((nstreams, nslots), np.int32)
+        p = None if ap is None else C.byref(_ap_params(ap.get("passes", 1), ap.get("hyps", ("CQ ? ?",)),
+                                                       ap.get("ap_max_hard_errors", AP_MAX_HARD_ERRORS), ap.get("osd_order", -1),
+                                                       ap.get("osd_max_hard_errors", OSD_MAX_HARD_ERRORS)))
+        self._ck(self.lib.ft8gpu_decode_messages_resolved(self.h, iq.ctypes.data, nstreams, nslots, p, state.ctypes.data, int(max_age),
+                                                          msgs.ctypes.data, n.ctypes.data, resolved.ctypes.data, HOST_PTRS))
+        return msgs, n, resolved, state
+
+    def decode_messages_resolved_dev(self, iq_dev, nstreams, nslots, state_dev, max_age, msgs_dev, n_msgs_dev, resolved_dev, ap=None):
+        """the same with every array in HBM; ap as in decode_messages_resolved"""
+        p = None if ap is None else C.byref(_ap_params(ap.get("passes", 1), ap.get("hyps", ("CQ ? ?",)),
+                                                       ap.get("ap_max_hard_errors", AP_MAX_HARD_ERRORS), ap.get("osd_order", -1),
+                                                       ap.get("osd_max_hard_errors", OSD_MAX_HARD_ERRORS)))
+        self._ck(self.lib.ft8gpu_decode_messages_resolved(self.h, _ptr(iq_dev), nstreams, nslots, p, _ptr(state_dev), int(max_age),
+                                                          _ptr(msgs_dev), _ptr(n_msgs_dev), _ptr(resolved_dev), DEVICE_PTRS))
 
     # ---- device-pointer API (inputs and outputs resident in HBM) --------------------------------
     def ap_candidates_dev(self, mag_dev, cands_dev, counts_dev, status_in_dev, nframes, hyps, max_hard_errors, status_out_dev, info_dev):

@@ -15,6 +15,7 @@
 #include "../../include/ft8_lib/ft8/encode.h"
 #include "ft8_tables.h"
 
+#include <stdio.h>
 #include <string.h>
 
 #define NTOKENS  2063592
@@ -55,6 +56,72 @@ static int call_hash(const char *call, int len, int bits, uint32_t *out) {
     }
     *out = (uint32_t)((47055833459ull * n) >> (64 - bits));
     return 0;
+}
+
+/* ---- the call hash table of a receiver, host side (ft8gpu.h "hashed call signs"; csrc/callhash.hip is the kernel) -------- */
+void ft8gpu_callhash_reset(ft8gpu_callhash_state *state) {
+    if (state) memset(state, 0, sizeof *state);
+}
+
+/* the length of a call the table takes: 1 .. 11 characters of the alphabet, no blank at either end; else -1 */
+static int table_call_len(const char *call) {
+    if (!call) return -1;
+    const size_t len = strnlen(call, 12);
+    if (len < 1 || len > 11 || call[0] == ' ' || call[len - 1] == ' ') return -1;
+    for (size_t i = 0; i < len; ++i) if (idx_in(A_CALL11, call[i]) < 0) return -1;
+    return (int)len;
+}
+
+int ft8gpu_call_hash(const char *call, int bits, uint32_t *out) {
+    const int len = table_call_len(call);
+    if (len < 0 || bits < 1 || bits > 32 || !out) return -1;
+    return call_hash(call, len, bits, out);
+}
+
+int ft8gpu_callhash_insert(ft8gpu_callhash_state *state, const char *call) {
+    const int len = table_call_len(call);
+    uint32_t h22;
+    if (!state || len < 0 || call_hash(call, len, 22, &h22) != 0) return -1;
+    ft8gpu_callhash_entry *e = &state->entry[h22 >> 10];
+    memset(e->call, ' ', sizeof e->call);
+    memcpy(e->call, call, (size_t)len);
+    e->len = (uint8_t)len;
+    e->h22 = h22;
+    state->stamp[h22 >> 10] = state->slot;
+    return 0;
+}
+
+int ft8gpu_callhash_lookup(const ft8gpu_callhash_state *state, int bits, uint32_t hash, uint32_t max_age, char out[12]) {
+    if (out) out[0] = 0;
+    if (!state || !out || (bits != 12 && bits != 22) || hash >> bits) return -1;
+    const uint32_t i = bits == 22 ? hash >> 10 : hash;
+    const ft8gpu_callhash_entry *e = &state->entry[i];
+    if (e->len == 0) return 0;
+    if (max_age != 0 && (uint32_t)(state->slot - state->stamp[i]) > max_age) return 0;
+    if (bits == 22 && e->h22 != hash) return 0;
+    const size_t len = e->len > 11 ? 11 : e->len;
+    memcpy(out, e->call, len);
+    out[len] = 0;
+    return 1;
+}
+
+int ft8gpu_format_resolved(const ft8gpu_message *msgs, const ft8gpu_resolved *resolved, int32_t n, char *out, size_t cap) {
+    char line[96];
+    size_t at = 0;
+    if (out && cap) out[0] = 0;
+    if (n > 0 && (!msgs || !resolved)) return -1;
+    for (int32_t i = 0; i < n && i < FT8GPU_K_MAX_MESSAGES; i++) {
+        const int len = snprintf(line, sizeof line, "%3d %4.1f %4d ~  %.40s\n", msgs[i].snr_db, (double)msgs[i].dt_s,
+                                 (int)msgs[i].freq_hz, resolved[i].text);
+        if (len < 0) continue;
+        if (out && at < cap) {
+            const size_t room = cap - at - 1, k = (size_t)len < room ? (size_t)len : room;
+            memcpy(out + at, line, k);
+            out[at + k] = 0;
+        }
+        at += (size_t)len;
+    }
+    return (int)at;
 }
 
 /* ---- 28-bit code of a standard call (no suffix): -1 if the text is not one ---------------------- */
