@@ -575,6 +575,136 @@ int  ft8gpu_callhash_lookup(const ft8gpu_callhash_state *state, int bits, uint32
  * resolved[i].text, for i < n (at most 50) */
 int  ft8gpu_format_resolved(const ft8gpu_message *msgs, const ft8gpu_resolved *resolved, int32_t n, char *out, size_t cap);
 
+/* ---- expected messages: undecoded candidates against what a receiver heard in earlier slots ------------------------------
+ * (DESIGN.md "Expected messages"; not in the reference, which treats every 15 s slot as if nothing had been heard before it.)
+ * FT8 traffic repeats: the same CQ two slots later, the RRR / RR73 / 73 that closes a QSO.  A receiver keeps a table of
+ * expected payloads, and every candidate BP fails on is compared with the codewords of the table: a full 77-bit hypothesis
+ * where AP uses a partial one.  The rule is exact, integers and float comparisons only.
+ *
+ * State.  One ft8gpu_expect_state per receiver, caller-owned, in host or device memory like the arrays of the call.
+ * entry[i]: payload = 77 bits, MSB first, as ft8gpu_pack77 writes them (bits 77..79 are ignored wherever a payload is read
+ * and zero wherever one is written); used != 0 = the entry is live; kind 0 = heard, 1 = derived; stamp = the value of `slot`
+ * at the last write or refresh.  cursor (read modulo 512) is where the next new entry goes, slot the number of slots
+ * consumed so far, pad is zero.  An entry is expired when max_age != 0 and (uint32_t)(slot - stamp) > max_age (unsigned:
+ * the counter may wrap); max_age = 0 never expires.  Expiry is judged only when candidates are matched: an expired entry
+ * stays in the table and can be refreshed.
+ *
+ * Matching (ft8gpu_match_candidates; the states are read only).
+ *   A candidate qualifies as for OSD: its status record has ok == 0 and ldpc_errors != 0; one that does not gets
+ *   status_out = status_in and an all-zero info record.
+ *   llr[0..173], h[i] = llr[i] > 0 and w[i] = 255 if |llr[i]| >= 32 else (int)(|llr[i]| * 8) are exactly OSD's.  A non-finite
+ *   llr[i]: result 6, nothing is compared.
+ *   The live entries of the frame's state are those with used != 0 that are not expired at state.slot.  None: result 0, the
+ *   info record is all zero and the status is copied.
+ *   c_j = the codeword of live entry j's payload: the 77 bits, their CRC-14 as ft8_lib's encoder computes it, the 83 generator
+ *   parities.  nhard_j = the number of positions where c_j differs from h, metric_j = the sum of w over those positions.
+ *   The best entry has the smallest metric, ties go to the smallest table index; info.index is that index, info.nhard and
+ *   info.metric its values, accepted or not.
+ *   Only the best entry is judged; the first failing check names the result: 5 all-zero payload, 2 nhard > max_hard_errors,
+ *   4 unpack77 < 0, else 1 = accepted.  (3 and 7 do not occur here; the numbering stays that of OSD and AP.)
+ *   On acceptance the status record becomes that of a BP success, as OSD writes it (ok = 1, ldpc_errors = 0, both CRC fields
+ *   the codeword's CRC, unpack_status, a91, text; iters as it was); otherwise it is unchanged.
+ *
+ * Update (ft8gpu_expect_update).  Each receiver takes its slots in order, within a slot the records [0, n) in order,
+ * n = n_msgs[f] clamped to [0, 50].  The record's payload P (the first 77 bits of a91) goes through insert(P, 0).  With
+ * derive != 0, a record of type 1 (i3 = bits 74..76 = 1) whose two call fields are standard calls in clear (n28 >= NTOKENS +
+ * MAX22, the constants of the call hash rule) then inserts three derived payloads with kind 1: the two 29-bit call fields
+ * swapped (bits 0..28 and 29..57 change places, each call keeps its /R or /P flag), ir (bit 58) = 0, i3 = 1, and igrid4
+ * (bits 59..73) = 32402, 32403, 32404 in that order: RRR, RR73, 73.  CQ and the other special tokens, hashed fields, i3 = 2
+ * and every other message type derive nothing.
+ *   insert(P, kind): if an entry with used != 0 and the same 77 bits exists, expired or not (the smallest index if a
+ *   caller-built state holds several), its stamp = slot and its kind &= kind -- a message once heard stays kind 0.  Otherwise
+ *   entry[cursor % 512] = { P, used = 1, kind, stamp = slot } and cursor = cursor % 512 + 1.
+ * After the slot's records slot increments, also for a slot without records. */
+#define FT8GPU_EXPECT_ENTRIES 512
+typedef struct {
+    uint8_t  payload[10];    /*  0 */
+    uint8_t  used;           /* 10 */
+    uint8_t  kind;           /* 11 */
+    uint32_t stamp;          /* 12 */
+} ft8gpu_expect_entry;
+typedef struct {
+    ft8gpu_expect_entry entry[FT8GPU_EXPECT_ENTRIES];   /*    0 */
+    uint32_t cursor;                                    /* 8192 */
+    uint32_t slot;                                      /* 8196 */
+    uint32_t pad[2];                                    /* 8200  zero */
+} ft8gpu_expect_state;
+typedef struct {
+    uint8_t  result;         /* 0 not attempted or no live entry, 1 accepted, 2, 4, 5 the failing check, 6 non-finite soft bits */
+    uint8_t  nhard;          /* the best entry's values, accepted or not */
+    uint16_t index;
+    int32_t  metric;
+} ft8gpu_match_info;
+typedef struct {
+    int32_t  max_hard_errors;    /* 0 .. 174; FT8GPU_MATCH_MAX_HARD_ERRORS is the recommended value */
+    uint32_t max_age;            /* slots; 0 = entries never expire */
+    int32_t  derive;             /* != 0: the update rule derives RRR / RR73 / 73 */
+} ft8gpu_expect_params;
+#ifndef __cplusplus
+_Static_assert(sizeof(ft8gpu_expect_entry) == 16 && offsetof(ft8gpu_expect_entry, used) == 10 && offsetof(ft8gpu_expect_entry, kind) == 11 &&
+               offsetof(ft8gpu_expect_entry, stamp) == 12, "ft8gpu_expect_entry layout");
+_Static_assert(sizeof(ft8gpu_expect_state) == 8208 && offsetof(ft8gpu_expect_state, cursor) == 8192 &&
+               offsetof(ft8gpu_expect_state, slot) == 8196 && offsetof(ft8gpu_expect_state, pad) == 8200, "ft8gpu_expect_state layout");
+_Static_assert(sizeof(ft8gpu_match_info) == 8 && offsetof(ft8gpu_match_info, nhard) == 1 && offsetof(ft8gpu_match_info, index) == 2 &&
+               offsetof(ft8gpu_match_info, metric) == 4, "ft8gpu_match_info layout");
+_Static_assert(sizeof(ft8gpu_expect_params) == 12 && offsetof(ft8gpu_expect_params, max_age) == 4 &&
+               offsetof(ft8gpu_expect_params, derive) == 8, "ft8gpu_expect_params layout");
+#else
+static_assert(sizeof(ft8gpu_expect_entry) == 16 && offsetof(ft8gpu_expect_entry, used) == 10 && offsetof(ft8gpu_expect_entry, kind) == 11 &&
+              offsetof(ft8gpu_expect_entry, stamp) == 12, "ft8gpu_expect_entry layout");
+static_assert(sizeof(ft8gpu_expect_state) == 8208 && offsetof(ft8gpu_expect_state, cursor) == 8192 &&
+              offsetof(ft8gpu_expect_state, slot) == 8196 && offsetof(ft8gpu_expect_state, pad) == 8200, "ft8gpu_expect_state layout");
+static_assert(sizeof(ft8gpu_match_info) == 8 && offsetof(ft8gpu_match_info, nhard) == 1 && offsetof(ft8gpu_match_info, index) == 2 &&
+              offsetof(ft8gpu_match_info, metric) == 4, "ft8gpu_match_info layout");
+static_assert(sizeof(ft8gpu_expect_params) == 12 && offsetof(ft8gpu_expect_params, max_age) == 4 &&
+              offsetof(ft8gpu_expect_params, derive) == 8, "ft8gpu_expect_params layout");
+#endif
+/* Recommended max_hard_errors, from profiles/match_gain.json (tools/match_gain.py, a sweep over 30 .. 60): the largest gate
+ * that accepts nothing wrong on the 96 CQ frames of 20 and of 30 signals at -22 .. 0 dB (7119 / 8078 failing candidates, the
+ * planted messages and 236 unrelated CQ messages in the table) and on 96 noise frames (942 candidates, 256 unrelated CQ
+ * messages).  The wrong best entries begin at 50 hard errors on both CQ rows and at 54 on noise; at 49 matching gains 334 /
+ * 494 planted messages over BP's 1046 / 1295 (+32 % / +38 %; AP gains 42 and OSD order 2 gains 30 on the first row).  Nothing
+ * but the gate keeps a wrong entry out: every table entry is a codeword with a good CRC.  The hazard is a message on the air
+ * whose near relative is in the table while it is not itself: on 48 two-call frames whose table holds RRR / RR73 / 73 / -10
+ * of every planted pair but never the message, 7 of 3867 candidates accept a sibling at 49 (0.15 per frame; 1 at 45, 13 at
+ * 50).  A caller that lists closings without hearing them (derive, or its own list) and cannot afford those uses 40: no
+ * sibling is accepted up to 42, and the gain on the first row is still 236. */
+#define FT8GPU_MATCH_MAX_HARD_ERRORS 49
+/* stage entry: mag [nframes][94208], cands / status_in / status_out / info [nframes][max_candidates], counts [nframes],
+ * states [nframes] (the state of the receiver each frame belongs to; 16-byte aligned in the device form); host or device
+ * pointers by `flags`.  max_hard_errors in [0, 174].  Records below counts[f] are written, records at and behind it are
+ * not touched.  status_out may be status_in. */
+int ft8gpu_match_candidates(ft8gpu_ctx *ctx, const uint8_t *mag, const ft8gpu_candidate *cands, const int32_t *counts,
+                            const ft8gpu_decode_status *status_in, int nframes, const ft8gpu_expect_state *states,
+                            uint32_t max_age, int max_hard_errors, ft8gpu_decode_status *status_out, ft8gpu_match_info *info,
+                            int flags);
+/* stage entry of the update rule: msgs [nstreams][nslots][50], n_msgs [nstreams][nslots], state [nstreams], one object per
+ * receiver, read at entry and written at exit; host or device pointers by `flags` (device form: msgs and state 16-byte
+ * aligned).  The host form stages whole receivers, or runs of slots of one receiver, at most max_frames frames at a time;
+ * the result does not depend on the cut. */
+int ft8gpu_expect_update(ft8gpu_ctx *ctx, const ft8gpu_message *msgs, const int32_t *n_msgs, int nstreams, int nslots,
+                         ft8gpu_expect_state *state, int derive, int flags);
+/* The whole path over iq [nstreams][nslots][2][48000], for the frame of receiver r at slot t:
+ *   1. the records [0, n1) are byte for byte those of ft8gpu_decode_messages;
+ *   2. ft8gpu_match_candidates runs in place on that frame's BP status records, against the receiver's state as the slots
+ *      0 .. t - 1 left it;
+ *   3. the append step of the multi-pass path (ft8gpu_append_messages' rule) adds, in candidate order, every unique gained
+ *      message not yet among the frame's records, up to 50 in all; pad[2] of such a record is 1;
+ *   4. the update rule runs over the frame's final records.
+ * n_by_stage [nstreams][nslots][2] (NULL: not written): the count after BP and after matching.  nslots slots in one call
+ * leave the bytes that nslots calls of one slot leave, in msgs, n_msgs and the state.  Not composed with AP, OSD or
+ * multi-pass. */
+int ft8gpu_decode_messages_expected(ft8gpu_ctx *ctx, const float *iq, int nstreams, int nslots, ft8gpu_expect_state *state,
+                                    const ft8gpu_expect_params *params, ft8gpu_message *msgs, int32_t *n_msgs,
+                                    int32_t *n_by_stage, int flags);
+/* Host helpers of the table (plain C, no GPU): a caller builds any list for the stage entry with them, e.g. the replies it
+ * expects to its own call. */
+void ft8gpu_expect_reset(ft8gpu_expect_state *state);
+/* insert(payload, kind) of the update rule at state->slot; kind 0 or 1, else -1 */
+int  ft8gpu_expect_insert(ft8gpu_expect_state *state, const uint8_t payload[10], int kind);
+/* the same with the payload ft8gpu_pack77 gives for text, as kind 0; -1 if the packer refuses the text */
+int  ft8gpu_expect_insert_text(ft8gpu_expect_state *state, const char *text);
+
 /* ---- tooling: encoder + synthetic frames (pack77 / ft8_encode / CPFSK synth of
  *      decoderSelfTest, rtlsdr_ft8d.c:924-955) --------------------------------------------- */
 /* Message text -> 77 bits in 10 bytes (pack77, :927); 0 = ok, -1 = the text fits no message type.  Tokens are separated

@@ -56,6 +56,13 @@ RESOLVED_DTYPE = np.dtype([("text", "S40"), ("n_hashed", "u1"), ("n_resolved", "
                            ("resolved_mask", "u1"), ("pad", "u1", (4,))])
 assert CALLHASH_ENTRY_DTYPE.itemsize == 16 and CALLHASH_STATE_DTYPE.itemsize == 81936 and RESOLVED_DTYPE.itemsize == 48
 assert STATUS_DTYPE.itemsize == 48 and SIGNAL_DTYPE.itemsize == 92
+# ft8gpu_expect_entry / ft8gpu_expect_state / ft8gpu_match_info: the expected messages of a receiver (ft8gpu_match_candidates)
+EXPECT_ENTRIES = 512        # FT8GPU_EXPECT_ENTRIES
+EXPECT_ENTRY_DTYPE = np.dtype([("payload", "u1", (10,)), ("used", "u1"), ("kind", "u1"), ("stamp", "<u4")])
+EXPECT_STATE_DTYPE = np.dtype([("entry", EXPECT_ENTRY_DTYPE, (EXPECT_ENTRIES,)), ("cursor", "<u4"), ("slot", "<u4"), ("pad", "<u4", (2,))])
+MATCH_INFO_DTYPE = np.dtype([("result", "u1"), ("nhard", "u1"), ("index", "<u2"), ("metric", "<i4")])
+MATCH_MAX_HARD_ERRORS = 49  # FT8GPU_MATCH_MAX_HARD_ERRORS, the recommended gate
+assert EXPECT_ENTRY_DTYPE.itemsize == 16 and EXPECT_STATE_DTYPE.itemsize == 8208 and MATCH_INFO_DTYPE.itemsize == 8
 
 
 class Params(C.Structure):
@@ -77,6 +84,11 @@ class ApParams(C.Structure):
     osd_max_hard_errors 0..83, hyps[4]"""
     _fields_ = [("passes", C.c_int32), ("nhyp", C.c_int32), ("ap_max_hard_errors", C.c_int32), ("osd_order", C.c_int32),
                 ("osd_max_hard_errors", C.c_int32), ("hyps", ApHypothesis * 4)]
+
+
+class ExpectParams(C.Structure):
+    """ft8gpu_expect_params: max_hard_errors 0..174, max_age in slots (0: never expires), derive != 0: RRR / RR73 / 73"""
+    _fields_ = [("max_hard_errors", C.c_int32), ("max_age", C.c_uint32), ("derive", C.c_int32)]
 
 
 class Timings(C.Structure):
@@ -120,6 +132,8 @@ ABI_SYMBOLS = [
     "ft8gpu_ap_candidates", "ft8gpu_ap_from_text", "ft8gpu_decode_messages_ap",
     "ft8gpu_resolve_calls", "ft8gpu_decode_messages_resolved", "ft8gpu_callhash_reset", "ft8gpu_call_hash",
     "ft8gpu_callhash_insert", "ft8gpu_callhash_lookup", "ft8gpu_format_resolved",
+    "ft8gpu_match_candidates", "ft8gpu_expect_update", "ft8gpu_decode_messages_expected", "ft8gpu_expect_reset",
+    "ft8gpu_expect_insert", "ft8gpu_expect_insert_text",
     "ft8_find_sync", "ft8_decode", "ft8_encode", "pack77",            # ft8_lib level (include/ft8_lib/ft8/*.h)
     "initFFTW", "freeFFTW", "ft8_subsystem", "ft8gpu_read_raw_iq", "ft8gpu_read_c2", "ft8gpu_write_raw_iq",
 ]
@@ -267,6 +281,14 @@ def _declare(L):
         L.ft8gpu_callhash_insert.argtypes = [vp, C.c_char_p]
         L.ft8gpu_callhash_lookup.argtypes = [vp, C.c_int, C.c_uint32, C.c_uint32, vp]
         L.ft8gpu_format_resolved.argtypes = [vp, vp, C.c_int32, vp, C.c_size_t]
+    if hasattr(L, "ft8gpu_match_candidates"):             # absent from older builds loaded by load_library_at
+        L.ft8gpu_match_candidates.argtypes = [vp, vp, vp, vp, vp, C.c_int, vp, C.c_uint32, C.c_int, vp, vp, C.c_int]
+        L.ft8gpu_expect_update.argtypes = [vp, vp, vp, C.c_int, C.c_int, vp, C.c_int, C.c_int]
+        L.ft8gpu_decode_messages_expected.argtypes = [vp, vp, C.c_int, C.c_int, vp, C.POINTER(ExpectParams), vp, vp, vp, C.c_int]
+        L.ft8gpu_expect_reset.argtypes = [vp]
+        L.ft8gpu_expect_reset.restype = None
+        L.ft8gpu_expect_insert.argtypes = [vp, vp, C.c_int]
+        L.ft8gpu_expect_insert_text.argtypes = [vp, C.c_char_p]
     L.ft8gpu_rx_decimate.argtypes = [vp, vp, C.c_int, C.c_size_t, vp, C.c_int, C.c_int]
     if hasattr(L, "ft8gpu_rx_stream"):                    # absent from older builds loaded by load_library_at
         L.ft8gpu_rx_stream.argtypes = [vp, vp, C.c_int, C.c_int, C.c_size_t, vp, vp, vp, C.c_int, C.c_int]
@@ -377,6 +399,35 @@ def callhash_lookup(state, bits, hash_value, max_age=0):
     if rc < 0:
         raise ValueError(f"bits {bits} / hash {hash_value}: not a 12- or 22-bit hash")
     return buf.value.decode() if rc else None
+
+
+def expect_state(n=1):
+    """n reset tables of expected messages (EXPECT_STATE_DTYPE [n], all zero: what ft8gpu_expect_reset leaves)"""
+    return np.zeros(n, EXPECT_STATE_DTYPE)
+
+
+def _one_expect_state(state):
+    assert isinstance(state, np.ndarray) and state.dtype == EXPECT_STATE_DTYPE and state.size == 1 and state.flags["C_CONTIGUOUS"]
+    return state
+
+
+def expect_reset(state):
+    """ft8gpu_expect_reset on one state (an EXPECT_STATE_DTYPE array of one element, in place)"""
+    load_library().ft8gpu_expect_reset(_one_expect_state(state).ctypes.data)
+
+
+def expect_insert(state, payload, kind=0):
+    """ft8gpu_expect_insert: insert(payload, kind) of the update rule at the state's slot (in place); payload: 10 bytes"""
+    payload = np.ascontiguousarray(payload, np.uint8)
+    assert payload.shape == (10,)
+    if load_library().ft8gpu_expect_insert(_one_expect_state(state).ctypes.data, payload.ctypes.data, int(kind)) != 0:
+        raise ValueError(f"kind {kind} is neither 0 (heard) nor 1 (derived)")
+
+
+def expect_insert_text(state, text):
+    """ft8gpu_expect_insert_text: the message as ft8gpu_pack77 packs it, as a heard entry (in place)"""
+    if load_library().ft8gpu_expect_insert_text(_one_expect_state(state).ctypes.data, text.encode()) != 0:
+        raise ValueError(f"cannot pack {text!r} as an FT8 message")
 
 
 def format_resolved(msgs, resolved, n):
@@ -786,6 +837,81 @@ class Decoder:
                                                        ap.get("osd_max_hard_errors", OSD_MAX_HARD_ERRORS)))
         self._ck(self.lib.ft8gpu_decode_messages_resolved(self.h, _ptr(iq_dev), nstreams, nslots, p, _ptr(state_dev), int(max_age),
                                                           _ptr(msgs_dev), _ptr(n_msgs_dev), _ptr(resolved_dev), DEVICE_PTRS))
+
+    def match_candidates(self, mag, cands, counts, status_in, states, max_age=0, max_hard_errors=MATCH_MAX_HARD_ERRORS,
+                         status_out=None, info=None):
+        """ft8gpu_match_candidates.  states: EXPECT_STATE_DTYPE [B], the table of the receiver each frame belongs to (read only)
+        -> (status_out [B][cap] STATUS_DTYPE, info [B][cap] MATCH_INFO_DTYPE), new arrays; records at and behind counts[f] keep
+        what status_out / info held (zeros when None)"""
+        mag = np.ascontiguousarray(mag, np.uint8).reshape(-1, MAG_ARRAY)
+        B = mag.shape[0]
+        cands = np.ascontiguousarray(cands)
+        counts = np.ascontiguousarray(counts, np.int32)
+        status_in = np.ascontiguousarray(status_in).view(np.uint8).reshape(B, self.max_candidates, 48)
+        states = np.ascontiguousarray(states)
+        assert cands.shape == (B, self.max_candidates) and cands.dtype == CAND_DTYPE and counts.shape == (B,)
+        assert states.dtype == EXPECT_STATE_DTYPE and states.shape == (B,)
+        out = np.zeros((B, self.max_candidates, 48), np.uint8) if status_out is None else \
+            np.array(status_out, copy=True, order="C").view(np.uint8).reshape(B, self.max_candidates, 48)
+        inf = np.zeros((B, self.max_candidates), MATCH_INFO_DTYPE) if info is None else \
+            np.array(info, copy=True, order="C").view(MATCH_INFO_DTYPE).reshape(B, self.max_candidates)
+        self._ck(self.lib.ft8gpu_match_candidates(self.h, mag.ctypes.data, cands.ctypes.data, counts.ctypes.data, status_in.ctypes.data,
+                                                  B, states.ctypes.data, int(max_age), int(max_hard_errors), out.ctypes.data,
+                                                  inf.ctypes.data, HOST_PTRS))
+        return out.view(STATUS_DTYPE).reshape(B, self.max_candidates), inf
+
+    def match_candidates_dev(self, mag_dev, cands_dev, counts_dev, status_in_dev, nframes, states_dev, max_age, max_hard_errors,
+                             status_out_dev, info_dev):
+        """status_out_dev may be status_in_dev; states_dev: [nframes] 8208-byte tables, 16-byte aligned; info_dev: 8-byte records"""
+        self._ck(self.lib.ft8gpu_match_candidates(self.h, _ptr(mag_dev), _ptr(cands_dev), _ptr(counts_dev), _ptr(status_in_dev), nframes,
+                                                  _ptr(states_dev), int(max_age), int(max_hard_errors), _ptr(status_out_dev),
+                                                  _ptr(info_dev), DEVICE_PTRS))
+
+    def expect_update(self, msgs, n_msgs, state=None, derive=True):
+        """ft8gpu_expect_update.  msgs: MESSAGE_DTYPE [nstreams][nslots][50], n_msgs: int32 [nstreams][nslots]; state:
+        EXPECT_STATE_DTYPE [nstreams] as a previous call returned it, or None for reset tables (the caller's array stays as it
+        is) -> the exit state [nstreams]"""
+        msgs = np.ascontiguousarray(msgs)
+        n_msgs = np.ascontiguousarray(n_msgs, np.int32)
+        nstreams, nslots = n_msgs.shape
+        assert msgs.dtype == MESSAGE_DTYPE and msgs.shape == (nstreams, nslots, MAX_MESSAGES)
+        state = np.zeros(nstreams, EXPECT_STATE_DTYPE) if state is None else np.array(state, EXPECT_STATE_DTYPE, copy=True, ndmin=1)
+        assert state.shape == (nstreams,)
+        self._ck(self.lib.ft8gpu_expect_update(self.h, msgs.ctypes.data, n_msgs.ctypes.data, nstreams, nslots, state.ctypes.data,
+                                               int(bool(derive)), HOST_PTRS))
+        return state
+
+    def expect_update_dev(self, msgs_dev, n_msgs_dev, nstreams, nslots, state_dev, derive=True):
+        """all arrays in HBM; msgs and state 16-byte aligned; the states are updated in place"""
+        self._ck(self.lib.ft8gpu_expect_update(self.h, _ptr(msgs_dev), _ptr(n_msgs_dev), nstreams, nslots, _ptr(state_dev),
+                                               int(bool(derive)), DEVICE_PTRS))
+
+    def decode_messages_expected(self, iq, state=None, max_hard_errors=MATCH_MAX_HARD_ERRORS, max_age=0, derive=True, msgs=None):
+        """ft8gpu_decode_messages_expected.  iq: float32 [nstreams][nslots][2][48000]; state as in expect_update
+        -> (msgs [nstreams][nslots][50], n_msgs [nstreams][nslots], n_by_stage [nstreams][nslots][2]: the count after BP and
+        after matching, the exit state [nstreams]); pad[2] of a record gained by matching is 1"""
+        iq = np.ascontiguousarray(iq, np.float32)
+        nstreams, nslots = iq.shape[:2]
+        assert iq.shape[2:] == (2, NSAMPLES)
+        state = np.zeros(nstreams, EXPECT_STATE_DTYPE) if state is None else np.array(state, EXPECT_STATE_DTYPE, copy=True, ndmin=1)
+        assert state.shape == (nstreams,)
+        if msgs is None:
+            msgs = np.zeros((nstreams, nslots, MAX_MESSAGES), MESSAGE_DTYPE)
+        assert msgs.dtype == MESSAGE_DTYPE and msgs.shape == (nstreams, nslots, MAX_MESSAGES) and msgs.flags["C_CONTIGUOUS"]
+        n = np.zeros((nstreams, nslots), np.int32)
+        nbs = np.zeros((nstreams, nslots, 2), np.int32)
+        p = ExpectParams(int(max_hard_errors), int(max_age), int(bool(derive)))
+        self._ck(self.lib.ft8gpu_decode_messages_expected(self.h, iq.ctypes.data, nstreams, nslots, state.ctypes.data, C.byref(p),
+                                                          msgs.ctypes.data, n.ctypes.data, nbs.ctypes.data, HOST_PTRS))
+        return msgs, n, nbs, state
+
+    def decode_messages_expected_dev(self, iq_dev, nstreams, nslots, state_dev, max_hard_errors, max_age, derive, msgs_dev, n_msgs_dev,
+                                     n_by_stage_dev=None):
+        """the same with every array in HBM (iq, msgs and state 16-byte aligned); n_by_stage_dev: [nstreams][nslots][2] or None"""
+        p = ExpectParams(int(max_hard_errors), int(max_age), int(bool(derive)))
+        self._ck(self.lib.ft8gpu_decode_messages_expected(self.h, _ptr(iq_dev), nstreams, nslots, _ptr(state_dev), C.byref(p),
+                                                          _ptr(msgs_dev), _ptr(n_msgs_dev),
+                                                          None if n_by_stage_dev is None else _ptr(n_by_stage_dev), DEVICE_PTRS))
 
     # ---- device-pointer API (inputs and outputs resident in HBM) --------------------------------
     def ap_candidates_dev(self, mag_dev, cands_dev, counts_dev, status_in_dev, nframes, hyps, max_hard_errors, status_out_dev, info_dev):

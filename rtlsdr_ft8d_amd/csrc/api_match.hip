@@ -1,0 +1,199 @@
+// api_match.hip -- host side of the expected messages: the stage entries ft8gpu_match_candidates and ft8gpu_expect_update
+// and the whole path ft8gpu_decode_messages_expected (DESIGN.md "Expected messages"; the kernels are match.hip, the host
+// helpers of the table are plain C in ft8_pack.c).
+//
+// Buffers.  The codewords of the tables (24 bytes per entry plus the live masks), the info records and the host form's
+// staging of the states and of status_out live in the context's growable RX buffers, which no other entry uses while this one
+// holds the context's mutex; they grow on the first call that needs them.  Everything else is the staging of the messages path.
+//
+// The whole path cuts its [nstreams][nslots] frames as the call hash table does: whole receivers while a receiver fits into
+// max_frames frames, else runs of consecutive slots of one receiver.  A piece is gathered slot-major (all receivers of the
+// piece's first slot, then of its second, ...), so that the front of the pipeline runs once over the piece and the slot-by-slot
+// part -- match, append, update, each nstreams frames wide -- works on contiguous frames.  One slot per receiver (a daemon's
+// call every 15 s) and one receiver are slot-major already: the device form then works on the caller's arrays.
+#include "match.h"
+#include "ft8gpu_ctx.h"
+
+namespace {
+
+constexpr int kMatchMaxHard = kLdpcN;
+
+int check_match_args(int max_hard_errors) {
+    if (max_hard_errors < 0 || max_hard_errors > kMatchMaxHard)
+        return ft8_fail("max_hard_errors %d out of range [0, %d]", max_hard_errors, kMatchMaxHard);
+    return 0;
+}
+
+// the context's RX buffers as scratch of at least these sizes (0: not needed)
+int ensure_match_buffers(ft8gpu_ctx *c, size_t work, size_t states, size_t status, size_t info) {
+    if (work > c->rx_sums_cap || states > c->rx_p2_cap || status > c->rx_iq_cap || info > c->rx_raw_cap)
+        HIP_TRY(hipStreamSynchronize(c->stream));                   // the old buffers may still be in use
+    if (grow_buffer(&c->d_rx_sums, &c->rx_sums_cap, work)) return -1;
+    if (grow_buffer(&c->d_rx_p2, &c->rx_p2_cap, states)) return -1;
+    if (grow_buffer((void **)&c->d_rx_iq, &c->rx_iq_cap, status)) return -1;
+    if (grow_buffer((void **)&c->d_rx_raw, &c->rx_raw_cap, info)) return -1;
+    return 0;
+}
+
+// rows of `width` bytes between two arrays with different strides (host or device on either side)
+hipError_t copy_rows(void *dst, size_t dpitch, const void *src, size_t spitch, size_t width, int rows, hipStream_t s) {
+    if (rows == 1 || (dpitch == width && spitch == width)) return hipMemcpyAsync(dst, src, width * rows, hipMemcpyDefault, s);
+    return hipMemcpy2DAsync(dst, dpitch, src, spitch, width, (size_t)rows, hipMemcpyDefault, s);
+}
+
+}  // namespace
+
+extern "C" {
+
+int ft8gpu_match_candidates(ft8gpu_ctx *c, const uint8_t *mag, const ft8gpu_candidate *cands, const int32_t *counts,
+                            const ft8gpu_decode_status *status_in, int nframes, const ft8gpu_expect_state *states,
+                            uint32_t max_age, int max_hard_errors, ft8gpu_decode_status *status_out, ft8gpu_match_info *info,
+                            int flags) {
+    CHECK_COMMON(c, nframes);
+    if (check_match_args(max_hard_errors)) return -1;
+    if (nframes == 0) return 0;
+    if (!mag || !cands || !counts || !status_in || !states || !status_out || !info) return ft8_fail("NULL array argument");
+    const bool dev = flags & FT8GPU_DEVICE_PTRS;
+    if (dev && ((uintptr_t)states & 15) != 0) return ft8_fail("states must be 16-byte aligned");
+    if (ensure_messages_buffers(c)) return -1;
+    const int mc = c->params.max_candidates;
+    const size_t piece = (size_t)(nframes < c->max_frames ? nframes : c->max_frames);
+    if (ensure_match_buffers(c, piece * kExpectWorkBytes, dev ? 0 : piece * sizeof(ft8gpu_expect_state),
+                             dev ? 0 : piece * mc * sizeof(ft8gpu_decode_status), dev ? 0 : piece * mc * sizeof(ft8gpu_match_info)))
+        return -1;
+    // records at and behind a frame's count keep the caller's bytes (both outputs are uploaded in the host form)
+    const StageArg a[] = { { mag, c->d_mag, kMagArray, kIn }, { cands, c->d_cands, mc * sizeof(ft8gpu_candidate), kIn },
+                           { counts, c->d_counts, sizeof(int32_t), kIn },
+                           { status_in, c->d_status, mc * sizeof(ft8gpu_decode_status), kIn },
+                           { states, c->d_rx_p2, sizeof(ft8gpu_expect_state), kIn },
+                           { status_out, c->d_rx_iq, mc * sizeof(ft8gpu_decode_status), kInOut },
+                           { info, c->d_rx_raw, mc * sizeof(ft8gpu_match_info), kInOut } };
+    return for_each_chunk(c, nframes, flags & FT8GPU_DEVICE_PTRS, a, [&](int n, void *const *p) {
+        HIP_TRY(launch_expect_encode((const ft8gpu_expect_state *)p[4], n, max_age, c->d_msgtab, c->d_rx_sums, c->stream));
+        HIP_TRY(launch_match((const uint8_t *)p[0], (const ft8gpu_candidate *)p[1], (const int32_t *)p[2],
+                             (const ft8gpu_decode_status *)p[3], (ft8gpu_decode_status *)p[5], (ft8gpu_match_info *)p[6], n, mc,
+                             c->d_rx_sums, max_hard_errors, c->stream));
+        return 0;
+    });
+}
+
+int ft8gpu_expect_update(ft8gpu_ctx *c, const ft8gpu_message *msgs, const int32_t *n_msgs, int nstreams, int nslots,
+                         ft8gpu_expect_state *state, int derive, int flags) {
+    if (!c) return ft8_fail("ctx is NULL");
+    if (nstreams < 0 || nslots < 0) return ft8_fail("nstreams %d / nslots %d: negative", nstreams, nslots);
+    Entry entry_(c);
+    HIP_TRY(entry_.err);
+    if (nstreams == 0 || nslots == 0) return 0;
+    if (!msgs || !n_msgs || !state) return ft8_fail("NULL array argument");
+    const bool dev = flags & FT8GPU_DEVICE_PTRS;
+    if (dev && (((uintptr_t)msgs | (uintptr_t)state) & 15) != 0) return ft8_fail("msgs and state must be 16-byte aligned");
+    if (dev && ((uintptr_t)n_msgs & 3) != 0) return ft8_fail("n_msgs must be 4-byte aligned");
+    // a piece: rg receivers with all their slots, or one receiver with ns of its slots; nothing bounds a piece in the device form
+    const int mf = c->max_frames;
+    const int ns_max = dev || nslots <= mf ? nslots : mf;
+    const int rg_max = dev ? nstreams : (nslots <= mf ? mf / nslots : 1);
+    if (!dev) {
+        if (ensure_match_buffers(c, 0, (size_t)rg_max * sizeof(ft8gpu_expect_state), 0, 0)) return -1;
+        if (!c->d_msgs) HIP_TRY(hipMalloc(&c->d_msgs, (size_t)mf * kMaxMessages * sizeof(ft8gpu_message)));
+    }
+    for (int r0 = 0; r0 < nstreams; r0 += rg_max) {
+        const int rg = nstreams - r0 < rg_max ? nstreams - r0 : rg_max;
+        for (int s0 = 0; s0 < nslots; s0 += ns_max) {
+            const int ns = nslots - s0 < ns_max ? nslots - s0 : ns_max;      // ns < nslots only with rg == 1
+            const size_t f0 = (size_t)r0 * nslots + s0;
+            const StageArg a[] = { { msgs + f0 * kMaxMessages, c->d_msgs, (size_t)ns * kMaxMessages * sizeof(ft8gpu_message), kIn },
+                                   { n_msgs + f0, c->d_nres, (size_t)ns * sizeof(int32_t), kIn },
+                                   { state + r0, c->d_rx_p2, sizeof(ft8gpu_expect_state), kInOut } };
+            const int rc = for_each_chunk(c, rg, flags & FT8GPU_DEVICE_PTRS, a, [&](int n, void *const *p) {
+                HIP_TRY(launch_expect_update((const ft8gpu_message *)p[0], (const int32_t *)p[1], n, ns, (ft8gpu_expect_state *)p[2],
+                                             derive, c->stream));
+                return 0;
+            });
+            if (rc) return rc;
+        }
+    }
+    return 0;
+}
+
+int ft8gpu_decode_messages_expected(ft8gpu_ctx *c, const float *iq, int nstreams, int nslots, ft8gpu_expect_state *state,
+                                    const ft8gpu_expect_params *params, ft8gpu_message *msgs, int32_t *n_msgs,
+                                    int32_t *n_by_stage, int flags) {
+    if (!c) return ft8_fail("ctx is NULL");
+    if (nstreams < 0 || nslots < 0) return ft8_fail("nstreams %d / nslots %d: negative", nstreams, nslots);
+    if ((long long)nstreams * nslots > 0x7FFFFFFF) return ft8_fail("nstreams * nslots = %lld frames: too many", (long long)nstreams * nslots);
+    if (!params) return ft8_fail("params is NULL");
+    if (check_match_args(params->max_hard_errors)) return -1;
+    Entry entry_(c);
+    HIP_TRY(entry_.err);
+    if (nstreams == 0 || nslots == 0) return 0;
+    if (!iq || !state || !msgs || !n_msgs) return ft8_fail("NULL array argument");
+    const bool dev = flags & FT8GPU_DEVICE_PTRS;
+    if (dev && (((uintptr_t)msgs | (uintptr_t)state | (uintptr_t)iq) & 15) != 0) return ft8_fail("iq, msgs and state must be 16-byte aligned");
+    if (ensure_messages_buffers(c)) return -1;
+    const int mf = c->max_frames, mc = c->params.max_candidates;
+    const size_t F = 2 * (size_t)kNSamples * sizeof(float), M = kMaxMessages * sizeof(ft8gpu_message);
+    if (!c->d_iq) HIP_TRY(hipMalloc(&c->d_iq, (size_t)mf * F));
+    if (!c->d_msgs) HIP_TRY(hipMalloc(&c->d_msgs, (size_t)mf * M));
+    if (!c->d_nbs) HIP_TRY(hipMalloc(&c->d_nbs, (size_t)mf * FT8GPU_MAX_PASSES * 2 * sizeof(int32_t)));
+    const int ns_max = nslots <= mf ? nslots : mf;
+    const int rg_max = nslots <= mf ? (nstreams < mf / nslots ? nstreams : mf / nslots) : 1;
+    if (ensure_match_buffers(c, (size_t)rg_max * kExpectWorkBytes, dev ? 0 : (size_t)rg_max * sizeof(ft8gpu_expect_state), 0,
+                             (size_t)rg_max * mc * sizeof(ft8gpu_match_info)))
+        return -1;
+    const int gate = params->max_hard_errors, derive = params->derive;
+    const uint32_t max_age = params->max_age;
+    hipStream_t s = c->stream;
+    for (int r0 = 0; r0 < nstreams; r0 += rg_max) {
+        const int rg = nstreams - r0 < rg_max ? nstreams - r0 : rg_max;
+        ft8gpu_expect_state *st = dev ? state + r0 : (ft8gpu_expect_state *)c->d_rx_p2;
+        if (!dev) HIP_TRY(hipMemcpyAsync(st, state + r0, (size_t)rg * sizeof(ft8gpu_expect_state), hipMemcpyHostToDevice, s));
+        for (int s0 = 0; s0 < nslots; s0 += ns_max) {
+            const int ns = nslots - s0 < ns_max ? nslots - s0 : ns_max;      // ns < nslots only with rg == 1
+            const int nfr = rg * ns;
+            const size_t f0 = (size_t)r0 * nslots + s0;                      // the piece's first frame; receiver r's slot t is f0 + r * nslots + t
+            // A piece whose frames are consecutive in the caller's arrays (one receiver, or one slot per receiver) is slot-major
+            // as it stands: the device form works on the caller's arrays.  Otherwise gather slot-major; slots past a frame's
+            // count keep the caller's bytes, so msgs travels both ways.
+            const bool direct = dev && (rg == 1 || nslots == 1);
+            const float *piq = direct ? iq + f0 * 2 * (size_t)kNSamples : c->d_iq;
+            ft8gpu_message *pm = direct ? msgs + f0 * kMaxMessages : c->d_msgs;
+            int32_t *pn = direct ? n_msgs + f0 : c->d_nres;
+            int32_t *pb = direct && n_by_stage ? n_by_stage + 2 * f0 : c->d_nbs;
+            for (int t = 0; t < ns && !direct; ++t) {
+                HIP_TRY(copy_rows((char *)c->d_iq + (size_t)t * rg * F, F, (const char *)iq + (f0 + t) * F, (size_t)nslots * F, F, rg, s));
+                HIP_TRY(copy_rows((char *)c->d_msgs + (size_t)t * rg * M, M, (const char *)msgs + (f0 + t) * M, (size_t)nslots * M, M, rg, s));
+            }
+            if (run_pipeline_messages(c, piq, nfr, pm, pn)) return -1;
+            HIP_TRY(hipMemcpy2DAsync(pb, 2 * sizeof(int32_t), pn, sizeof(int32_t), sizeof(int32_t), (size_t)nfr, hipMemcpyDeviceToDevice, s));
+            for (int t = 0; t < ns; ++t) {
+                const size_t o = (size_t)t * rg;
+                ft8gpu_decode_status *status = c->d_status + o * mc;
+                ft8gpu_message *dm = pm + o * kMaxMessages;
+                HIP_TRY(launch_expect_encode(st, rg, max_age, c->d_msgtab, c->d_rx_sums, s));
+                HIP_TRY(launch_match(c->d_mag + o * kMagArray, c->d_cands + o * mc, c->d_counts + o, status, status,
+                                     (ft8gpu_match_info *)c->d_rx_raw, rg, mc, c->d_rx_sums, gate, s));
+                HIP_TRY(launch_append(c->d_mag + o * kMagArray, c->d_base + o * 2 * kNumBin, c->d_cands + o * mc, c->d_counts + o, status,
+                                      c->d_msgtab, nullptr, rg, mc, c->params.min_score, dm, pn + o, s));
+                HIP_TRY(launch_match_tag(pb + 2 * o, 2, pn + o, rg, dm, s));
+                HIP_TRY(launch_expect_update(dm, pn + o, rg, 1, st, derive, s));
+            }
+            HIP_TRY(hipMemcpy2DAsync(pb + 1, 2 * sizeof(int32_t), pn, sizeof(int32_t), sizeof(int32_t), (size_t)nfr, hipMemcpyDeviceToDevice, s));
+            for (int t = 0; t < ns && !direct; ++t) {
+                const size_t o = (size_t)t * rg;
+                HIP_TRY(copy_rows((char *)msgs + (f0 + t) * M, (size_t)nslots * M, (const char *)c->d_msgs + o * M, M, M, rg, s));
+                HIP_TRY(copy_rows(n_msgs + f0 + t, (size_t)nslots * sizeof(int32_t), c->d_nres + o, sizeof(int32_t), sizeof(int32_t), rg, s));
+                if (n_by_stage)
+                    HIP_TRY(copy_rows(n_by_stage + 2 * (f0 + t), (size_t)nslots * 2 * sizeof(int32_t), c->d_nbs + 2 * o, 2 * sizeof(int32_t),
+                                      2 * sizeof(int32_t), rg, s));
+            }
+            HIP_TRY(hipStreamSynchronize(s));                                // the staging buffers are free for the next piece
+        }
+        if (!dev) {
+            HIP_TRY(hipMemcpyAsync(state + r0, st, (size_t)rg * sizeof(ft8gpu_expect_state), hipMemcpyDeviceToHost, s));
+            HIP_TRY(hipStreamSynchronize(s));
+        }
+    }
+    return 0;
+}
+
+}  // extern "C"

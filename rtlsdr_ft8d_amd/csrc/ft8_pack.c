@@ -124,6 +124,40 @@ int ft8gpu_format_resolved(const ft8gpu_message *msgs, const ft8gpu_resolved *re
     return (int)at;
 }
 
+/* ---- the expected messages of a receiver, host side (ft8gpu.h "expected messages"; csrc/match.hip has the kernels) -------- */
+void ft8gpu_expect_reset(ft8gpu_expect_state *state) {
+    if (state) memset(state, 0, sizeof *state);
+}
+
+int ft8gpu_expect_insert(ft8gpu_expect_state *state, const uint8_t payload[10], int kind) {
+    if (!state || !payload || (kind != 0 && kind != 1)) return -1;
+    uint8_t p[10];
+    memcpy(p, payload, 10);
+    p[9] &= 0xF8u;
+    for (int i = 0; i < FT8GPU_EXPECT_ENTRIES; ++i) {
+        ft8gpu_expect_entry *e = &state->entry[i];
+        if (e->used && !memcmp(e->payload, p, 9) && (e->payload[9] & 0xF8u) == p[9]) {
+            e->stamp = state->slot;
+            e->kind &= (uint8_t)kind;
+            return 0;
+        }
+    }
+    const uint32_t at = state->cursor % FT8GPU_EXPECT_ENTRIES;
+    ft8gpu_expect_entry *e = &state->entry[at];
+    memcpy(e->payload, p, 10);
+    e->used = 1;
+    e->kind = (uint8_t)kind;
+    e->stamp = state->slot;
+    state->cursor = at + 1;
+    return 0;
+}
+
+int ft8gpu_expect_insert_text(ft8gpu_expect_state *state, const char *text) {
+    uint8_t p[10];
+    if (!state || !text || ft8gpu_pack77(text, p) != 0) return -1;
+    return ft8gpu_expect_insert(state, p, 0);
+}
+
 /* ---- 28-bit code of a standard call (no suffix): -1 if the text is not one ---------------------- */
 static int32_t pack_basecall(const char *call, int len, int workarounds) {
     char c6[7] = "      ";

@@ -1,0 +1,405 @@
+// match.hip -- the candidates belief propagation gives up on, compared with the messages a receiver expects from earlier
+// slots (include/ft8gpu.h "expected messages", DESIGN.md "Expected messages").  Not part of the reference's path.  The rule is
+// exact (integers and float comparisons), restated in tests/ft8_spec_match.py: soft bits, hard decision h and 8-bit weights
+// as ordered-statistics decoding forms them (osd.hip); every live entry of the receiver's table is a full 77-bit hypothesis,
+// its codeword c_j is compared with h, the entry with the smallest (metric, index) is judged: all-zero, hard errors, unpack77.
+//
+//   ft8_expect_encode_kernel  one lane per table entry, once per frame and call: CRC-14 and the 83 generator parities of the
+//                             payload, the codeword as six dwords in position order, and per round of 64 entries the mask
+//                             of the live ones (used != 0, not expired at the state's slot).
+//   ft8_match_kernel          one wave64 per candidate, four per workgroup, the launch geometry of the LDPC kernel.  A wave
+//                             whose candidate does not qualify copies the record and leaves.  Lanes are table entries: 512
+//                             entries are eight rounds of 64, and a round without a live entry is skipped on the scalar
+//                             side.  h and the weights are wave-uniform: three 64-bit words and eight bit planes of three
+//                             words (ballots, SGPRs), so the metric of an entry is 24 and / popcount pairs on its c_j ^ h
+//                             instead of 174 table steps.  metric << 9 | index through one butterfly minimum is the best
+//                             entry with the rule's tie break.  The epilogue is OSD's: unpack77 on two 64-bit words, the
+//                             48-byte record of a BP success composed in LDS.
+//   ft8_expect_update_kernel  the update rule, one wave per receiver with its table in LDS (8 KB): a receiver is a strictly
+//                             sequential walk over its slots and records; an insert first looks for its 77 bits (eight
+//                             entries per lane, ballots, the smallest index), then refreshes that entry or overwrites the
+//                             one under the cursor.
+#include "match.h"
+#include "unpack_dev.h"
+#include "bp_math.h"
+#include <stddef.h>
+
+namespace {
+
+__constant__ uint8_t c_match_gray[8] = { 0, 1, 3, 2, 5, 6, 4, 7 };
+
+constexpr int kOffRec = 192;                           // dwords: 174 soft bits, then the record
+constexpr int kMatchLds = kOffRec + 12;
+constexpr int kIdxBits = 9;                            // 512 entries; metric <= 174 * 255 < 2^16
+constexpr uint32_t kKeyNone = 0xFFFFFFFFu;
+static_assert(kExpectEntries == 1 << kIdxBits, "the key holds a table index in its low bits");
+static_assert(sizeof(ft8gpu_expect_entry) == 16 && sizeof(ft8gpu_expect_state) == 8208, "table layout");
+
+__device__ __forceinline__ void wave_lds_sync() {
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+}
+__device__ __forceinline__ int wave_sum(int v) {
+#pragma unroll
+    for (int m = 1; m < 64; m <<= 1) v += __shfl_xor(v, m);
+    return __builtin_amdgcn_readfirstlane(v);
+}
+__device__ __forceinline__ uint32_t wave_min(uint32_t v) {
+#pragma unroll
+    for (int m = 1; m < 64; m <<= 1) v = min(v, (uint32_t)__shfl_xor((int)v, m));
+    return (uint32_t)__builtin_amdgcn_readfirstlane((int)v);
+}
+
+// the 77 payload bits of a table entry (or of a91) as two words, MSB first: bits 0..63, and bits 64..76 at the top
+__device__ __forceinline__ void payload_words(uint32_t x, uint32_t y, uint32_t z, uint64_t &w0, uint64_t &w1) {
+    w0 = (uint64_t)__builtin_bswap32(x) << 32 | __builtin_bswap32(y);
+    w1 = (uint64_t)(__builtin_bswap32(z) & 0xFFF80000u) << 32;
+}
+
+__global__ __launch_bounds__(256)
+void ft8_expect_encode_kernel(const ft8gpu_expect_state *__restrict__ states, uint32_t max_age,
+                              const MsgTables *__restrict__ tab, uint32_t *__restrict__ cw, uint64_t *__restrict__ live) {
+    const int frame = blockIdx.y;
+    const int e = blockIdx.x * 256 + threadIdx.x;
+    const ft8gpu_expect_state *st = states + frame;
+    const uint4 ent = reinterpret_cast<const uint4 *>(st->entry)[e];
+    const uint32_t slot = st->slot;
+    const bool used = ((ent.z >> 16) & 0xFFu) != 0u;
+    const bool expired = max_age != 0u && (uint32_t)(slot - ent.w) > max_age;
+    uint64_t w0, w1;
+    payload_words(ent.x, ent.y, ent.z, w0, w1);
+    // CRC-14, polynomial 0x2757, over the 77 bits and five zeros, as ft8_lib's encoder computes it
+    uint32_t rem = 0;
+    for (int bit = 0; bit < 82; ++bit) {
+        const uint32_t b = bit < 64 ? (uint32_t)(w0 >> (63 - bit)) & 1u : (uint32_t)(w1 >> (127 - bit)) & 1u;
+        rem ^= b << 13;
+        rem = (rem & 0x2000u) ? ((rem << 1) ^ 0x2757u) & 0x3FFFu : (rem << 1) & 0x3FFFu;
+    }
+    w1 |= (uint64_t)rem << 37;                                        // bits 77..90
+    // position order: position p at bit p & 63 of word p >> 6
+    uint64_t c0 = __brevll(w0), c1 = __brevll(w1), c2 = 0;
+    const uint32_t m0 = (uint32_t)(w0 >> 32), m1 = (uint32_t)w0, m2 = (uint32_t)(w1 >> 32);
+    for (int m = 0; m < kLdpcM; ++m) {
+        const uint64_t par = (uint64_t)((__popc(m0 & tab->gen[m][0]) + __popc(m1 & tab->gen[m][1]) + __popc(m2 & tab->gen[m][2])) & 1);
+        const int p = kLdpcK + m;
+        if (p < 128) c1 |= par << (p - 64); else c2 |= par << (p - 128);
+    }
+    uint32_t *out = cw + (size_t)frame * (kExpectEntries * 6) + e;
+    out[0 * kExpectEntries] = (uint32_t)c0;
+    out[1 * kExpectEntries] = (uint32_t)(c0 >> 32);
+    out[2 * kExpectEntries] = (uint32_t)c1;
+    out[3 * kExpectEntries] = (uint32_t)(c1 >> 32);
+    out[4 * kExpectEntries] = (uint32_t)c2;
+    out[5 * kExpectEntries] = (uint32_t)(c2 >> 32);
+    const uint64_t mask = __ballot(used && !expired);
+    if ((threadIdx.x & 63) == 0) live[(size_t)frame * kExpectRounds + (e >> 6)] = mask;
+}
+
+// sum of the weights over the set bits of x: weights as eight bit planes
+__device__ __forceinline__ uint32_t metric_of(const uint64_t x[3], const uint64_t (&P)[8][3]) {
+    uint32_t m = 0;
+#pragma unroll
+    for (int b = 0; b < 8; ++b)
+        m += (uint32_t)(__popcll(x[0] & P[b][0]) + __popcll(x[1] & P[b][1]) + __popcll(x[2] & P[b][2])) << b;
+    return m;
+}
+
+__global__ __launch_bounds__(256)
+void ft8_match_kernel(const uint8_t *__restrict__ mag, const ft8gpu_candidate *__restrict__ cands,
+                      const int32_t *__restrict__ counts, const ft8gpu_decode_status *status_in,
+                      ft8gpu_decode_status *status_out, ft8gpu_match_info *info, int nframes, int max_candidates,
+                      const uint32_t *__restrict__ cw_all, const uint64_t *__restrict__ live_all, int max_hard_errors,
+                      unsigned blocks_per_frame) {
+    __shared__ __attribute__((aligned(16))) uint32_t s_mem[4][kMatchLds];
+
+    const int lane = threadIdx.x & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const int frame = (int)(blockIdx.x / blocks_per_frame);
+    const int ci = (int)(blockIdx.x - (unsigned)frame * blocks_per_frame) * 4 + wave;
+    if (frame >= nframes || ci >= max_candidates) return;
+    if (ci >= counts[frame]) return;                                  // wave-uniform: records behind the count are not touched
+
+    const size_t rec_index = (size_t)frame * max_candidates + ci;
+    const uint32_t *in32 = reinterpret_cast<const uint32_t *>(status_in + rec_index);
+    uint32_t *out32 = reinterpret_cast<uint32_t *>(status_out + rec_index);
+    uint32_t *info32 = reinterpret_cast<uint32_t *>(info + rec_index);
+    static_assert(sizeof(ft8gpu_decode_status) == 48 && sizeof(ft8gpu_match_info) == 8, "record sizes");
+
+    // ---- which candidates: ok == 0 and ldpc_errors != 0 (status_out may be status_in: read first) -------------------
+    const uint32_t mine = lane < 12 ? in32[lane] : 0u;
+    const uint32_t dw0 = (uint32_t)__builtin_amdgcn_readlane((int)mine, 0);
+    const uint32_t dw2 = (uint32_t)__builtin_amdgcn_readlane((int)mine, 2);
+    const bool attempt = ((dw2 >> 8) & 0xFFu) == 0u && (dw0 & 0xFFFFu) != 0u;
+    if (!attempt) {
+        if (lane < 12 && out32 != in32) out32[lane] = mine;
+        if (lane < 2) info32[lane] = 0u;
+        return;
+    }
+
+    uint32_t *s = s_mem[wave];
+    float *llr = reinterpret_cast<float *>(s);
+    const ft8gpu_candidate cand = cands[rec_index];
+
+    // ---- ft8_extract_likelihood, ftx_normalize_logl: the LDPC kernel's arithmetic (decode.hip, as in osd.hip) --------
+    if (lane < 58) {
+        const int k = lane;
+        const int sym = k + ((k < 29) ? 7 : 14);
+        const int block = cand.time_offset + sym;
+        int l0 = 0, l1 = 0, l2 = 0;
+        if (block >= 0 && block < kNumBlocks) {
+            const int index = ((cand.time_offset * 2 + cand.time_sub) * 2 + cand.freq_sub) * kNumBin + cand.freq_offset;
+            const uint8_t *ps = mag + (size_t)frame * kMagArray + index + sym * kBlockStride;
+            int s2[8];
+#pragma unroll
+            for (int j = 0; j < 8; ++j) s2[j] = ps[c_match_gray[j]];
+            l0 = max(max(s2[4], s2[5]), max(s2[6], s2[7])) - max(max(s2[0], s2[1]), max(s2[2], s2[3]));
+            l1 = max(max(s2[2], s2[3]), max(s2[6], s2[7])) - max(max(s2[0], s2[1]), max(s2[4], s2[5]));
+            l2 = max(max(s2[1], s2[3]), max(s2[5], s2[7])) - max(max(s2[0], s2[2]), max(s2[4], s2[6]));
+        }
+        llr[3 * k + 0] = (float)l0;
+        llr[3 * k + 1] = (float)l1;
+        llr[3 * k + 2] = (float)l2;
+    }
+    wave_lds_sync();
+
+    float cw[3];
+    bool has[3];
+    int isum = 0, isum2 = 0;
+#pragma unroll
+    for (int r = 0; r < 3; ++r) {
+        const int n = lane + 64 * r;
+        has[r] = n < kLdpcN;
+        cw[r] = has[r] ? llr[n] : 0.0f;
+        const int v = (int)cw[r];
+        isum += v;
+        isum2 += v * v;
+    }
+    const float sum = (float)wave_sum(isum);
+    const float sum2 = (float)wave_sum(isum2);
+    const float inv_n = 1.0f / 174;
+    const float variance = (sum2 - (sum * sum * inv_n)) * inv_n;
+    const float norm_factor = bpm::llr_norm_factor(variance);
+    bool finite = true;
+#pragma unroll
+    for (int r = 0; r < 3; ++r) {
+        cw[r] = has[r] ? cw[r] * norm_factor : 0.0f;
+        finite = finite && (__float_as_uint(cw[r]) & 0x7F800000u) != 0x7F800000u;
+    }
+    if (!__all(finite)) {                                             // wave-uniform: nothing is compared
+        if (lane < 12 && out32 != in32) out32[lane] = mine;
+        if (lane < 2) info32[lane] = lane == 0 ? 6u : 0u;
+        return;
+    }
+
+    // ---- the live entries of the frame's table; none: result 0 ----------------------------------------------------------
+    const uint64_t *live = live_all + (size_t)frame * kExpectRounds;
+    uint64_t lm[kExpectRounds], any = 0ull;
+#pragma unroll
+    for (int r = 0; r < kExpectRounds; ++r) { lm[r] = live[r]; any |= lm[r]; }
+    if (any == 0ull) {
+        if (lane < 12 && out32 != in32) out32[lane] = mine;
+        if (lane < 2) info32[lane] = 0u;
+        return;
+    }
+
+    // ---- hard decisions and weight planes in position order, wave-uniform ----------------------------------------------
+    uint64_t H[3], P[8][3];
+#pragma unroll
+    for (int q = 0; q < 3; ++q) {
+        const uint32_t bits = __float_as_uint(cw[q]);
+        const float a = __uint_as_float(bits & 0x7FFFFFFFu);
+        const bool hbit = has[q] && (bits >> 31) == 0u && (bits & 0x7FFFFFFFu) != 0u;        // llr > 0
+        int w = a >= 32.0f ? 255 : (int)(a * 8.0f);
+        w = has[q] ? w : 0;
+        H[q] = __ballot(hbit);
+#pragma unroll
+        for (int b = 0; b < 8; ++b) P[b][q] = __ballot((w >> b) & 1);
+    }
+
+    // ---- every live entry: lanes are entries, a round is 64 of them ----------------------------------------------------
+    const uint32_t *cwf = cw_all + (size_t)frame * (kExpectEntries * 6);
+    uint32_t best = kKeyNone;
+#pragma unroll
+    for (int r = 0; r < kExpectRounds; ++r) {
+        if (lm[r] == 0ull) continue;                                  // wave-uniform
+        if ((lm[r] >> lane) & 1ull) {
+            const uint32_t *p = cwf + 64 * r + lane;
+            uint64_t x[3];
+#pragma unroll
+            for (int j = 0; j < 3; ++j)
+                x[j] = ((uint64_t)p[(2 * j) * kExpectEntries] | ((uint64_t)p[(2 * j + 1) * kExpectEntries] << 32)) ^ H[j];
+            best = min(best, (metric_of(x, P) << kIdxBits) | (uint32_t)(64 * r + lane));
+        }
+    }
+    best = wave_min(best);
+    const int index = (int)(best & (uint32_t)(kExpectEntries - 1));
+    const uint32_t metric = best >> kIdxBits;
+
+    // ---- the best entry's codeword again (one address for the wave), then the checks ----------------------------------
+    uint64_t B[3];
+#pragma unroll
+    for (int j = 0; j < 3; ++j)
+        B[j] = (uint64_t)cwf[(2 * j) * kExpectEntries + index] | ((uint64_t)cwf[(2 * j + 1) * kExpectEntries + index] << 32);
+    const int nhard = __popcll(B[0] ^ H[0]) + __popcll(B[1] ^ H[1]) + __popcll(B[2] ^ H[2]);
+
+    uint32_t *rec32 = s + kOffRec;
+    char *rec = reinterpret_cast<char *>(rec32);
+    const uint64_t w0 = __brevll(B[0]);                               // codeword bits 0..63, MSB first
+    const uint64_t w1 = __brevll(B[1]) & 0xFFFFFFE000000000ull;       // bits 64..90
+    int result;
+    if ((B[0] | B[1] | B[2]) == 0ull) result = 5;                     // the code is systematic: an all-zero payload
+    else if (nhard > max_hard_errors) result = 2;
+    else {
+        // the record of a BP success (decode.hip), iters as it was; the CRC is the encoder's own
+        static_assert(offsetof(ft8gpu_decode_status, a91) == 10 && offsetof(ft8gpu_decode_status, text) == 22, "record layout");
+        const uint32_t crc = (uint32_t)(w1 >> 37) & 0x3FFFu;
+        if (lane < 12) {
+            const uint32_t hi0 = (uint32_t)(w0 >> 32), lo0 = (uint32_t)w0, hi1 = (uint32_t)(w1 >> 32);
+            uint32_t v = 0;
+            if (lane == 0) v = dw0 & 0xFFFF0000u;
+            else if (lane == 1) v = crc | (crc << 16);
+            else if (lane == 2) v = (__builtin_bswap32(hi0) & 0xFFFFu) << 16;
+            else if (lane == 3) v = (__builtin_bswap32(hi0) >> 16) | (__builtin_bswap32(lo0) << 16);
+            else if (lane == 4) v = (__builtin_bswap32(lo0) >> 16) | (__builtin_bswap32(hi1) << 16);
+            else if (lane == 5) v = __builtin_bswap32(hi1) >> 16;
+            rec32[lane] = v;
+        }
+        wave_lds_sync();
+        int rc = 0;
+        if (lane == 0) {
+            rc = ft8dev::unpack77(w0, w1 & 0xFFF8000000000000ull, rec + offsetof(ft8gpu_decode_status, text));
+            rec[offsetof(ft8gpu_decode_status, unpack_status)] = (char)rc;
+            rec[offsetof(ft8gpu_decode_status, ok)] = 1;
+        }
+        rc = __builtin_amdgcn_readfirstlane(rc);
+        wave_lds_sync();
+        result = rc < 0 ? 4 : 1;
+    }
+    if (lane < 12 && (result == 1 || out32 != in32)) out32[lane] = result == 1 ? rec32[lane] : mine;
+    if (lane == 0) {
+        info32[0] = (uint32_t)result | ((uint32_t)nhard << 8) | ((uint32_t)index << 16);
+        info32[1] = metric;
+    }
+}
+
+// ---- the update rule ---------------------------------------------------------------------------------------------------
+
+constexpr uint32_t kZ77 = 0x0000F8FFu;                 // payload bytes 8, 9 in an entry's third dword, bits 77..79 cleared
+
+// insert(P, kind) on the table in LDS; wave-uniform arguments, every lane takes part
+__device__ __forceinline__ void table_insert(uint4 *tab, uint32_t &cursor, uint32_t slot, uint32_t x, uint32_t y, uint32_t z77,
+                                             uint32_t kind, int lane) {
+    int found = -1;
+#pragma unroll
+    for (int r = 0; r < kExpectRounds; ++r) {
+        const uint4 e = tab[64 * r + lane];
+        const uint64_t hit = __ballot(((e.z >> 16) & 0xFFu) != 0u && e.x == x && e.y == y && (e.z & kZ77) == z77);
+        if (found < 0 && hit != 0ull) found = 64 * r + __builtin_ctzll(hit);
+    }
+    if (found >= 0) {
+        if (lane == 0) {
+            uint4 e = tab[found];
+            e.z = (e.z & 0x00FFFFFFu) | ((e.z >> 24) & kind) << 24;   // a message once heard stays kind 0
+            e.w = slot;
+            tab[found] = e;
+        }
+    } else {
+        const uint32_t at = cursor % (uint32_t)kExpectEntries;
+        if (lane == 0) tab[at] = make_uint4(x, y, z77 | (1u << 16) | (kind << 24), slot);
+        cursor = at + 1u;
+    }
+    wave_lds_sync();
+}
+
+__global__ __launch_bounds__(64)
+void ft8_expect_update_kernel(const ft8gpu_message *__restrict__ msgs, const int32_t *__restrict__ n_msgs, int ns,
+                              ft8gpu_expect_state *state, int derive) {
+    __shared__ uint4 tab[kExpectEntries];
+    const int lane = threadIdx.x;
+    ft8gpu_expect_state *st = state + blockIdx.x;
+    uint4 *entries = reinterpret_cast<uint4 *>(st->entry);
+    for (int i = lane; i < kExpectEntries; i += 64) tab[i] = entries[i];
+    uint32_t cursor = st->cursor, slot = st->slot;
+    wave_lds_sync();
+
+    for (int sl = 0; sl < ns; ++sl, ++slot) {
+        const size_t f = (size_t)blockIdx.x * ns + sl;
+        int n = n_msgs[f];
+        n = n < 0 ? 0 : (n > kMaxMessages ? kMaxMessages : n);
+        for (int r = 0; r < n; ++r) {
+            const uint4 a = reinterpret_cast<const uint4 *>(msgs + f * kMaxMessages + r)[3];      // a91[12], pad[4]: one address
+            const uint32_t x = a.x, y = a.y, z77 = a.z & kZ77;
+            table_insert(tab, cursor, slot, x, y, z77, 0u, lane);
+            if (!derive) continue;
+            uint64_t w0, w1;
+            payload_words(x, y, z77, w0, w1);
+            const uint32_t n29a = (uint32_t)(w0 >> 35), n29b = (uint32_t)(w0 >> 6) & 0x1FFFFFFFu;
+            const int i3 = (int)(w1 >> 51) & 7;
+            if (i3 != 1 || (n29a >> 1) < ft8dev::NTOKENS + ft8dev::MAX22 || (n29b >> 1) < ft8dev::NTOKENS + ft8dev::MAX22) continue;
+            for (uint32_t g = 32402u; g <= 32404u; ++g) {             // RRR, RR73, 73 with the calls swapped, ir = 0, i3 = 1
+                const uint64_t d0 = (uint64_t)n29b << 35 | (uint64_t)n29a << 6 | (g >> 10);
+                const uint32_t d1 = ((g & 0x3FFu) << 6) | (1u << 3);  // bits 64..79
+                table_insert(tab, cursor, slot, __builtin_bswap32((uint32_t)(d0 >> 32)), __builtin_bswap32((uint32_t)d0),
+                             __builtin_bswap32(d1 << 16), 1u, lane);
+            }
+        }
+    }
+    for (int i = lane; i < kExpectEntries; i += 64) entries[i] = tab[i];
+    if (lane == 0) { st->cursor = cursor; st->slot = slot; }
+}
+
+__global__ __launch_bounds__(256)
+void ft8_match_tag_kernel(const int32_t *__restrict__ n_before, int stride, const int32_t *__restrict__ n_msgs, int nframes,
+                          ft8gpu_message *__restrict__ msgs) {
+    const int frame = blockIdx.x * 4 + (threadIdx.x >> 6), r = threadIdx.x & 63;
+    if (frame >= nframes) return;
+    int lo = n_before[(size_t)frame * stride], hi = n_msgs[frame];
+    lo = lo < 0 ? 0 : lo;
+    hi = hi > kMaxMessages ? kMaxMessages : hi;
+    if (r < lo || r >= hi) return;
+    msgs[(size_t)frame * kMaxMessages + r].pad[2] = 1;
+}
+
+}  // namespace
+
+hipError_t launch_expect_encode(const ft8gpu_expect_state *states, int nframes, uint32_t max_age, const MsgTables *tab,
+                                void *work, hipStream_t s) {
+    if (nframes < 1) return hipSuccess;
+    uint32_t *cw = (uint32_t *)work;
+    uint64_t *live = (uint64_t *)((char *)work + (size_t)nframes * kExpectCwBytes);
+    for (int f0 = 0; f0 < nframes; f0 += 65535) {                     // gridDim.y
+        const int n = nframes - f0 < 65535 ? nframes - f0 : 65535;
+        hipLaunchKernelGGL(ft8_expect_encode_kernel, dim3(kExpectEntries / 256, (unsigned)n), dim3(256), 0, s, states + f0, max_age, tab,
+                           cw + (size_t)f0 * (kExpectEntries * 6), live + (size_t)f0 * kExpectRounds);
+    }
+    return hipGetLastError();
+}
+
+hipError_t launch_match(const uint8_t *mag, const ft8gpu_candidate *cands, const int32_t *counts,
+                        const ft8gpu_decode_status *status_in, ft8gpu_decode_status *status_out, ft8gpu_match_info *info,
+                        int nframes, int max_candidates, const void *work, int max_hard_errors, hipStream_t s) {
+    if (nframes < 1) return hipSuccess;
+    const unsigned bpf = (unsigned)(max_candidates + 3) / 4;
+    const unsigned long long nblocks = (unsigned long long)nframes * bpf;
+    if (nblocks >= (1ull << 31)) return hipErrorInvalidValue;
+    const uint32_t *cw = (const uint32_t *)work;
+    const uint64_t *live = (const uint64_t *)((const char *)work + (size_t)nframes * kExpectCwBytes);
+    hipLaunchKernelGGL(ft8_match_kernel, dim3((unsigned)nblocks), dim3(256), 0, s, mag, cands, counts, status_in, status_out, info,
+                       nframes, max_candidates, cw, live, max_hard_errors, bpf);
+    return hipGetLastError();
+}
+
+hipError_t launch_expect_update(const ft8gpu_message *msgs, const int32_t *n_msgs, int nrecv, int ns,
+                                ft8gpu_expect_state *state, int derive, hipStream_t s) {
+    if (nrecv < 1 || ns < 1) return hipSuccess;
+    hipLaunchKernelGGL(ft8_expect_update_kernel, dim3((unsigned)nrecv), dim3(64), 0, s, msgs, n_msgs, ns, state, derive);
+    return hipGetLastError();
+}
+
+hipError_t launch_match_tag(const int32_t *n_before, int stride, const int32_t *n_msgs, int nframes, ft8gpu_message *msgs,
+                            hipStream_t s) {
+    if (nframes < 1) return hipSuccess;
+    hipLaunchKernelGGL(ft8_match_tag_kernel, dim3((nframes + 3) / 4), dim3(256), 0, s, n_before, stride, n_msgs, nframes, msgs);
+    return hipGetLastError();
+}
