@@ -705,6 +705,148 @@ int  ft8gpu_expect_insert(ft8gpu_expect_state *state, const uint8_t payload[10],
 /* the same with the payload ft8gpu_pack77 gives for text, as kind 0; -1 if the packer refuses the text */
 int  ft8gpu_expect_insert_text(ft8gpu_expect_state *state, const char *text);
 
+/* ---- soft-bit memory: the soft bits of undecoded candidates summed over a receiver's slots ---------------------------------
+ * (DESIGN.md "Soft-bit memory"; not in the reference, where every 15 s slot starts from nothing.)  A station that repeats its
+ * message at the same audio frequency and clock offset, every time just below BP's threshold, is never decoded at all: the
+ * call hash table, the expected messages and AP need a decode or a guess.  A receiver therefore keeps the normalised soft bits
+ * of the candidates BP failed on, and a failing candidate of a later slot at the same position is decoded once more from the
+ * renormalised sum.  Nothing about the message is assumed.  The rule is exact: float32 operations in a stated order.
+ *
+ * State.  One ft8gpu_softmem_state per receiver, caller-owned, host or device memory like the arrays of the call.  entry[i]:
+ * cand = the candidate the entry was last stored from, used != 0 = live, count = the number of slots summed into llr
+ * (saturating at 255), stamp = the value of `slot` when written, llr[0..173] = the running sum of the per-slot normalised soft
+ * bits ([174], [175] zero).  cursor (read modulo 128) is where the next entry goes, slot the number of slots consumed, pad is
+ * zero.  An entry is expired when max_age != 0 and (uint32_t)(slot - stamp) > max_age; max_age = 0 never expires.
+ *
+ * Combining (ft8gpu_combine_candidates; the states are read only).
+ *   A candidate qualifies as for OSD, AP and matching: ok == 0 and ldpc_errors != 0.  One that does not gets status_out =
+ *   status_in and an all-zero info record.
+ *   own[0..173] = the soft bits the LDPC kernel starts from (ft8_extract_likelihood, ftx_normalize_logl).  A non-finite
+ *   own[i]: result 6, the rest of the info record zero.
+ *   Positions: T = 2 * time_offset + time_sub, F = 2 * freq_offset + freq_sub of the candidate; Te, Fe of an entry's cand.
+ *   Live entries: used != 0 and not expired at state.slot.  A live entry is a partner when |T - Te| <= 1 and |F - Fe| <= 1.
+ *   No partner: result 0, the info record all zero.
+ *   nagree = the number of i < 174 with (own[i] > 0) == (entry.llr[i] > 0)  (a NaN is not > 0).  The best partner has the
+ *   largest nagree; ties go to the smaller |T - Te| + |F - Fe|, then to the smaller index.  info.index, info.nagree and
+ *   info.count (the entry's count) are the best partner's, accepted or not.  Only the best partner is tried.
+ *   nagree < min_agree: result 8, BP does not run.
+ *   s[i] = entry.llr[i] + own[i] (one float32 addition), x = ftx_normalize_logl(s): sum and sum of squares accumulated in
+ *   index order in float32 (sum += s[i]; sum2 += s[i] * s[i], each operation rounded), variance = (sum2 - sum * sum * (1.0f /
+ *   174)) * (1.0f / 174), x[i] = s[i] * sqrtf(24.0f / variance).  A non-finite x[i] (a sum of zero variance, a NaN or an
+ *   infinity in the entry): result 6.
+ *   bp_decode(x, ldpc_iters) runs, bit-exact to the LDPC kernel's iteration.  The first failing check names the result:
+ *   7 no codeword within ldpc_iters, 5 all-zero, 3 CRC, 4 unpack77 < 0, else 1 = accepted.  (2 is not used: there is no
+ *   hard-error gate.  bp_decode leaves at an all-zero word before it counts its parity errors, so 5 is kept for the
+ *   numbering and cannot be reached.)  info.nhard = the number of positions where the codeword differs from x > 0, and 0
+ *   without a codeword; diagnostic only.
+ *   On acceptance the status record becomes that of a BP success, exactly as OSD, AP and matching write it (ok = 1,
+ *   ldpc_errors = 0, both CRC fields, unpack_status, a91, text; iters as it was); otherwise it is unchanged.
+ *
+ * Update (ft8gpu_softmem_update; one slot: frame f belongs to states[f], read at entry and written at exit, pairwise
+ * distinct).  In candidate order, the first store_per_slot candidates below counts[f] whose FINAL status record still has
+ * ok == 0 and ldpc_errors != 0 and whose own is finite are stored.  A candidate on which BP ran (info.result 3, 4, 5 or 7)
+ * stores llr[i] = entry[info.index].llr[i] + own[i] -- the s of combining -- with count = min(255, info.count + 1); every
+ * other stored candidate stores own with count = 1.  The k-th stored candidate goes to entry[cursor % 128] with cand = the
+ * candidate, used = 1, pad = 0, stamp = slot, llr[174] = llr[175] = 0, then cursor = cursor % 128 + 1.  Every sum is formed
+ * from the state as it was at entry, also when the ring overwrites the partner in the same slot.  Afterwards slot
+ * increments, also for a frame that stores nothing. */
+#define FT8GPU_SOFTMEM_ENTRIES 128
+typedef struct {
+    ft8gpu_candidate cand;   /*  0  the candidate the entry was stored from (its last slot) */
+    uint8_t  used;           /*  8 */
+    uint8_t  count;          /*  9  slots summed into llr, saturating at 255 */
+    uint16_t pad;            /* 10  zero */
+    uint32_t stamp;          /* 12  value of `slot` when written */
+    float    llr[176];       /* 16  running sum of the per-slot normalised soft bits; [174], [175] zero */
+} ft8gpu_softmem_entry;
+typedef struct {
+    ft8gpu_softmem_entry entry[FT8GPU_SOFTMEM_ENTRIES];   /*     0 */
+    uint32_t cursor;                                      /* 92160 */
+    uint32_t slot;                                        /* 92164 */
+    uint32_t pad[2];                                      /* 92168  zero */
+} ft8gpu_softmem_state;
+typedef struct {
+    uint8_t result;          /* 0 not attempted or no partner, 1 accepted, 3, 4, 5, 7 the failing check, 6 non-finite soft bits, 8 nagree < min_agree */
+    uint8_t nagree;          /* the best partner's values, accepted or not */
+    uint8_t index;
+    uint8_t count;
+    uint8_t nhard;           /* codeword against x > 0; 0 without a codeword */
+    uint8_t pad[3];          /* zero */
+} ft8gpu_combine_info;
+typedef struct {
+    int32_t  min_agree;          /* 0 .. 174; FT8GPU_COMBINE_MIN_AGREE is the recommended value */
+    uint32_t max_age;            /* slots; 0 = entries never expire */
+    int32_t  store_per_slot;     /* 0 .. 128; FT8GPU_COMBINE_STORE_PER_SLOT is the recommended value.  Above 64 a partner two slots
+                                  * back is overwritten before it is needed: the measured gain halves (see that constant) */
+} ft8gpu_combine_params;
+#ifndef __cplusplus
+_Static_assert(sizeof(ft8gpu_softmem_entry) == 720 && offsetof(ft8gpu_softmem_entry, used) == 8 && offsetof(ft8gpu_softmem_entry, count) == 9 &&
+               offsetof(ft8gpu_softmem_entry, pad) == 10 && offsetof(ft8gpu_softmem_entry, stamp) == 12 &&
+               offsetof(ft8gpu_softmem_entry, llr) == 16, "ft8gpu_softmem_entry layout");
+_Static_assert(sizeof(ft8gpu_softmem_state) == 92176 && offsetof(ft8gpu_softmem_state, cursor) == 92160 &&
+               offsetof(ft8gpu_softmem_state, slot) == 92164 && offsetof(ft8gpu_softmem_state, pad) == 92168, "ft8gpu_softmem_state layout");
+_Static_assert(sizeof(ft8gpu_combine_info) == 8 && offsetof(ft8gpu_combine_info, nagree) == 1 && offsetof(ft8gpu_combine_info, index) == 2 &&
+               offsetof(ft8gpu_combine_info, count) == 3 && offsetof(ft8gpu_combine_info, nhard) == 4, "ft8gpu_combine_info layout");
+_Static_assert(sizeof(ft8gpu_combine_params) == 12 && offsetof(ft8gpu_combine_params, max_age) == 4 &&
+               offsetof(ft8gpu_combine_params, store_per_slot) == 8, "ft8gpu_combine_params layout");
+#else
+static_assert(sizeof(ft8gpu_softmem_entry) == 720 && offsetof(ft8gpu_softmem_entry, used) == 8 && offsetof(ft8gpu_softmem_entry, count) == 9 &&
+              offsetof(ft8gpu_softmem_entry, pad) == 10 && offsetof(ft8gpu_softmem_entry, stamp) == 12 &&
+              offsetof(ft8gpu_softmem_entry, llr) == 16, "ft8gpu_softmem_entry layout");
+static_assert(sizeof(ft8gpu_softmem_state) == 92176 && offsetof(ft8gpu_softmem_state, cursor) == 92160 &&
+              offsetof(ft8gpu_softmem_state, slot) == 92164 && offsetof(ft8gpu_softmem_state, pad) == 92168, "ft8gpu_softmem_state layout");
+static_assert(sizeof(ft8gpu_combine_info) == 8 && offsetof(ft8gpu_combine_info, nagree) == 1 && offsetof(ft8gpu_combine_info, index) == 2 &&
+              offsetof(ft8gpu_combine_info, count) == 3 && offsetof(ft8gpu_combine_info, nhard) == 4, "ft8gpu_combine_info layout");
+static_assert(sizeof(ft8gpu_combine_params) == 12 && offsetof(ft8gpu_combine_params, max_age) == 4 &&
+              offsetof(ft8gpu_combine_params, store_per_slot) == 8, "ft8gpu_combine_params layout");
+#endif
+/* Recommended values, from profiles/combine_gain.json (tools/combine_gain.py: 96 receivers x 4 slots of 20 and of 30 CQ stations
+ * per slot at -24 .. 0 dB, every station repeating two slots later at its own frequency and clock offset, and 96 receivers x 4
+ * slots of noise; a sweep over min_agree 88 .. 130 in steps of 6 and store_per_slot 16 .. 128; BP alone decodes 4025 / 5022 of
+ * the 7680 / 11520 planted messages).
+ * min_agree: no point of the sweep accepts a message that was not on the air, on any row, so the recommended gate is the
+ * smallest swept one, 88 -- one above the 87 of 174 positions two unrelated words agree in on average.  What keeps a wrong word
+ * out is BP itself with the CRC and unpack77 behind it; the gate only spares BP runs (21.0 / 26.6 per frame at 88 and
+ * store_per_slot 48, 19.5 / 24.7 at 118), and from 118 on it costs messages: 99 / 129 gained at 88 .. 106, 94 / 125 at 118,
+ * 86 / 116 at 124, 59 / 97 at 130.  On noise hardly a candidate finds a partner (0.05 BP runs per frame at 88).
+ * store_per_slot: the gain is not monotone.  At 88 the two CQ rows together gain 157, 198, 218, 228, 230 at 16, 24, 32, 48,
+ * 64 and 116, 117 at 96, 128: the partner of a repeating station lies two slots back, and a ring of 128 entries that takes more
+ * than 64 candidates per slot has overwritten it by then (candidates come in descending sync score, so the first ones stored
+ * are the likeliest signals).  The smallest swept value within 2 % of the gain at 128 is therefore 16, which gives away a third
+ * of what 64 gains; the constant is the smallest value within 2 % of the largest gain, 48 (228 of 230). */
+#define FT8GPU_COMBINE_MIN_AGREE 88
+#define FT8GPU_COMBINE_STORE_PER_SLOT 48
+/* stage entry: mag [nframes][94208], cands / status_in / status_out / info [nframes][max_candidates], counts [nframes],
+ * states [nframes] (the state of the receiver each frame belongs to; 16-byte aligned in the device form); host or device
+ * pointers by `flags`.  min_agree in [0, 174]; ldpc_iters is the context's.  Records below counts[f] are written, records
+ * at and behind it are not touched.  status_out may be status_in. */
+int ft8gpu_combine_candidates(ft8gpu_ctx *ctx, const uint8_t *mag, const ft8gpu_candidate *cands, const int32_t *counts,
+                              const ft8gpu_decode_status *status_in, int nframes, const ft8gpu_softmem_state *states,
+                              uint32_t max_age, int min_agree, ft8gpu_decode_status *status_out, ft8gpu_combine_info *info,
+                              int flags);
+/* stage entry of the update rule, one slot of nframes receivers: status = the final status records, info = the records
+ * ft8gpu_combine_candidates wrote for the same frames and the same entry states (info.result, index and count are read;
+ * an index is taken modulo 128), states [nframes] in-out (16-byte aligned in the device form).  store_per_slot in [0, 128]. */
+int ft8gpu_softmem_update(ft8gpu_ctx *ctx, const uint8_t *mag, const ft8gpu_candidate *cands, const int32_t *counts,
+                          const ft8gpu_decode_status *status, const ft8gpu_combine_info *info, int nframes,
+                          ft8gpu_softmem_state *states, int store_per_slot, int flags);
+/* The whole path over iq [nstreams][nslots][2][48000], for the frame of receiver r at slot t:
+ *   1. the records [0, n1) are byte for byte those of ft8gpu_decode_messages;
+ *   2. ft8gpu_combine_candidates runs in place on that frame's BP status records, against the receiver's state as the slots
+ *      0 .. t - 1 left it;
+ *   3. the append step of the multi-pass path adds, in candidate order, every unique gained message not yet among the
+ *      frame's records, up to 50 in all; pad[2] of such a record is 2;
+ *   4. ft8gpu_softmem_update runs on the frame's final status records.
+ * n_by_stage [nstreams][nslots][2] (NULL: not written): the count after BP and after combining.  nslots slots in one call
+ * leave the bytes that nslots calls of one slot leave, in msgs, n_msgs and the state.  Host or device pointers by `flags`
+ * (device form: iq, msgs and state 16-byte aligned); the host form stages whole receivers, or runs of slots of one receiver,
+ * at most max_frames frames at a time.  Not composed with AP, OSD, multi-pass or matching. */
+int ft8gpu_decode_messages_combined(ft8gpu_ctx *ctx, const float *iq, int nstreams, int nslots, ft8gpu_softmem_state *state,
+                                    const ft8gpu_combine_params *params, ft8gpu_message *msgs, int32_t *n_msgs,
+                                    int32_t *n_by_stage, int flags);
+/* all zero, as a receiver starts (plain C, no GPU) */
+void ft8gpu_softmem_reset(ft8gpu_softmem_state *state);
+
 /* ---- tooling: encoder + synthetic frames (pack77 / ft8_encode / CPFSK synth of
  *      decoderSelfTest, rtlsdr_ft8d.c:924-955) --------------------------------------------- */
 /* Message text -> 77 bits in 10 bytes (pack77, :927); 0 = ok, -1 = the text fits no message type.  Tokens are separated

@@ -63,6 +63,17 @@ EXPECT_STATE_DTYPE = np.dtype([("entry", EXPECT_ENTRY_DTYPE, (EXPECT_ENTRIES,)),
 MATCH_INFO_DTYPE = np.dtype([("result", "u1"), ("nhard", "u1"), ("index", "<u2"), ("metric", "<i4")])
 MATCH_MAX_HARD_ERRORS = 49  # FT8GPU_MATCH_MAX_HARD_ERRORS, the recommended gate
 assert EXPECT_ENTRY_DTYPE.itemsize == 16 and EXPECT_STATE_DTYPE.itemsize == 8208 and MATCH_INFO_DTYPE.itemsize == 8
+# ft8gpu_softmem_entry / ft8gpu_softmem_state / ft8gpu_combine_info: the soft-bit memory of a receiver (ft8gpu_combine_candidates)
+SOFTMEM_ENTRIES = 128       # FT8GPU_SOFTMEM_ENTRIES
+SOFTMEM_ENTRY_DTYPE = np.dtype([("cand", CAND_DTYPE), ("used", "u1"), ("count", "u1"), ("pad", "<u2"), ("stamp", "<u4"),
+                                ("llr", "<f4", (176,))])
+SOFTMEM_STATE_DTYPE = np.dtype([("entry", SOFTMEM_ENTRY_DTYPE, (SOFTMEM_ENTRIES,)), ("cursor", "<u4"), ("slot", "<u4"),
+                                ("pad", "<u4", (2,))])
+COMBINE_INFO_DTYPE = np.dtype([("result", "u1"), ("nagree", "u1"), ("index", "u1"), ("count", "u1"), ("nhard", "u1"),
+                               ("pad", "u1", (3,))])
+COMBINE_MIN_AGREE = 88           # FT8GPU_COMBINE_MIN_AGREE, the recommended gate
+COMBINE_STORE_PER_SLOT = 48      # FT8GPU_COMBINE_STORE_PER_SLOT, the recommended number of candidates stored per slot
+assert SOFTMEM_ENTRY_DTYPE.itemsize == 720 and SOFTMEM_STATE_DTYPE.itemsize == 92176 and COMBINE_INFO_DTYPE.itemsize == 8
 
 
 class Params(C.Structure):
@@ -89,6 +100,11 @@ class ApParams(C.Structure):
 class ExpectParams(C.Structure):
     """ft8gpu_expect_params: max_hard_errors 0..174, max_age in slots (0: never expires), derive != 0: RRR / RR73 / 73"""
     _fields_ = [("max_hard_errors", C.c_int32), ("max_age", C.c_uint32), ("derive", C.c_int32)]
+
+
+class CombineParams(C.Structure):
+    """ft8gpu_combine_params: min_agree 0..174, max_age in slots (0: never expires), store_per_slot 0..128"""
+    _fields_ = [("min_agree", C.c_int32), ("max_age", C.c_uint32), ("store_per_slot", C.c_int32)]
 
 
 class Timings(C.Structure):
@@ -134,6 +150,7 @@ ABI_SYMBOLS = [
     "ft8gpu_callhash_insert", "ft8gpu_callhash_lookup", "ft8gpu_format_resolved",
     "ft8gpu_match_candidates", "ft8gpu_expect_update", "ft8gpu_decode_messages_expected", "ft8gpu_expect_reset",
     "ft8gpu_expect_insert", "ft8gpu_expect_insert_text",
+    "ft8gpu_combine_candidates", "ft8gpu_softmem_update", "ft8gpu_decode_messages_combined", "ft8gpu_softmem_reset",
     "ft8_find_sync", "ft8_decode", "ft8_encode", "pack77",            # ft8_lib level (include/ft8_lib/ft8/*.h)
     "initFFTW", "freeFFTW", "ft8_subsystem", "ft8gpu_read_raw_iq", "ft8gpu_read_c2", "ft8gpu_write_raw_iq",
 ]
@@ -289,6 +306,12 @@ def _declare(L):
         L.ft8gpu_expect_reset.restype = None
         L.ft8gpu_expect_insert.argtypes = [vp, vp, C.c_int]
         L.ft8gpu_expect_insert_text.argtypes = [vp, C.c_char_p]
+    if hasattr(L, "ft8gpu_combine_candidates"):           # absent from older builds loaded by load_library_at
+        L.ft8gpu_combine_candidates.argtypes = [vp, vp, vp, vp, vp, C.c_int, vp, C.c_uint32, C.c_int, vp, vp, C.c_int]
+        L.ft8gpu_softmem_update.argtypes = [vp, vp, vp, vp, vp, vp, C.c_int, vp, C.c_int, C.c_int]
+        L.ft8gpu_decode_messages_combined.argtypes = [vp, vp, C.c_int, C.c_int, vp, C.POINTER(CombineParams), vp, vp, vp, C.c_int]
+        L.ft8gpu_softmem_reset.argtypes = [vp]
+        L.ft8gpu_softmem_reset.restype = None
     L.ft8gpu_rx_decimate.argtypes = [vp, vp, C.c_int, C.c_size_t, vp, C.c_int, C.c_int]
     if hasattr(L, "ft8gpu_rx_stream"):                    # absent from older builds loaded by load_library_at
         L.ft8gpu_rx_stream.argtypes = [vp, vp, C.c_int, C.c_int, C.c_size_t, vp, vp, vp, C.c_int, C.c_int]
@@ -404,6 +427,17 @@ def callhash_lookup(state, bits, hash_value, max_age=0):
 def expect_state(n=1):
     """n reset tables of expected messages (EXPECT_STATE_DTYPE [n], all zero: what ft8gpu_expect_reset leaves)"""
     return np.zeros(n, EXPECT_STATE_DTYPE)
+
+
+def softmem_state(n=1):
+    """n reset soft-bit memories (SOFTMEM_STATE_DTYPE [n], all zero: what ft8gpu_softmem_reset leaves)"""
+    return np.zeros(n, SOFTMEM_STATE_DTYPE)
+
+
+def softmem_reset(state):
+    """ft8gpu_softmem_reset on one state (a SOFTMEM_STATE_DTYPE array of one element, in place)"""
+    assert isinstance(state, np.ndarray) and state.dtype == SOFTMEM_STATE_DTYPE and state.size == 1 and state.flags["C_CONTIGUOUS"]
+    load_library().ft8gpu_softmem_reset(state.ctypes.data)
 
 
 def _one_expect_state(state):
@@ -910,6 +944,85 @@ class Decoder:
         """the same with every array in HBM (iq, msgs and state 16-byte aligned); n_by_stage_dev: [nstreams][nslots][2] or None"""
         p = ExpectParams(int(max_hard_errors), int(max_age), int(bool(derive)))
         self._ck(self.lib.ft8gpu_decode_messages_expected(self.h, _ptr(iq_dev), nstreams, nslots, _ptr(state_dev), C.byref(p),
+                                                          _ptr(msgs_dev), _ptr(n_msgs_dev),
+                                                          None if n_by_stage_dev is None else _ptr(n_by_stage_dev), DEVICE_PTRS))
+
+    def combine_candidates(self, mag, cands, counts, status_in, states, max_age=0, min_agree=COMBINE_MIN_AGREE,
+                           status_out=None, info=None):
+        """ft8gpu_combine_candidates.  states: SOFTMEM_STATE_DTYPE [B], the memory of the receiver each frame belongs to (read
+        only) -> (status_out [B][cap] STATUS_DTYPE, info [B][cap] COMBINE_INFO_DTYPE), new arrays; records at and behind
+        counts[f] keep what status_out / info held (zeros when None)"""
+        mag = np.ascontiguousarray(mag, np.uint8).reshape(-1, MAG_ARRAY)
+        B = mag.shape[0]
+        cands = np.ascontiguousarray(cands)
+        counts = np.ascontiguousarray(counts, np.int32)
+        status_in = np.ascontiguousarray(status_in).view(np.uint8).reshape(B, self.max_candidates, 48)
+        states = np.ascontiguousarray(states)
+        assert cands.shape == (B, self.max_candidates) and cands.dtype == CAND_DTYPE and counts.shape == (B,)
+        assert states.dtype == SOFTMEM_STATE_DTYPE and states.shape == (B,)
+        out = np.zeros((B, self.max_candidates, 48), np.uint8) if status_out is None else \
+            np.array(status_out, copy=True, order="C").view(np.uint8).reshape(B, self.max_candidates, 48)
+        inf = np.zeros((B, self.max_candidates), COMBINE_INFO_DTYPE) if info is None else \
+            np.array(info, copy=True, order="C").view(COMBINE_INFO_DTYPE).reshape(B, self.max_candidates)
+        self._ck(self.lib.ft8gpu_combine_candidates(self.h, mag.ctypes.data, cands.ctypes.data, counts.ctypes.data, status_in.ctypes.data,
+                                                    B, states.ctypes.data, int(max_age), int(min_agree), out.ctypes.data,
+                                                    inf.ctypes.data, HOST_PTRS))
+        return out.view(STATUS_DTYPE).reshape(B, self.max_candidates), inf
+
+    def combine_candidates_dev(self, mag_dev, cands_dev, counts_dev, status_in_dev, nframes, states_dev, max_age, min_agree,
+                               status_out_dev, info_dev):
+        """status_out_dev may be status_in_dev; states_dev: [nframes] 92176-byte memories, 16-byte aligned; info_dev: 8-byte records"""
+        self._ck(self.lib.ft8gpu_combine_candidates(self.h, _ptr(mag_dev), _ptr(cands_dev), _ptr(counts_dev), _ptr(status_in_dev), nframes,
+                                                    _ptr(states_dev), int(max_age), int(min_agree), _ptr(status_out_dev),
+                                                    _ptr(info_dev), DEVICE_PTRS))
+
+    def softmem_update(self, mag, cands, counts, status, info, states, store_per_slot=COMBINE_STORE_PER_SLOT):
+        """ft8gpu_softmem_update, one slot.  status: the final status records [B][cap], info: COMBINE_INFO_DTYPE [B][cap] as
+        combine_candidates returned it for the same frames and states; states: SOFTMEM_STATE_DTYPE [B] (the caller's array stays
+        as it is) -> the exit states [B]"""
+        mag = np.ascontiguousarray(mag, np.uint8).reshape(-1, MAG_ARRAY)
+        B = mag.shape[0]
+        cands = np.ascontiguousarray(cands)
+        counts = np.ascontiguousarray(counts, np.int32)
+        status = np.ascontiguousarray(status).view(np.uint8).reshape(B, self.max_candidates, 48)
+        info = np.ascontiguousarray(info).view(COMBINE_INFO_DTYPE).reshape(B, self.max_candidates)
+        states = np.array(states, SOFTMEM_STATE_DTYPE, copy=True, ndmin=1)
+        assert cands.shape == (B, self.max_candidates) and cands.dtype == CAND_DTYPE and counts.shape == (B,) and states.shape == (B,)
+        self._ck(self.lib.ft8gpu_softmem_update(self.h, mag.ctypes.data, cands.ctypes.data, counts.ctypes.data, status.ctypes.data,
+                                                info.ctypes.data, B, states.ctypes.data, int(store_per_slot), HOST_PTRS))
+        return states
+
+    def softmem_update_dev(self, mag_dev, cands_dev, counts_dev, status_dev, info_dev, nframes, states_dev, store_per_slot):
+        """all arrays in HBM; the states (16-byte aligned) are updated in place"""
+        self._ck(self.lib.ft8gpu_softmem_update(self.h, _ptr(mag_dev), _ptr(cands_dev), _ptr(counts_dev), _ptr(status_dev),
+                                                _ptr(info_dev), nframes, _ptr(states_dev), int(store_per_slot), DEVICE_PTRS))
+
+    def decode_messages_combined(self, iq, state=None, min_agree=COMBINE_MIN_AGREE, max_age=0, store_per_slot=COMBINE_STORE_PER_SLOT,
+                                 msgs=None):
+        """ft8gpu_decode_messages_combined.  iq: float32 [nstreams][nslots][2][48000]; state: SOFTMEM_STATE_DTYPE [nstreams] as
+        a previous call returned it, or None for reset memories (the caller's array stays as it is)
+        -> (msgs [nstreams][nslots][50], n_msgs [nstreams][nslots], n_by_stage [nstreams][nslots][2]: the count after BP and
+        after combining, the exit state [nstreams]); pad[2] of a record gained by combining is 2"""
+        iq = np.ascontiguousarray(iq, np.float32)
+        nstreams, nslots = iq.shape[:2]
+        assert iq.shape[2:] == (2, NSAMPLES)
+        state = np.zeros(nstreams, SOFTMEM_STATE_DTYPE) if state is None else np.array(state, SOFTMEM_STATE_DTYPE, copy=True, ndmin=1)
+        assert state.shape == (nstreams,)
+        if msgs is None:
+            msgs = np.zeros((nstreams, nslots, MAX_MESSAGES), MESSAGE_DTYPE)
+        assert msgs.dtype == MESSAGE_DTYPE and msgs.shape == (nstreams, nslots, MAX_MESSAGES) and msgs.flags["C_CONTIGUOUS"]
+        n = np.zeros((nstreams, nslots), np.int32)
+        nbs = np.zeros((nstreams, nslots, 2), np.int32)
+        p = CombineParams(int(min_agree), int(max_age), int(store_per_slot))
+        self._ck(self.lib.ft8gpu_decode_messages_combined(self.h, iq.ctypes.data, nstreams, nslots, state.ctypes.data, C.byref(p),
+                                                          msgs.ctypes.data, n.ctypes.data, nbs.ctypes.data, HOST_PTRS))
+        return msgs, n, nbs, state
+
+    def decode_messages_combined_dev(self, iq_dev, nstreams, nslots, state_dev, min_agree, max_age, store_per_slot, msgs_dev,
+                                     n_msgs_dev, n_by_stage_dev=None):
+        """the same with every array in HBM (iq, msgs and state 16-byte aligned); n_by_stage_dev: [nstreams][nslots][2] or None"""
+        p = CombineParams(int(min_agree), int(max_age), int(store_per_slot))
+        self._ck(self.lib.ft8gpu_decode_messages_combined(self.h, _ptr(iq_dev), nstreams, nslots, _ptr(state_dev), C.byref(p),
                                                           _ptr(msgs_dev), _ptr(n_msgs_dev),
                                                           None if n_by_stage_dev is None else _ptr(n_by_stage_dev), DEVICE_PTRS))
 

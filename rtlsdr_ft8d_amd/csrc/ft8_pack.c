@@ -129,6 +129,11 @@ void ft8gpu_expect_reset(ft8gpu_expect_state *state) {
     if (state) memset(state, 0, sizeof *state);
 }
 
+/* the soft-bit memory of a receiver as it starts (ft8gpu.h "soft-bit memory"; csrc/combine.hip has the kernels) */
+void ft8gpu_softmem_reset(ft8gpu_softmem_state *state) {
+    if (state) memset(state, 0, sizeof *state);
+}
+
 int ft8gpu_expect_insert(ft8gpu_expect_state *state, const uint8_t payload[10], int kind) {
     if (!state || !payload || (kind != 0 && kind != 1)) return -1;
     uint8_t p[10];
