@@ -847,6 +847,90 @@ int ft8gpu_decode_messages_combined(ft8gpu_ctx *ctx, const float *iq, int nstrea
 /* all zero, as a receiver starts (plain C, no GPU) */
 void ft8gpu_softmem_reset(ft8gpu_softmem_state *state);
 
+/* ---- refined time and frequency: every message record located in the I/Q samples (DESIGN.md "Refined time and frequency") ----
+ * freq_hz and dt_s of ft8gpu_message are the centre of the candidate's cell on the sync grid, 3.125 Hz by 256 samples.  The stage
+ * below correlates the frame's samples with the message's own 79 tones on a grid of 32 samples, and at the best offset with
+ * the tones 3.125 and 6.25 Hz to either side and with a tone the message leaves empty.  It writes powers only; the host helper
+ * ft8gpu_refined_estimate turns them into seconds, hertz and decibels.  This text is the rule; tests/ft8_spec_refine.py
+ * restates it in numpy, and the device output equals the restatement byte for byte.
+ *
+ * Inputs: the frame x[j] = (I[j], Q[j]), j < 48000, with x[j] = 0 for every other j; a record's cand and a91.
+ *   T = 2 * time_offset + time_sub,  F = 2 * freq_offset + freq_sub
+ *   tone[m], m < 79: the Costas tones {3,1,4,0,6,5,2} at m = 0..6, 36..42, 72..78; data symbol d = m - 7 (m < 36) or m - 14 is
+ *     the Gray map {0,1,3,2,5,6,4,7} of codeword bits 3d .. 3d+2, MSB first; codeword bit i < 91 is bit i of a91 as stored
+ *     (byte i / 8, MSB first), bit 91 + r the parity of a91 AND generator row r (ft8_encode's rule; for a decoded message
+ *     the stored CRC is the encoder's)
+ *   w[i] = (cos, -sin)(2 pi i / 1024), i < 1024, in float32: the waterfall's twiddle table
+ *   k_m = F + 2 * tone[m]
+ * Arithmetic, float32, one IEEE operation each, nothing fused:
+ *   y(k, j) = x[j] * w[(k * j) mod 1024] = (xr * wr - xi * wi,  xr * wi + xi * wr)       (mod: the non-negative residue)
+ *   g(k, q) = y(k, 32q) + ... + y(k, 32q + 31): both components summed in ascending j from +0
+ *   s_m(e)  = 256 * T + FT8GPU_REFINE_LEAD + 512 * m + 32 * e                            (the first sample of symbol m)
+ *   c(m, k, e) = g(k, q0) + ... + g(k, q0 + 15) in ascending q from +0,  q0 = s_m(e) / 32 (exact)
+ *   P(u, e) = the sum over m = 0 .. 78, ascending from +0, of (re * re + im * im) of c(m, k_m + u, e)
+ * The lead of 256 samples is the waterfall's geometry: row T multiplies the samples 256 T .. 256 T + 1023 by a window that
+ * peaks at 256 T + 512, so it is centred on a symbol that starts at 256 T + 256.  (ft8o_synth_cpfsk and ft8gpu_synth_frames
+ * confirm it: a signal started at sample S is found on the row T nearest (S - 256) / 256, and the refined offset then puts
+ * s_0 on S.  dt_s of ft8gpu_message, 256 T / 3200, is therefore 0.08 s less than the start time t0_s of such a signal.)
+ * Time search:  pt_all[e + 16] = P(0, e), e = -16 .. 16; e_best = the first e in ascending order whose power is strictly
+ * greater than every earlier one (-16 when none is).  The range is +-512 samples because the record's candidate is the first
+ * that carried the message, not the best one.
+ * At e_best:  pf[u + 2] = P(u, e_best), u = -2 .. 2 (pf[2] is pt_all[e_best + 16]);  noise = the same sum with
+ * k = F + 2 * ((tone[m] + 4) & 7) in place of k_m: the tone four away, which this message leaves empty in that symbol. */
+#define FT8GPU_REFINE_LEAD     256     /* samples from the first sample of waterfall row T to the symbol it is centred on */
+#define FT8GPU_REFINE_STEP     32      /* samples per time-search step */
+#define FT8GPU_REFINE_RANGE    16      /* the search covers e = -16 .. 16 */
+typedef struct {
+    int16_t e_best;          /*  0 */
+    uint8_t valid;           /*  2  1 once written */
+    uint8_t pad0;            /*  3  zero */
+    float   pt[3];           /*  4  P(0, e_best - 1), P(0, e_best), P(0, e_best + 1); 0.0f where e lies outside [-16, 16] */
+    float   pf[5];           /* 16 */
+    float   noise;           /* 36 */
+    uint8_t pad[8];          /* 40  zero */
+} ft8gpu_refined;
+#ifndef __cplusplus
+_Static_assert(sizeof(ft8gpu_refined) == 48 && offsetof(ft8gpu_refined, valid) == 2 && offsetof(ft8gpu_refined, pad0) == 3 &&
+               offsetof(ft8gpu_refined, pt) == 4 && offsetof(ft8gpu_refined, pf) == 16 && offsetof(ft8gpu_refined, noise) == 36 &&
+               offsetof(ft8gpu_refined, pad) == 40, "ft8gpu_refined layout");
+#else
+static_assert(sizeof(ft8gpu_refined) == 48 && offsetof(ft8gpu_refined, valid) == 2 && offsetof(ft8gpu_refined, pad0) == 3 &&
+              offsetof(ft8gpu_refined, pt) == 4 && offsetof(ft8gpu_refined, pf) == 16 && offsetof(ft8gpu_refined, noise) == 36 &&
+              offsetof(ft8gpu_refined, pad) == 40, "ft8gpu_refined layout");
+#endif
+/* stage entry: iq [nframes][2][48000], msgs / refined [nframes][50], n_msgs [nframes] (taken as 0 when negative, 50 when
+ * larger); host or device pointers by `flags` (device form: iq 16-byte aligned).  refined[f][i] is written for i < n_msgs[f];
+ * records at and behind the count are not touched.  A record need not be a decode: any cand and a91 give defined output. */
+int ft8gpu_refine_messages(ft8gpu_ctx *ctx, const float *iq, const ft8gpu_message *msgs, const int32_t *n_msgs, int nframes,
+                           ft8gpu_refined *refined, int flags);
+/* ft8gpu_decode_messages, unchanged (msgs and n_msgs are byte for byte what it returns alone), then the stage on its records */
+int ft8gpu_decode_messages_refined(ft8gpu_ctx *ctx, const float *iq, int nframes, ft8gpu_message *msgs, int32_t *n_msgs,
+                                   ft8gpu_refined *refined, int flags);
+/* Host helper (plain C, no GPU): seconds, hertz and decibels from one record pair; 0, or -1 when an argument is NULL or
+ * refined->valid is 0 (nothing is written then).  vertex(a, b, c) = 0.5 (a - c) / (a - 2 b + c) clamped to [-0.5, 0.5], and 0
+ * when a - 2 b + c >= 0 (no maximum, equal values included) or a value is not finite; evaluated in double.
+ *   time:  v = vertex(pt), 0 when e_best - 1 or e_best + 1 lies outside [-16, 16];
+ *          dt_s = (256 T + FT8GPU_REFINE_LEAD + 32 (e_best + v)) / 3200: the start time of the signal within the frame, so a
+ *          signal ft8gpu_synth_frames starts at t0_s reports t0_s
+ *   freq:  u* = the first largest of pf[1 .. 3], v = vertex(pf[u* - 1 .. u* + 1]); freq_hz = 3.125 (F + (u* - 2) + v): the
+ *          frequency of tone 0
+ *   snr:   snr_db = 10 log10(max(pf[2] - noise, FLT_MIN) / noise * 6.25 / 2500) clamped to [-30, 49], the range of
+ *          ft8gpu_message.snr_db; noise <= 0 or not finite: 49 when pf[2] > 0, else -30
+ * Bias, stated rather than hidden: the correlation of a 512-sample symbol against a tone df away is sinc^2(df / 6.25 Hz), and
+ * pf samples it every half lobe width.  A parabola through three such points reads a true offset d (in steps of 3.125 Hz,
+ * |d| <= 0.5) too close to the grid point: exact at d = 0 and +-0.5, short by 0.031 step at |d| = 0.1, by 0.056 at 0.2 and by
+ * at most 0.069 step, 0.22 Hz, at |d| = 0.3.  In time |c|^2 falls off as (1 - |t| / 512 samples)^2 when the neighbouring
+ * symbols carry other tones, a cusp no parabola fits: the vertex is short by 0.046 step at |d| = 0.1 and by at most 0.09
+ * step of 32 samples, 2.9 samples, at |d| = 0.3.  Both are a tenth of the grid's error.  The SNR has a ceiling of its own: a
+ * signal d steps off the grid leaks sinc^2(4 + d / 2) of its power into the empty tone, up to -25 dB, and a window up to 16
+ * samples off the symbol takes in up to (16 / 512)^2, -30 dB, of a neighbouring symbol that uses that tone, so `noise` holds
+ * signal once the signal is some 25 dB above the noise in 6.25 Hz: above about 0 dB the estimate reads low.
+ * profiles/refine_accuracy.json has the measured errors. */
+int ft8gpu_refined_estimate(const ft8gpu_message *msg, const ft8gpu_refined *refined, float *dt_s, float *freq_hz, float *snr_db);
+/* ft8gpu_format_messages with the refined values: "%3d %5.2f %6.1f ~  %s\n" of the rounded snr_db, dt_s, freq_hz and text;
+ * a record whose refined->valid is 0 prints its message's own snr_db, dt_s and freq_hz in the same format */
+int ft8gpu_format_messages_refined(const ft8gpu_message *msgs, const ft8gpu_refined *refined, int32_t n, char *out, size_t cap);
+
 /* ---- tooling: encoder + synthetic frames (pack77 / ft8_encode / CPFSK synth of
  *      decoderSelfTest, rtlsdr_ft8d.c:924-955) --------------------------------------------- */
 /* Message text -> 77 bits in 10 bytes (pack77, :927); 0 = ok, -1 = the text fits no message type.  Tokens are separated

@@ -73,6 +73,10 @@ COMBINE_INFO_DTYPE = np.dtype([("result", "u1"), ("nagree", "u1"), ("index", "u1
                                ("pad", "u1", (3,))])
 COMBINE_MIN_AGREE = 88           # FT8GPU_COMBINE_MIN_AGREE, the recommended gate
 COMBINE_STORE_PER_SLOT = 48      # FT8GPU_COMBINE_STORE_PER_SLOT, the recommended number of candidates stored per slot
+# refined time and frequency (ft8gpu_refine_messages): the powers around a record's position in the I/Q samples
+REFINED_DTYPE = np.dtype([("e_best", "<i2"), ("valid", "u1"), ("pad0", "u1"), ("pt", "<f4", (3,)), ("pf", "<f4", (5,)),
+                          ("noise", "<f4"), ("pad", "u1", (8,))])
+assert REFINED_DTYPE.itemsize == 48
 assert SOFTMEM_ENTRY_DTYPE.itemsize == 720 and SOFTMEM_STATE_DTYPE.itemsize == 92176 and COMBINE_INFO_DTYPE.itemsize == 8
 
 
@@ -151,6 +155,7 @@ ABI_SYMBOLS = [
     "ft8gpu_match_candidates", "ft8gpu_expect_update", "ft8gpu_decode_messages_expected", "ft8gpu_expect_reset",
     "ft8gpu_expect_insert", "ft8gpu_expect_insert_text",
     "ft8gpu_combine_candidates", "ft8gpu_softmem_update", "ft8gpu_decode_messages_combined", "ft8gpu_softmem_reset",
+    "ft8gpu_refine_messages", "ft8gpu_decode_messages_refined", "ft8gpu_refined_estimate", "ft8gpu_format_messages_refined",
     "ft8_find_sync", "ft8_decode", "ft8_encode", "pack77",            # ft8_lib level (include/ft8_lib/ft8/*.h)
     "initFFTW", "freeFFTW", "ft8_subsystem", "ft8gpu_read_raw_iq", "ft8gpu_read_c2", "ft8gpu_write_raw_iq",
 ]
@@ -312,6 +317,11 @@ def _declare(L):
         L.ft8gpu_decode_messages_combined.argtypes = [vp, vp, C.c_int, C.c_int, vp, C.POINTER(CombineParams), vp, vp, vp, C.c_int]
         L.ft8gpu_softmem_reset.argtypes = [vp]
         L.ft8gpu_softmem_reset.restype = None
+    if hasattr(L, "ft8gpu_refine_messages"):              # absent from older builds loaded by load_library_at
+        L.ft8gpu_refine_messages.argtypes = [vp, vp, vp, vp, C.c_int, vp, C.c_int]
+        L.ft8gpu_decode_messages_refined.argtypes = [vp, vp, C.c_int, vp, vp, vp, C.c_int]
+        L.ft8gpu_refined_estimate.argtypes = [vp, vp, C.POINTER(C.c_float), C.POINTER(C.c_float), C.POINTER(C.c_float)]
+        L.ft8gpu_format_messages_refined.argtypes = [vp, vp, C.c_int32, vp, C.c_size_t]
     L.ft8gpu_rx_decimate.argtypes = [vp, vp, C.c_int, C.c_size_t, vp, C.c_int, C.c_int]
     if hasattr(L, "ft8gpu_rx_stream"):                    # absent from older builds loaded by load_library_at
         L.ft8gpu_rx_stream.argtypes = [vp, vp, C.c_int, C.c_int, C.c_size_t, vp, vp, vp, C.c_int, C.c_int]
@@ -1027,6 +1037,45 @@ class Decoder:
                                                           None if n_by_stage_dev is None else _ptr(n_by_stage_dev), DEVICE_PTRS))
 
     # ---- device-pointer API (inputs and outputs resident in HBM) --------------------------------
+    def refine_messages(self, iq, msgs, n_msgs, refined=None):
+        """the refine stage (ft8gpu_refine_messages) -> refined [B][50] REFINED_DTYPE; records at and behind n_msgs[f] keep what
+        `refined` held (zeros when None)"""
+        iq = np.ascontiguousarray(iq, np.float32)
+        msgs = np.ascontiguousarray(msgs)
+        n_msgs = np.ascontiguousarray(n_msgs, np.int32)
+        B = iq.shape[0]
+        assert iq.shape[1:] == (2, NSAMPLES) and msgs.dtype == MESSAGE_DTYPE and msgs.shape == (B, MAX_MESSAGES) and n_msgs.shape == (B,)
+        if refined is None:
+            refined = np.zeros((B, MAX_MESSAGES), REFINED_DTYPE)
+        assert refined.dtype == REFINED_DTYPE and refined.shape == (B, MAX_MESSAGES) and refined.flags["C_CONTIGUOUS"]
+        self._ck(self.lib.ft8gpu_refine_messages(self.h, iq.ctypes.data, msgs.ctypes.data, n_msgs.ctypes.data, B, refined.ctypes.data,
+                                               HOST_PTRS))
+        return refined
+
+    def refine_messages_dev(self, iq_dev, msgs_dev, n_msgs_dev, nframes, refined_dev):
+        self._ck(self.lib.ft8gpu_refine_messages(self.h, _ptr(iq_dev), _ptr(msgs_dev), _ptr(n_msgs_dev), int(nframes), _ptr(refined_dev),
+                                               DEVICE_PTRS))
+
+    def decode_messages_refined(self, iq, msgs=None, refined=None):
+        """ft8gpu_decode_messages and the refine stage on its records -> (msgs [B][50], n_msgs [B], refined [B][50])"""
+        iq = np.ascontiguousarray(iq, np.float32)
+        B = iq.shape[0]
+        assert iq.shape[1:] == (2, NSAMPLES)
+        if msgs is None:
+            msgs = np.zeros((B, MAX_MESSAGES), MESSAGE_DTYPE)
+        if refined is None:
+            refined = np.zeros((B, MAX_MESSAGES), REFINED_DTYPE)
+        assert msgs.dtype == MESSAGE_DTYPE and msgs.shape == (B, MAX_MESSAGES) and msgs.flags["C_CONTIGUOUS"]
+        assert refined.dtype == REFINED_DTYPE and refined.shape == (B, MAX_MESSAGES) and refined.flags["C_CONTIGUOUS"]
+        n = np.zeros(B, np.int32)
+        self._ck(self.lib.ft8gpu_decode_messages_refined(self.h, iq.ctypes.data, B, msgs.ctypes.data, n.ctypes.data, refined.ctypes.data,
+                                                       HOST_PTRS))
+        return msgs, n, refined
+
+    def decode_messages_refined_dev(self, iq_dev, nframes, msgs_dev, n_msgs_dev, refined_dev):
+        self._ck(self.lib.ft8gpu_decode_messages_refined(self.h, _ptr(iq_dev), int(nframes), _ptr(msgs_dev), _ptr(n_msgs_dev),
+                                                       _ptr(refined_dev), DEVICE_PTRS))
+
     def ap_candidates_dev(self, mag_dev, cands_dev, counts_dev, status_in_dev, nframes, hyps, max_hard_errors, status_out_dev, info_dev):
         """status_out_dev may be status_in_dev; info_dev: [nframes][max_candidates] 8-byte records; hyps stay on the host"""
         hyps = _ap_hyps(hyps)
@@ -1280,6 +1329,40 @@ def format_messages(msgs, n):
         raise Ft8GpuError("ft8gpu_format_messages failed")
     buf = C.create_string_buffer(need + 1)
     L.ft8gpu_format_messages(msgs.ctypes.data, n, buf, len(buf))
+    return buf.value.decode()
+
+
+def refined_estimate(msgs, refined):
+    """ft8gpu_refined_estimate for arrays of records of one shape -> (dt_s, freq_hz, snr_db, valid), float32 / bool arrays of that
+    shape; where a record is not valid the three values are NaN"""
+    L = load_library()
+    msgs = np.ascontiguousarray(msgs)
+    refined = np.ascontiguousarray(refined)
+    assert msgs.dtype == MESSAGE_DTYPE and refined.dtype == REFINED_DTYPE and msgs.shape == refined.shape
+    out = np.full((3,) + msgs.shape, np.nan, np.float32)
+    ok = np.zeros(msgs.shape, bool)
+    m, r = msgs.reshape(-1), refined.reshape(-1)
+    o = out.reshape(3, -1)
+    a, b, c = C.c_float(), C.c_float(), C.c_float()
+    for i in range(m.size):
+        if L.ft8gpu_refined_estimate(m[i:].ctypes.data, r[i:].ctypes.data, C.byref(a), C.byref(b), C.byref(c)) == 0:
+            o[:, i] = (a.value, b.value, c.value)
+            ok.reshape(-1)[i] = True
+    return out[0], out[1], out[2], ok
+
+
+def format_messages_refined(msgs, refined, n):
+    """ft8gpu_format_messages_refined: "SNR DT Freq ~ Message" with DT to two decimals and Freq to one"""
+    L = load_library()
+    msgs = np.ascontiguousarray(msgs)
+    refined = np.ascontiguousarray(refined)
+    assert msgs.dtype == MESSAGE_DTYPE and refined.dtype == REFINED_DTYPE
+    n = int(min(n, msgs.size, refined.size))
+    need = L.ft8gpu_format_messages_refined(msgs.ctypes.data, refined.ctypes.data, n, None, 0)
+    if need < 0:
+        raise Ft8GpuError("ft8gpu_format_messages_refined failed")
+    buf = C.create_string_buffer(need + 1)
+    L.ft8gpu_format_messages_refined(msgs.ctypes.data, refined.ctypes.data, n, buf, len(buf))
     return buf.value.decode()
 
 
