@@ -196,7 +196,7 @@ void ft8_sync_kernel(const uint8_t *__restrict__ mag, uint32_t *__restrict__ lis
         const int navg = __builtin_amdgcn_readfirstlane(s_navg[t0i]);
         // trunc(num / navg) >= min_score  <=>  num >= T   (C division truncates toward zero; navg = 0 leaves the sum undivided)
         int T = navg > 0 ? (min_score > 0 ? min_score * navg : (min_score - 1) * navg + 1) : min_score;
-        T = T > 32767 ? 32767 : (T < -32768 ? -32768 : T);       // |num| <= 21420: saturated thresholds mean never / always
+        T = T > 32767 ? 32767 : (T < -32768 ? -32768 : T);       // |num| <= 255 navg <= 19125: saturated thresholds mean never / always
         const s16x2 Tpk = { (short)T, (short)T };
         const u32 *pa0 = reinterpret_cast<const u32 *>(s_map + (kOffA + tl + 0) * kMapPitch) + 2 * lane;   // t' = t0 + 1
         const u32 *pa1 = reinterpret_cast<const u32 *>(s_map + (kOffA + tl + 1) * kMapPitch) + 2 * lane;   // t0 + 2
@@ -224,9 +224,9 @@ void ft8_sync_kernel(const uint8_t *__restrict__ mag, uint32_t *__restrict__ lis
         if (SCORE_MAP || any) {                                   // wave-uniform
             const float rnavg = navg > 0 ? 1.0f / (float)navg : 1.0f;
             // score /= navg (C int division, truncating toward zero) without an integer divide: with
-            // |score| <= 21*4*255 and navg <= 84 the quotient is either an integer or at least 1/84 away from
-            // one, while float(score)*fl(1/navg) is within 2e-3 of it, so adding 0.004 away from zero and
-            // truncating is exact.
+            // |score| <= 255 navg and navg <= 75 (navg is one of 50, 52, 56, 60, 63, 67, 71, 75) the quotient is either an
+            // integer or at least 1/75 away from one, while float(score)*fl(1/navg) is within 2e-3 of it, so adding
+            // 0.004 away from zero and truncating is exact (tests/test_sync_craft_cpu.py: every numerator, every navg).
             auto quotient = [&](int num) {
                 const float fs_ = (float)num;
                 return (int)(fs_ * rnavg + __builtin_copysignf(0.004f, fs_));
