@@ -931,6 +931,85 @@ int ft8gpu_refined_estimate(const ft8gpu_message *msg, const ft8gpu_refined *ref
  * a record whose refined->valid is 0 prints its message's own snr_db, dt_s and freq_hz in the same format */
 int ft8gpu_format_messages_refined(const ft8gpu_message *msgs, const ft8gpu_refined *refined, int32_t n, char *out, size_t cap);
 
+/* ---- subtraction in the I/Q samples: decode again after the decoded signals are cancelled in the frame itself -----------------
+ * (DESIGN.md "Subtraction in the I/Q samples").  Every record's waveform is rebuilt from its tones at the place the refine
+ * stage found, searched once more on a grid of 0.78125 Hz by 8 samples, scaled by a smoothed complex amplitude and subtracted
+ * from the float samples.  This text is the rule; tests/ft8_spec_subtract.py restates it in numpy, and the device output equals
+ * the restatement byte for byte.  float32 throughout, one IEEE operation per step, nothing fused, every sum sequential in the
+ * stated order from +0, every phase an exact table index formed in uint32 (4096 divides 2^32, so wrapping is harmless).
+ *
+ * Inputs: the frame x[j], zero outside 0 .. 47999; a record's cand and a91; its ft8gpu_refined record R.  T, F and tone[m] are
+ * those of the refine rule.  u* = the first largest of R.pf[1 .. 3] (ft8gpu_refined_estimate's choice), as an index 1 .. 3.
+ * (a) w4[i] = (cos, -sin)(2 pi i / 4096), i < 4096, each the float of the double value (ft8gpu_subtract_twiddles): a step of
+ *     3200 / 4096 = 0.78125 Hz.  w4[4 i] is w[i] of the refine rule.
+ * (b) Reference phase of a start sample S and a base index k4:  K_m = k4 + 8 tone[m];  Theta_0 = 0,
+ *     Theta_(m+1) = (Theta_m + 512 K_m) mod 4096 (which is (512 m k4) mod 4096, the tones' share being whole turns);  for
+ *     s_m = S + 512 m <= j < s_m + 512:  theta(j) = (Theta_m + K_m (j - s_m)) mod 4096  -- the continuous phase of CPFSK up to
+ *     a constant.  z(j) = x[j] * w4[theta(j)] = (xr wr - xi wi, xr wi + xi wr).
+ *     seg(S, k4, q), q = 0 .. 1263: the sum of z over j = S + 32 q .. S + 32 q + 31, ascending from +0.
+ *     P(S, k4) = the sum over m = 0 .. 78, ascending from +0, of re^2 + im^2 of (seg(16 m) + ... + seg(16 m + 15), ascending
+ *     from +0).
+ * (c) Fine search.  S_0 = 256 T + FT8GPU_REFINE_LEAD + 32 R.e_best.  Frequency first:  pf[d + 2] = P(S_0, 4 (F + u* - 2) + d),
+ *     d = -2 .. 2;  d* = the first d in ascending order whose power is strictly greater than every earlier one (-2 when none
+ *     is);  k4* = 4 (F + u* - 2) + d*.  Then time:  pt[t + 2] = P(S_0 + 8 t, k4*), t = -2 .. 2;  t* likewise;
+ *     S* = S_0 + 8 t*, a multiple of 8.
+ * (d) Amplitude.  G(q) = seg(S*, k4*, q).  A(q) = (G(p_lo) + ... + G(p_hi)) * inv[n], both components summed ascending from
+ *     +0, p_lo = max(0, q - 8), p_hi = min(1263, q + 8), n = p_hi - p_lo + 1, inv[n] = (float)(1.0 / (32 n)) from a host
+ *     table (the device multiplies, it never divides).  Segments outside the frame hold zeros and still count in n.
+ * (e) Subtraction, for the records i = first[f] .. n_msgs[f] - 1 of frame f in that order: for every j inside record i's 79
+ *     symbols (S*_i <= j < S*_i + 40448) and inside the frame, with q = (j - S*_i) / 32 and w = w4[theta_i(j)]:
+ *       x'r[j] = x'r[j] - (Ar wr + Ai wi);   x'i[j] = x'i[j] - (Ai wr - Ar wi)                      (A = A_i(q); A conj(w))
+ *     Every A_i comes from the INPUT frame, not from a partly subtracted one; only this accumulation is ordered.  Samples
+ *     outside every record are copied bit for bit.
+ * A record with R.valid == 0 is skipped (its info is all zero); every other cand, a91 and R give defined output. */
+#define FT8GPU_SUBTRACT_TABLE   4096    /* entries of w4 */
+#define FT8GPU_SUBTRACT_SMOOTH  8       /* the amplitude is averaged over q - 8 .. q + 8: 17 segments of 32 samples */
+#define FT8GPU_SUBTRACT_RANGE   2       /* both fine searches cover -2 .. 2 */
+#define FT8GPU_SUBTRACT_TSTEP   8       /* samples per step of the fine time search */
+typedef struct {
+    int32_t k4;              /*  0  k4* */
+    int32_t s_best;          /*  4  S* */
+    int8_t  d_best;          /*  8  d* */
+    int8_t  t_best;          /*  9  t* */
+    uint8_t valid;           /* 10  1 when the record was subtracted, 0 when it was skipped (everything else zero then) */
+    uint8_t pad0;            /* 11  zero */
+    float   pf[5];           /* 12 */
+    float   pt[5];           /* 32 */
+    uint8_t pad[12];         /* 52  zero */
+} ft8gpu_subtract_info;
+#ifndef __cplusplus
+_Static_assert(sizeof(ft8gpu_subtract_info) == 64 && offsetof(ft8gpu_subtract_info, s_best) == 4 &&
+               offsetof(ft8gpu_subtract_info, d_best) == 8 && offsetof(ft8gpu_subtract_info, t_best) == 9 &&
+               offsetof(ft8gpu_subtract_info, valid) == 10 && offsetof(ft8gpu_subtract_info, pad0) == 11 &&
+               offsetof(ft8gpu_subtract_info, pf) == 12 && offsetof(ft8gpu_subtract_info, pt) == 32 &&
+               offsetof(ft8gpu_subtract_info, pad) == 52, "ft8gpu_subtract_info layout");
+#else
+static_assert(sizeof(ft8gpu_subtract_info) == 64 && offsetof(ft8gpu_subtract_info, s_best) == 4 &&
+              offsetof(ft8gpu_subtract_info, d_best) == 8 && offsetof(ft8gpu_subtract_info, t_best) == 9 &&
+              offsetof(ft8gpu_subtract_info, valid) == 10 && offsetof(ft8gpu_subtract_info, pad0) == 11 &&
+              offsetof(ft8gpu_subtract_info, pf) == 12 && offsetof(ft8gpu_subtract_info, pt) == 32 &&
+              offsetof(ft8gpu_subtract_info, pad) == 52, "ft8gpu_subtract_info layout");
+#endif
+/* host helper (plain C, no GPU): out[2 i], out[2 i + 1] = w4[i], 8192 floats */
+void ft8gpu_subtract_twiddles(float *out);
+/* stage entry: iq / iq_out [nframes][2][48000] (iq_out may be iq), msgs / refined / info [nframes][50], first / n_msgs
+ * [nframes] (each clamped to [0, 50]); host or device pointers by `flags` (device form: iq and iq_out 16-byte aligned).
+ * iq_out[f] = iq[f] with the records [first[f], n_msgs[f]) subtracted; info[f][i] is written for those records and not touched
+ * elsewhere; info may be NULL. */
+int ft8gpu_subtract_messages(ft8gpu_ctx *ctx, const float *iq, const ft8gpu_message *msgs, const ft8gpu_refined *refined,
+                             const int32_t *first, const int32_t *n_msgs, int nframes, float *iq_out,
+                             ft8gpu_subtract_info *info, int flags);
+/* Multi-pass decoding with subtraction.  Pass 1 is ft8gpu_decode_messages, unchanged, on x_1 = iq.  Pass p + 1, for every frame
+ * that gained records in pass p and holds fewer than 50: the records first written in pass p are refined on x_p
+ * (ft8gpu_refine_messages) and subtracted from it, x_(p+1); the waterfall, sync search, candidate heap and LDPC decode run on
+ * x_(p+1) with the context's params; ft8gpu_append_messages' rule appends the new unique messages (snr_db from this pass's
+ * waterfall against the pass-1 baseline).  Every other frame keeps its x_p and is not decoded again.  passes in
+ * [1, FT8GPU_MAX_PASSES]; msgs, n_msgs, n_by_pass as ft8gpu_decode_messages_passes; residual [nframes][2][48000] (NULL: not
+ * written) receives every frame's last x_p.  iq is never written.  Host or device pointers, chunked by max_frames; the host
+ * reads one int per later pass and stops early when no frame is left. */
+int ft8gpu_decode_messages_subtracted(ft8gpu_ctx *ctx, const float *iq, int nframes, int passes, ft8gpu_message *msgs,
+                                      int32_t *n_msgs, int32_t *n_by_pass, float *residual, int flags);
+
 /* ---- tooling: encoder + synthetic frames (pack77 / ft8_encode / CPFSK synth of
  *      decoderSelfTest, rtlsdr_ft8d.c:924-955) --------------------------------------------- */
 /* Message text -> 77 bits in 10 bytes (pack77, :927); 0 = ok, -1 = the text fits no message type.  Tokens are separated

@@ -77,6 +77,11 @@ COMBINE_STORE_PER_SLOT = 48      # FT8GPU_COMBINE_STORE_PER_SLOT, the recommende
 REFINED_DTYPE = np.dtype([("e_best", "<i2"), ("valid", "u1"), ("pad0", "u1"), ("pt", "<f4", (3,)), ("pf", "<f4", (5,)),
                           ("noise", "<f4"), ("pad", "u1", (8,))])
 assert REFINED_DTYPE.itemsize == 48
+# subtraction in the I/Q samples (ft8gpu_subtract_messages): what the fine search chose for a record
+SUBTRACT_INFO_DTYPE = np.dtype([("k4", "<i4"), ("s_best", "<i4"), ("d_best", "i1"), ("t_best", "i1"), ("valid", "u1"), ("pad0", "u1"),
+                                ("pf", "<f4", (5,)), ("pt", "<f4", (5,)), ("pad", "u1", (12,))])
+SUBTRACT_TABLE = 4096            # FT8GPU_SUBTRACT_TABLE
+assert SUBTRACT_INFO_DTYPE.itemsize == 64
 assert SOFTMEM_ENTRY_DTYPE.itemsize == 720 and SOFTMEM_STATE_DTYPE.itemsize == 92176 and COMBINE_INFO_DTYPE.itemsize == 8
 
 
@@ -156,6 +161,7 @@ ABI_SYMBOLS = [
     "ft8gpu_expect_insert", "ft8gpu_expect_insert_text",
     "ft8gpu_combine_candidates", "ft8gpu_softmem_update", "ft8gpu_decode_messages_combined", "ft8gpu_softmem_reset",
     "ft8gpu_refine_messages", "ft8gpu_decode_messages_refined", "ft8gpu_refined_estimate", "ft8gpu_format_messages_refined",
+    "ft8gpu_subtract_messages", "ft8gpu_decode_messages_subtracted", "ft8gpu_subtract_twiddles",
     "ft8_find_sync", "ft8_decode", "ft8_encode", "pack77",            # ft8_lib level (include/ft8_lib/ft8/*.h)
     "initFFTW", "freeFFTW", "ft8_subsystem", "ft8gpu_read_raw_iq", "ft8gpu_read_c2", "ft8gpu_write_raw_iq",
 ]
@@ -322,6 +328,11 @@ def _declare(L):
         L.ft8gpu_decode_messages_refined.argtypes = [vp, vp, C.c_int, vp, vp, vp, C.c_int]
         L.ft8gpu_refined_estimate.argtypes = [vp, vp, C.POINTER(C.c_float), C.POINTER(C.c_float), C.POINTER(C.c_float)]
         L.ft8gpu_format_messages_refined.argtypes = [vp, vp, C.c_int32, vp, C.c_size_t]
+    if hasattr(L, "ft8gpu_subtract_messages"):
+        L.ft8gpu_subtract_messages.argtypes = [vp, vp, vp, vp, vp, vp, C.c_int, vp, vp, C.c_int]
+        L.ft8gpu_decode_messages_subtracted.argtypes = [vp, vp, C.c_int, C.c_int, vp, vp, vp, vp, C.c_int]
+        L.ft8gpu_subtract_twiddles.argtypes = [vp]
+        L.ft8gpu_subtract_twiddles.restype = None
     L.ft8gpu_rx_decimate.argtypes = [vp, vp, C.c_int, C.c_size_t, vp, C.c_int, C.c_int]
     if hasattr(L, "ft8gpu_rx_stream"):                    # absent from older builds loaded by load_library_at
         L.ft8gpu_rx_stream.argtypes = [vp, vp, C.c_int, C.c_int, C.c_size_t, vp, vp, vp, C.c_int, C.c_int]
@@ -1076,6 +1087,58 @@ class Decoder:
         self._ck(self.lib.ft8gpu_decode_messages_refined(self.h, _ptr(iq_dev), int(nframes), _ptr(msgs_dev), _ptr(n_msgs_dev),
                                                        _ptr(refined_dev), DEVICE_PTRS))
 
+    def subtract_messages(self, iq, msgs, refined, first, n_msgs, info=None, want_info=True):
+        """the subtraction stage (ft8gpu_subtract_messages) -> (iq_out [B][2][48000], info [B][50] SUBTRACT_INFO_DTYPE): the frames
+        with the records [first[f], n_msgs[f]) subtracted; info records outside that range keep what `info` held (zeros when None).
+        want_info = False passes NULL and returns (iq_out, None)."""
+        iq = np.ascontiguousarray(iq, np.float32)
+        msgs = np.ascontiguousarray(msgs)
+        refined = np.ascontiguousarray(refined)
+        first = np.ascontiguousarray(first, np.int32)
+        n_msgs = np.ascontiguousarray(n_msgs, np.int32)
+        B = iq.shape[0]
+        assert iq.shape[1:] == (2, NSAMPLES) and msgs.dtype == MESSAGE_DTYPE and msgs.shape == (B, MAX_MESSAGES)
+        assert refined.dtype == REFINED_DTYPE and refined.shape == (B, MAX_MESSAGES) and first.shape == (B,) and n_msgs.shape == (B,)
+        if not want_info:
+            info = None
+        elif info is None:
+            info = np.zeros((B, MAX_MESSAGES), SUBTRACT_INFO_DTYPE)
+        assert info is None or (info.dtype == SUBTRACT_INFO_DTYPE and info.shape == (B, MAX_MESSAGES) and info.flags["C_CONTIGUOUS"])
+        out = np.zeros((B, 2, NSAMPLES), np.float32)
+        self._ck(self.lib.ft8gpu_subtract_messages(self.h, iq.ctypes.data, msgs.ctypes.data, refined.ctypes.data, first.ctypes.data,
+                                                 n_msgs.ctypes.data, B, out.ctypes.data, None if info is None else info.ctypes.data,
+                                                 HOST_PTRS))
+        return out, info
+
+    def subtract_messages_dev(self, iq_dev, msgs_dev, refined_dev, first_dev, n_msgs_dev, nframes, iq_out_dev, info_dev=None):
+        """every array in HBM (iq_dev and iq_out_dev 16-byte aligned; iq_out_dev may be iq_dev); info_dev: [nframes][50] 64-byte
+        records or None"""
+        self._ck(self.lib.ft8gpu_subtract_messages(self.h, _ptr(iq_dev), _ptr(msgs_dev), _ptr(refined_dev), _ptr(first_dev),
+                                                 _ptr(n_msgs_dev), int(nframes), _ptr(iq_out_dev),
+                                                 None if info_dev is None else _ptr(info_dev), DEVICE_PTRS))
+
+    def decode_messages_subtracted(self, iq, passes=2, msgs=None, want_residual=True):
+        """multi-pass decoding with subtraction in the I/Q samples (ft8gpu_decode_messages_subtracted) -> (msgs [B][50], n_msgs [B],
+        n_by_pass [B][passes], residual [B][2][48000] or None): every frame's last x_p"""
+        iq = np.ascontiguousarray(iq, np.float32)
+        B = iq.shape[0]
+        assert iq.shape[1:] == (2, NSAMPLES)
+        if msgs is None:
+            msgs = np.zeros((B, MAX_MESSAGES), MESSAGE_DTYPE)
+        assert msgs.dtype == MESSAGE_DTYPE and msgs.shape == (B, MAX_MESSAGES) and msgs.flags["C_CONTIGUOUS"]
+        n = np.zeros(B, np.int32)
+        nbp = np.zeros((B, max(int(passes), 1)), np.int32)
+        res = np.zeros((B, 2, NSAMPLES), np.float32) if want_residual else None
+        self._ck(self.lib.ft8gpu_decode_messages_subtracted(self.h, iq.ctypes.data, B, int(passes), msgs.ctypes.data, n.ctypes.data,
+                                                          nbp.ctypes.data, None if res is None else res.ctypes.data, HOST_PTRS))
+        return msgs, n, nbp, res
+
+    def decode_messages_subtracted_dev(self, iq_dev, nframes, passes, msgs_dev, n_msgs_dev, n_by_pass_dev=None, residual_dev=None):
+        """n_by_pass_dev: [nframes][passes] int32 or None; residual_dev: [nframes][2][48000] float32 (16-byte aligned) or None"""
+        self._ck(self.lib.ft8gpu_decode_messages_subtracted(self.h, _ptr(iq_dev), int(nframes), int(passes), _ptr(msgs_dev),
+                                                          _ptr(n_msgs_dev), None if n_by_pass_dev is None else _ptr(n_by_pass_dev),
+                                                          None if residual_dev is None else _ptr(residual_dev), DEVICE_PTRS))
+
     def ap_candidates_dev(self, mag_dev, cands_dev, counts_dev, status_in_dev, nframes, hyps, max_hard_errors, status_out_dev, info_dev):
         """status_out_dev may be status_in_dev; info_dev: [nframes][max_candidates] 8-byte records; hyps stay on the host"""
         hyps = _ap_hyps(hyps)
@@ -1349,6 +1412,14 @@ def refined_estimate(msgs, refined):
             o[:, i] = (a.value, b.value, c.value)
             ok.reshape(-1)[i] = True
     return out[0], out[1], out[2], ok
+
+
+def subtract_twiddles():
+    """ft8gpu_subtract_twiddles: w4[i] = (cos, -sin)(2 pi i / 4096) as float32 [4096][2]"""
+    L = load_library()
+    out = np.zeros((SUBTRACT_TABLE, 2), np.float32)
+    L.ft8gpu_subtract_twiddles(out.ctypes.data)
+    return out
 
 
 def format_messages_refined(msgs, refined, n):

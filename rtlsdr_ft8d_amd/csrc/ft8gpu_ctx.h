@@ -80,6 +80,13 @@ struct ft8gpu_ctx {
     int ap_cap = 0;
     int32_t *d_nap = nullptr;              //   the counts before the AP append [max_frames], host staging of n_by_stage
     int32_t *d_nbs3 = nullptr;             //   [max_frames][FT8GPU_MAX_PASSES][3]
+    struct SubTables *d_subtab = nullptr;  // subtraction in the I/Q samples, lazily on its first call: the constant tables,
+    uint32_t *d_sub_scratch = nullptr;     //   what the estimate kernel leaves for the apply kernel [sub_frames][50][2560],
+    int sub_frames = 0;
+    float *d_sub_x = nullptr;              //   the frames being subtracted from [max_frames][2][48000] (staging of iq_out / residual),
+    ft8gpu_refined *d_sub_ref = nullptr;   //   the refined records [max_frames][50], the info records of the host form,
+    ft8gpu_subtract_info *d_sub_info = nullptr;
+    int32_t *d_sub_nref = nullptr;         //   and the counts a pass refines and subtracts [max_frames]
     ft8gpu_synth_signal *d_sigs = nullptr;
     size_t sigs_cap = 0;
     void *d_rx_sums = nullptr, *d_rx_p2 = nullptr;     // RX front end scratch
@@ -169,6 +176,8 @@ int ensure_osd_buffers(ft8gpu_ctx *c);
 int check_osd_args(int order, int max_hard_errors);
 // api_ap.hip: frees the AP buffers (ft8gpu_destroy)
 void free_ap_buffers(ft8gpu_ctx *c);
+// api_subtract.hip: frees the subtraction buffers (ft8gpu_destroy)
+void free_subtract_buffers(ft8gpu_ctx *c);
 // ft8gpu_decode_batch with one more form: kIqOnDevice, frames resident on the context's GPU and records to host arrays
 // (used by the multi-GPU entries; not part of the ABI, whose entry passes on FT8GPU_DEVICE_PTRS only)
 constexpr int kIqOnDevice = 2;
