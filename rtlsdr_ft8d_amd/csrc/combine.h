@@ -5,7 +5,8 @@
 constexpr int kSoftmemEntries = FT8GPU_SOFTMEM_ENTRIES;
 
 // combine.hip: the soft-bit memory of a receiver against the candidates BP gives up on (include/ft8gpu.h "soft-bit memory").
-// combine_tables_init uploads the file's own copy of the LDPC edge tables and the CRC table (ap.hip keeps its own).
+// combine_tables_init uploads the file's instance of the LDPC tables (cand_dev.h: LdpcTables; a __device__ variable belongs
+// to one translation unit, so ap.hip has another).
 hipError_t combine_tables_init(hipStream_t s);
 hipError_t launch_combine(const uint8_t *mag, const ft8gpu_candidate *cands, const int32_t *counts,
                           const ft8gpu_decode_status *status_in, ft8gpu_decode_status *status_out, ft8gpu_combine_info *info,

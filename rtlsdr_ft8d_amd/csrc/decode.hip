@@ -28,22 +28,11 @@
 //     operation can observe.)
 //   * every other float expression is written in the reference's operation order and compiled
 //     with -ffp-contract=off (fused operations appear only inside the division chain above).
-#include "ft8gpu_internal.h"
-#include "ft8_tables.h"
-#include "unpack_dev.h"
-#include "bp_math.h"
-#include "ldpc_lds_layout.h"
-#include <stddef.h>
-#include <stdlib.h>
-#include <type_traits>
+// The wave helpers, the division guard (guard_key) and the builders of the LDPC tables are shared with the kernels that give
+// this one's failures a second chance (cand_dev.h).
+#include "cand_dev.h"
 
 namespace {
-
-using bpm::f2;
-using bpm::tanh_pair;
-using bpm::tanh_one;
-using bpm::atanh_pair;
-using bpm::atanh_one;
 
 // The pipeline only needs to know WHETHER a hard decision satisfies all 83 checks (the error count
 // matters to nobody once it is non-zero).  The XOR of any set of parity rows is itself a parity
@@ -68,28 +57,6 @@ struct DecodeTables {
 };
 
 __device__ DecodeTables d_tab;
-__constant__ uint8_t c_gray[8] = { 0, 1, 3, 2, 5, 6, 4, 7 };
-
-constexpr int kRows = 84;                     // 83 check rows + 1 spare row for idle lanes
-constexpr int kTocFloats = kRows * 8;         // plane LO: [84] float4 (slots 0..3), plane HI: [84] float4 (slots 4..7)
-constexpr int kWaveLds = kTocFloats + 192;    // + 174 LLRs
-
-__host__ __device__ constexpr int slot_index(int m, int pos) {
-    return pos < 4 ? 4 * m + pos : 4 * kRows + 4 * m + (pos - 4);
-}
-
-// min(|a|, |b|, |c|) in one instruction (no canonicalising copies of the operands)
-__device__ __forceinline__ float min3_abs(float a, float b, float c) {
-    float r;
-    asm("v_min3_f32 %0, |%1|, |%2|, |%3|" : "=v"(r) : "v"(a), "v"(b), "v"(c));
-    return r;
-}
-// a + b as one v_add_f32 the vectoriser cannot see through
-__device__ __forceinline__ float add_f32(float a, float b) {
-    float r;
-    asm("v_add_f32 %0, %1, %2" : "=v"(r) : "v"(a), "v"(b));
-    return r;
-}
 
 // a * (b.x, b.x) and a * (b.y, b.y) as one v_pk_mul_f32: the broadcast of one half of b is the instruction's op_sel /
 // op_sel_hi operand modifier.  (Register pairs are even-aligned, so a float that a ds_read_b128 left in an odd register
@@ -111,83 +78,6 @@ __device__ __forceinline__ float any_f32() {
     float r;
     asm volatile("" : "=v"(r));
     return r;
-}
-
-// Guard key of a value: (bits << 1) - 1 as unsigned.  Zero maps to 0xFFFFFFFF, every other value to
-// twice its magnitude bits minus one, so "minimum key over a set >= key(T)" says: each member is
-// zero or at least T in magnitude.
-//
-// ONE guard per iteration, on the nine row products P of the lane, with T = 2^-59, covers both
-// division sites of the following work:
-//   * fast_atanh(P): numerator P*(945 - 735P^2 + 64P^4) with |P| <= 1.0072^6, so |numerator| >= 200|P|;
-//   * the state ah = fast_atanh(P) (tov = -2*ah) then satisfies ah == 0 or |ah| >= 2^-59 (|atanh_r(P)| >= |P|),
-//     and the halved LLRs cwh are 0 or >= 0.0095 (an integer times sqrt(24/variance)/2, variance <= 255^2).
-//     Any sum of two or three floats that are each 0 or >= 2^-59 is 0 or >= 2^-82 (all are multiples of
-//     2^-82), hence the next iteration's x is 0 or >= 2^-82, and fast_tanh's numerator x*(945 + ...) >= 945|x|.
-// Both are far above v_div_scale's 2^-103 rescaling threshold.  Large, infinite and NaN values need
-// no guard: |x| > 4.97 is overridden by fast_tanh's clamp in either division form, the products are
-// bounded, and NaN stays NaN through both forms.  Iteration 0 starts from tov = 0.
-//
-// The products of iteration 0 satisfy the guard by construction, so it is not evaluated for them (exact-zero LLRs
-// -- differences of bytes -- are common, and each would send the quick form on to the exact key test).  Proof:
-//   * in iteration 0 every message is x = cwh + 0 + 0 = cwh = -(k * f) / 2 with an integer |k| <= 255 and
-//     f = sqrtf(24 / variance).  variance = (sum2 - sum^2/174) / 174 <= sum2 / 174 <= 255^2, so f >= sqrt(24)/255 >
-//     0.0192 and x is 0 or |x| >= 0.0096 > 2^-6.71 (f infinite or NaN -- variance 0 or, by rounding, below 0 -- gives
-//     infinite or NaN x: no guard needed, see above);
-//   * t = fast_tanh(x) = x r(x^2) with r(u) = (945 + 105 u + u^2) / (945 + 420 u + 15 u^2): zero only for x = 0.
-//     r falls on u >= 0 (the numerator of r' is -297675 - 26460 u - 1155 u^2), so for |x| <= 4.97 it is at least
-//     r(4.97^2) = 0.2026, hence |t| >= 0.2026 * 0.0096 > 2^-9.01; beyond 4.97 the clamp gives |t| = 1.  The handful of
-//     roundings in f, x and t move these by parts in 2^-22: take |t| > 2^-9.1;
-//   * a row product multiplies at most six such t (rows have six or seven members and skip one); |t| <= 1.0073, so no
-//     partial product leaves the normal range, none is zero unless a factor is, and each of the five roundings loses
-//     at most 2^-24 of the value: P is 0 or |P| > 2^-54.6 (1 - 2^-24)^5 > 2^-55 > 2^-59 = T.
-// (What the guard of iteration k > 0 sees depends on the sums of messages and has no such bound.)
-__device__ __forceinline__ uint32_t guard_key(float v) { return (__float_as_uint(v) << 1) - 1u; }
-constexpr uint32_t kGuardMin = ((127u - 59u) << 24) - 1u;       // guard_key(0x1p-59f)
-
-__device__ __forceinline__ void wave_lds_sync() {
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-}
-
-// sum over the 64 lanes with DPP adds (no LDS crossbar round trips); the total comes back uniform
-__device__ __forceinline__ int wave_sum(int v) {
-    v += __builtin_amdgcn_update_dpp(0, v, 0xB1, 0xF, 0xF, true);    // quad_perm [1,0,3,2]
-    v += __builtin_amdgcn_update_dpp(0, v, 0x4E, 0xF, 0xF, true);    // quad_perm [2,3,0,1]
-    v += __builtin_amdgcn_update_dpp(0, v, 0x141, 0xF, 0xF, true);   // row_half_mirror
-    v += __builtin_amdgcn_update_dpp(0, v, 0x140, 0xF, 0xF, true);   // row_mirror: every lane holds its row's sum
-    v += __builtin_amdgcn_update_dpp(0, v, 0x142, 0xA, 0xF, true);   // row_bcast:15 into rows 1 and 3
-    v += __builtin_amdgcn_update_dpp(0, v, 0x143, 0xC, 0xF, true);   // row_bcast:31 into rows 2 and 3
-    return __builtin_amdgcn_readlane(v, 63);
-}
-
-// the same reduction with XOR (CRC contributions of the set payload bits)
-__device__ __forceinline__ uint32_t wave_xor(uint32_t x) {
-    int v = (int)x;
-    v ^= __builtin_amdgcn_update_dpp(0, v, 0xB1, 0xF, 0xF, true);
-    v ^= __builtin_amdgcn_update_dpp(0, v, 0x4E, 0xF, 0xF, true);
-    v ^= __builtin_amdgcn_update_dpp(0, v, 0x141, 0xF, 0xF, true);
-    v ^= __builtin_amdgcn_update_dpp(0, v, 0x140, 0xF, 0xF, true);
-    v ^= __builtin_amdgcn_update_dpp(0, v, 0x142, 0xA, 0xF, true);
-    v ^= __builtin_amdgcn_update_dpp(0, v, 0x143, 0xC, 0xF, true);
-    return (uint32_t)__builtin_amdgcn_readlane(v, 63);
-}
-
-// ftx_compute_crc(a91 with bits 77.. cleared, 82 bits): CRC-14, polynomial 0x2757.  Bit-serial
-// restatement (only the first 77 bits can be set; five zero bits follow).  Runs on the host when the tables are
-// built: the kernel uses the linearity of the CRC (init 0, no final XOR) -- the CRC of a message is the XOR of the
-// CRCs of its set bits -- so each lane contributes the table entries of the payload bits it holds and one DPP
-// reduction replaces 82 dependent shift/xor steps on a single lane.
-__host__ __device__ inline uint32_t crc14_82(const uint8_t *msg) {
-    uint32_t rem = 0;
-    int idx_byte = 0;
-    for (int bit = 0; bit < 82; ++bit) {
-        if ((bit & 7) == 0) rem ^= (uint32_t)msg[idx_byte++] << 6;
-        if (rem & 0x2000u) rem = ((rem << 1) ^ 0x2757u) & 0xFFFFu;
-        else rem = (rem << 1) & 0xFFFFu;
-    }
-    return rem & 0x3FFFu;
 }
 
 // COUNT_ERRORS: ldpc_check() on every iteration with the exact number of failed rows (status
@@ -597,40 +487,14 @@ void ft8_decode_kernel(const uint8_t *__restrict__ mag, const ft8gpu_candidate *
 
 hipError_t decode_tables_init(hipStream_t s) {
     static DecodeTables h;
-    for (int r = 0; r < 3; ++r)
-        for (int l = 0; l < 64; ++l) {
-            const int n = l + 64 * r;
-            for (int e = 0; e < 3; ++e) {
-                if (n >= kLdpcN) { h.edge_slot[r][l][e] = (uint16_t)slot_index(kRows - 1, e); continue; }
-                const int m = kFT8_Mn[n][e] - 1;
-                int pos = -1;
-                for (int j = 0; j < kFT8_Num_rows[m]; ++j)
-                    if (kFT8_Nm[m][j] - 1 == n) pos = j;
-                // the row's place in the LDS tile comes from the conflict-minimising layout (ldpc_lds_layout.h); its members keep their order
-                h.edge_slot[r][l][e] = (uint16_t)slot_index(kLdsRowPos[m], pos);
-            }
-        }
-    for (int rr = 0; rr < 2; ++rr)
-        for (int l = 0; l < 64; ++l) {
-            const int m = l + 64 * rr;
-            h.row_valid[rr][l] = m < kLdpcM;
-            h.rowmask[rr][l][0] = h.rowmask[rr][l][1] = h.rowmask[rr][l][2] = 0;
-            if (m >= kLdpcM) continue;
-            for (int j = 0; j < kFT8_Num_rows[m]; ++j) {
-                const int n = kFT8_Nm[m][j] - 1;
-                h.rowmask[rr][l][n >> 6] |= 1ull << (n & 63);
-            }
-        }
     {
-        // which lane multiplies which row: also from the layout search (the float4 accesses of the owners want distinct positions
-        // mod 16 within their lane groups).  Checked here: every row is owned exactly once by a lane of the right kind, every
-        // position is used once, the spare position stays spare.
+        // The generated layout (ldpc_lds_layout.h), checked here, once, ahead of every use of the tables built from it: every row
+        // is owned exactly once by a lane of the right kind, every position is used once, the spare position stays spare.
         int owned[kLdpcM] = { 0 }, used[kRows] = { 0 };
         for (int l = 0; l < 64; ++l) {
-            h.own6[l] = h.own7[l] = (uint8_t)(kRows - 1);
             const int m6 = kOwn6Row[l], m7 = kOwn7Row[l];
-            if (m6 != 255) { if (m6 >= kLdpcM || kFT8_Num_rows[m6] != 6) abort(); h.own6[l] = kLdsRowPos[m6]; ++owned[m6]; }
-            if (m7 != 255) { if (m7 >= kLdpcM || kFT8_Num_rows[m7] != 7) abort(); h.own7[l] = kLdsRowPos[m7]; ++owned[m7]; }
+            if (m6 != 255) { if (m6 >= kLdpcM || kFT8_Num_rows[m6] != 6) abort(); ++owned[m6]; }
+            if (m7 != 255) { if (m7 >= kLdpcM || kFT8_Num_rows[m7] != 7) abort(); ++owned[m7]; }
         }
         for (int m = 0; m < kLdpcM; ++m) { if (owned[m] != 1 || kLdsRowPos[m] >= kRows - 1 || used[kLdsRowPos[m]]++) abort(); }
         if (kLdsRowPos[kRows - 1] != kRows - 1) abort();
@@ -641,6 +505,10 @@ hipError_t decode_tables_init(hipStream_t s) {
             for (int l = 0; l < 64; ++l)
                 if (kVarOf[r][l] != (l + 64 * r < kLdpcN ? l + 64 * r : 255)) abort();
     }
+    fill_edge_slots(h.edge_slot);
+    fill_rowmasks(h.rowmask, h.row_valid);
+    fill_owners(h.own6, h.own7);
+    fill_crc_bits(h.crc_bit);
     for (int G = 1; G <= kMaxCheckGroups; ++G) {
         for (int g = 0; g < kMaxCheckGroups; ++g)
             for (int w = 0; w < 3; ++w) h.group_mask[G][g][w] = 0;
@@ -649,11 +517,6 @@ hipError_t decode_tables_init(hipStream_t s) {
                 const int n = kFT8_Nm[m][j] - 1;
                 h.group_mask[G][m % G][n >> 6] ^= 1ull << (n & 63);
             }
-    }
-    for (int i = 0; i < 77; ++i) {
-        uint8_t m[12] = { 0 };
-        m[i >> 3] = (uint8_t)(0x80u >> (i & 7));                 // payload bit i, MSB first (pack_bits order)
-        h.crc_bit[i] = (uint16_t)crc14_82(m);
     }
     return hipMemcpyToSymbolAsync(HIP_SYMBOL(d_tab), &h, sizeof(h), 0, hipMemcpyHostToDevice, s);
 }

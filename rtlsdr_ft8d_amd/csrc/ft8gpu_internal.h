@@ -86,7 +86,7 @@ hipError_t launch_append(const uint8_t *mag, const uint8_t *base, const ft8gpu_c
                          int max_candidates, int min_score, ft8gpu_message *msgs, int32_t *n_msgs, hipStream_t s);
 hipError_t launch_pass_counts(const int32_t *n_msgs, int32_t *nbp, int nframes, int passes, int col0, hipStream_t s);
 // osd.hip: ordered-statistics decoding of the candidates BP gives up on (DESIGN.md "Ordered-statistics decoding");
-// osd_tables_init uploads the generator's column masks and the CRC table on the first OSD call
+// osd_tables_init uploads the generator's column masks and the CRC table (cand_dev.h builds it) on the first OSD call
 hipError_t osd_tables_init(hipStream_t s);
 hipError_t launch_osd(const uint8_t *mag, const ft8gpu_candidate *cands, const int32_t *counts,
                       const ft8gpu_decode_status *status_in, ft8gpu_decode_status *status_out, ft8gpu_osd_info *info,
@@ -94,8 +94,8 @@ hipError_t launch_osd(const uint8_t *mag, const ft8gpu_candidate *cands, const i
 // pad[0] = nhard for the records [n_before[f], n_msgs[f]) of the frames behind the pass's slots (map == nullptr: slot = frame)
 hipError_t launch_osd_tag(const ft8gpu_osd_info *info, const int32_t *map, const int32_t *n_before, const int32_t *n_msgs,
                           int nslots, int max_candidates, ft8gpu_message *msgs, hipStream_t s);
-// ap.hip: a-priori decoding of the candidates BP gives up on (DESIGN.md "A-priori decoding"); ap_tables_init uploads its copy
-// of the LDPC edge tables and the CRC table on the first AP call; hyps is host memory (it travels as a kernel argument)
+// ap.hip: a-priori decoding of the candidates BP gives up on (DESIGN.md "A-priori decoding"); ap_tables_init uploads the
+// file's instance of the LDPC tables (cand_dev.h: LdpcTables) on the first AP call; hyps is host memory (it travels as a kernel argument)
 hipError_t ap_tables_init(hipStream_t s);
 hipError_t launch_ap(const uint8_t *mag, const ft8gpu_candidate *cands, const int32_t *counts,
                      const ft8gpu_decode_status *status_in, ft8gpu_decode_status *status_out, ft8gpu_ap_info *info,

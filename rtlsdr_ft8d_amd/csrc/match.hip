@@ -13,20 +13,17 @@
 //                             side.  h and the weights are wave-uniform: three 64-bit words and eight bit planes of three
 //                             words (ballots, SGPRs), so the metric of an entry is 24 and / popcount pairs on its c_j ^ h
 //                             instead of 174 table steps.  metric << 9 | index through one butterfly minimum is the best
-//                             entry with the rule's tie break.  The epilogue is OSD's: unpack77 on two 64-bit words, the
-//                             48-byte record of a BP success composed in LDS.
+//                             entry with the rule's tie break.  The soft bits and the epilogue -- unpack77 on two 64-bit
+//                             words, the 48-byte record of a BP success composed in LDS -- are the shared device code of
+//                             cand_dev.h.
 //   ft8_expect_update_kernel  the update rule, one wave per receiver with its table in LDS (8 KB): a receiver is a strictly
 //                             sequential walk over its slots and records; an insert first looks for its 77 bits (eight
 //                             entries per lane, ballots, the smallest index), then refreshes that entry or overwrites the
 //                             one under the cursor.
 #include "match.h"
-#include "unpack_dev.h"
-#include "bp_math.h"
-#include <stddef.h>
+#include "cand_dev.h"
 
 namespace {
-
-__constant__ uint8_t c_match_gray[8] = { 0, 1, 3, 2, 5, 6, 4, 7 };
 
 constexpr int kOffRec = 192;                           // dwords: 174 soft bits, then the record
 constexpr int kMatchLds = kOffRec + 12;
@@ -34,22 +31,6 @@ constexpr int kIdxBits = 9;                            // 512 entries; metric <=
 constexpr uint32_t kKeyNone = 0xFFFFFFFFu;
 static_assert(kExpectEntries == 1 << kIdxBits, "the key holds a table index in its low bits");
 static_assert(sizeof(ft8gpu_expect_entry) == 16 && sizeof(ft8gpu_expect_state) == 8208, "table layout");
-
-__device__ __forceinline__ void wave_lds_sync() {
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-}
-__device__ __forceinline__ int wave_sum(int v) {
-#pragma unroll
-    for (int m = 1; m < 64; m <<= 1) v += __shfl_xor(v, m);
-    return __builtin_amdgcn_readfirstlane(v);
-}
-__device__ __forceinline__ uint32_t wave_min(uint32_t v) {
-#pragma unroll
-    for (int m = 1; m < 64; m <<= 1) v = min(v, (uint32_t)__shfl_xor((int)v, m));
-    return (uint32_t)__builtin_amdgcn_readfirstlane((int)v);
-}
 
 // the 77 payload bits of a table entry (or of a91) as two words, MSB first: bits 0..63, and bits 64..76 at the top
 __device__ __forceinline__ void payload_words(uint32_t x, uint32_t y, uint32_t z, uint64_t &w0, uint64_t &w1) {
@@ -96,15 +77,6 @@ void ft8_expect_encode_kernel(const ft8gpu_expect_state *__restrict__ states, ui
     if ((threadIdx.x & 63) == 0) live[(size_t)frame * kExpectRounds + (e >> 6)] = mask;
 }
 
-// sum of the weights over the set bits of x: weights as eight bit planes
-__device__ __forceinline__ uint32_t metric_of(const uint64_t x[3], const uint64_t (&P)[8][3]) {
-    uint32_t m = 0;
-#pragma unroll
-    for (int b = 0; b < 8; ++b)
-        m += (uint32_t)(__popcll(x[0] & P[b][0]) + __popcll(x[1] & P[b][1]) + __popcll(x[2] & P[b][2])) << b;
-    return m;
-}
-
 __global__ __launch_bounds__(256)
 void ft8_match_kernel(const uint8_t *__restrict__ mag, const ft8gpu_candidate *__restrict__ cands,
                       const int32_t *__restrict__ counts, const ft8gpu_decode_status *status_in,
@@ -126,69 +98,17 @@ void ft8_match_kernel(const uint8_t *__restrict__ mag, const ft8gpu_candidate *_
     uint32_t *info32 = reinterpret_cast<uint32_t *>(info + rec_index);
     static_assert(sizeof(ft8gpu_decode_status) == 48 && sizeof(ft8gpu_match_info) == 8, "record sizes");
 
-    // ---- which candidates: ok == 0 and ldpc_errors != 0 (status_out may be status_in: read first) -------------------
-    const uint32_t mine = lane < 12 ? in32[lane] : 0u;
-    const uint32_t dw0 = (uint32_t)__builtin_amdgcn_readlane((int)mine, 0);
-    const uint32_t dw2 = (uint32_t)__builtin_amdgcn_readlane((int)mine, 2);
-    const bool attempt = ((dw2 >> 8) & 0xFFu) == 0u && (dw0 & 0xFFFFu) != 0u;
-    if (!attempt) {
-        if (lane < 12 && out32 != in32) out32[lane] = mine;
-        if (lane < 2) info32[lane] = 0u;
+    uint32_t mine, dw0;
+    if (!read_record(in32, lane, mine, dw0)) {                        // does not qualify
+        leave_record(out32, in32, info32, mine, 0u, lane);
         return;
     }
 
     uint32_t *s = s_mem[wave];
-    float *llr = reinterpret_cast<float *>(s);
-    const ft8gpu_candidate cand = cands[rec_index];
-
-    // ---- ft8_extract_likelihood, ftx_normalize_logl: the LDPC kernel's arithmetic (decode.hip, as in osd.hip) --------
-    if (lane < 58) {
-        const int k = lane;
-        const int sym = k + ((k < 29) ? 7 : 14);
-        const int block = cand.time_offset + sym;
-        int l0 = 0, l1 = 0, l2 = 0;
-        if (block >= 0 && block < kNumBlocks) {
-            const int index = ((cand.time_offset * 2 + cand.time_sub) * 2 + cand.freq_sub) * kNumBin + cand.freq_offset;
-            const uint8_t *ps = mag + (size_t)frame * kMagArray + index + sym * kBlockStride;
-            int s2[8];
-#pragma unroll
-            for (int j = 0; j < 8; ++j) s2[j] = ps[c_match_gray[j]];
-            l0 = max(max(s2[4], s2[5]), max(s2[6], s2[7])) - max(max(s2[0], s2[1]), max(s2[2], s2[3]));
-            l1 = max(max(s2[2], s2[3]), max(s2[6], s2[7])) - max(max(s2[0], s2[1]), max(s2[4], s2[5]));
-            l2 = max(max(s2[1], s2[3]), max(s2[5], s2[7])) - max(max(s2[0], s2[2]), max(s2[4], s2[6]));
-        }
-        llr[3 * k + 0] = (float)l0;
-        llr[3 * k + 1] = (float)l1;
-        llr[3 * k + 2] = (float)l2;
-    }
-    wave_lds_sync();
-
     float cw[3];
     bool has[3];
-    int isum = 0, isum2 = 0;
-#pragma unroll
-    for (int r = 0; r < 3; ++r) {
-        const int n = lane + 64 * r;
-        has[r] = n < kLdpcN;
-        cw[r] = has[r] ? llr[n] : 0.0f;
-        const int v = (int)cw[r];
-        isum += v;
-        isum2 += v * v;
-    }
-    const float sum = (float)wave_sum(isum);
-    const float sum2 = (float)wave_sum(isum2);
-    const float inv_n = 1.0f / 174;
-    const float variance = (sum2 - (sum * sum * inv_n)) * inv_n;
-    const float norm_factor = bpm::llr_norm_factor(variance);
-    bool finite = true;
-#pragma unroll
-    for (int r = 0; r < 3; ++r) {
-        cw[r] = has[r] ? cw[r] * norm_factor : 0.0f;
-        finite = finite && (__float_as_uint(cw[r]) & 0x7F800000u) != 0x7F800000u;
-    }
-    if (!__all(finite)) {                                             // wave-uniform: nothing is compared
-        if (lane < 12 && out32 != in32) out32[lane] = mine;
-        if (lane < 2) info32[lane] = lane == 0 ? 6u : 0u;
+    if (!soft_bits(mag, frame, cands[rec_index], reinterpret_cast<float *>(s), lane, cw, has)) {      // wave-uniform: nothing is compared
+        leave_record(out32, in32, info32, mine, 6u, lane);
         return;
     }
 
@@ -198,8 +118,7 @@ void ft8_match_kernel(const uint8_t *__restrict__ mag, const ft8gpu_candidate *_
 #pragma unroll
     for (int r = 0; r < kExpectRounds; ++r) { lm[r] = live[r]; any |= lm[r]; }
     if (any == 0ull) {
-        if (lane < 12 && out32 != in32) out32[lane] = mine;
-        if (lane < 2) info32[lane] = 0u;
+        leave_record(out32, in32, info32, mine, 0u, lane);
         return;
     }
 
@@ -244,39 +163,14 @@ void ft8_match_kernel(const uint8_t *__restrict__ mag, const ft8gpu_candidate *_
     const int nhard = __popcll(B[0] ^ H[0]) + __popcll(B[1] ^ H[1]) + __popcll(B[2] ^ H[2]);
 
     uint32_t *rec32 = s + kOffRec;
-    char *rec = reinterpret_cast<char *>(rec32);
-    const uint64_t w0 = __brevll(B[0]);                               // codeword bits 0..63, MSB first
-    const uint64_t w1 = __brevll(B[1]) & 0xFFFFFFE000000000ull;       // bits 64..90
     int result;
     if ((B[0] | B[1] | B[2]) == 0ull) result = 5;                     // the code is systematic: an all-zero payload
     else if (nhard > max_hard_errors) result = 2;
     else {
-        // the record of a BP success (decode.hip), iters as it was; the CRC is the encoder's own
-        static_assert(offsetof(ft8gpu_decode_status, a91) == 10 && offsetof(ft8gpu_decode_status, text) == 22, "record layout");
-        const uint32_t crc = (uint32_t)(w1 >> 37) & 0x3FFFu;
-        if (lane < 12) {
-            const uint32_t hi0 = (uint32_t)(w0 >> 32), lo0 = (uint32_t)w0, hi1 = (uint32_t)(w1 >> 32);
-            uint32_t v = 0;
-            if (lane == 0) v = dw0 & 0xFFFF0000u;
-            else if (lane == 1) v = crc | (crc << 16);
-            else if (lane == 2) v = (__builtin_bswap32(hi0) & 0xFFFFu) << 16;
-            else if (lane == 3) v = (__builtin_bswap32(hi0) >> 16) | (__builtin_bswap32(lo0) << 16);
-            else if (lane == 4) v = (__builtin_bswap32(lo0) >> 16) | (__builtin_bswap32(hi1) << 16);
-            else if (lane == 5) v = __builtin_bswap32(hi1) >> 16;
-            rec32[lane] = v;
-        }
-        wave_lds_sync();
-        int rc = 0;
-        if (lane == 0) {
-            rc = ft8dev::unpack77(w0, w1 & 0xFFF8000000000000ull, rec + offsetof(ft8gpu_decode_status, text));
-            rec[offsetof(ft8gpu_decode_status, unpack_status)] = (char)rc;
-            rec[offsetof(ft8gpu_decode_status, ok)] = 1;
-        }
-        rc = __builtin_amdgcn_readfirstlane(rc);
-        wave_lds_sync();
-        result = rc < 0 ? 4 : 1;
+        const uint32_t crc = (uint32_t)(__brevll(B[1]) >> 37) & 0x3FFFu;      // bits 77..90: the CRC is the encoder's own
+        result = compose_record(B[0], B[1], dw0, crc, crc, rec32, lane) < 0 ? 4 : 1;
     }
-    if (lane < 12 && (result == 1 || out32 != in32)) out32[lane] = result == 1 ? rec32[lane] : mine;
+    store_record(out32, in32, rec32, mine, result == 1, lane);
     if (lane == 0) {
         info32[0] = (uint32_t)result | ((uint32_t)nhard << 8) | ((uint32_t)index << 16);
         info32[1] = metric;

@@ -20,12 +20,8 @@
 //     and spreads j over the lanes.  (metric << 13 | index) through one butterfly minimum is the best pattern with the
 //     rule's tie break;
 //   * the best pattern returns to codeword order through the ranks, and the epilogue is the LDPC kernel's: CRC-14 by
-//     linearity, unpack77 on two 64-bit words, the 48-byte record composed in LDS.
-#include "ft8gpu_internal.h"
-#include "ft8_tables.h"
-#include "unpack_dev.h"
-#include "bp_math.h"
-#include <stddef.h>
+//     linearity, unpack77 on two 64-bit words, the 48-byte record composed in LDS (cand_dev.h, as the soft bits).
+#include "cand_dev.h"
 
 namespace {
 
@@ -35,36 +31,14 @@ struct OsdTables {
 };
 
 __device__ OsdTables d_osd;
-__constant__ uint8_t c_osd_gray[8] = { 0, 1, 3, 2, 5, 6, 4, 7 };
 
 constexpr int kRowStride = 7;                          // dwords between reduced rows in LDS (odd: conflict-free per lane)
 constexpr int kOffPerm = 192, kOffRows = 384, kOffCw = kOffRows + kLdpcK * kRowStride + 3, kOffRec = kOffCw + 8;
 constexpr int kOsdLds = kOffRec + 12;
 static_assert(kOffCw % 2 == 0 && kOffRec % 4 == 0, "LDS areas keep their alignment");
 
-__device__ __forceinline__ void wave_lds_sync() {
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-}
-
-__device__ __forceinline__ int wave_sum(int v) {
-#pragma unroll
-    for (int m = 1; m < 64; m <<= 1) v += __shfl_xor(v, m);
-    return __builtin_amdgcn_readfirstlane(v);
-}
-__device__ __forceinline__ uint32_t wave_xor(uint32_t v) {
-#pragma unroll
-    for (int m = 1; m < 64; m <<= 1) v ^= (uint32_t)__shfl_xor((int)v, m);
-    return (uint32_t)__builtin_amdgcn_readfirstlane((int)v);
-}
 __device__ __forceinline__ uint64_t wave_xor64(uint64_t v) {
     return (uint64_t)wave_xor((uint32_t)v) | ((uint64_t)wave_xor((uint32_t)(v >> 32)) << 32);
-}
-__device__ __forceinline__ uint32_t wave_min(uint32_t v) {
-#pragma unroll
-    for (int m = 1; m < 64; m <<= 1) v = min(v, (uint32_t)__shfl_xor((int)v, m));
-    return (uint32_t)__builtin_amdgcn_readfirstlane((int)v);
 }
 __device__ __forceinline__ uint64_t readlane64(uint64_t v, int l) {
     const uint32_t lo = (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)v, l);
@@ -77,15 +51,6 @@ __device__ __forceinline__ void load_row(const uint32_t *rows, int k, uint64_t x
     const uint32_t *p = rows + k * kRowStride;
 #pragma unroll
     for (int j = 0; j < 3; ++j) x[j] = (uint64_t)p[2 * j] | ((uint64_t)p[2 * j + 1] << 32);
-}
-
-// sum of the weights over the set bits of x: weights as eight bit planes
-__device__ __forceinline__ uint32_t metric_of(const uint64_t x[3], const uint64_t (&P)[8][3]) {
-    uint32_t m = 0;
-#pragma unroll
-    for (int b = 0; b < 8; ++b)
-        m += (uint32_t)(__popcll(x[0] & P[b][0]) + __popcll(x[1] & P[b][1]) + __popcll(x[2] & P[b][2])) << b;
-    return m;
 }
 
 constexpr uint32_t kKeyNone = 0xFFFFFFFFu;
@@ -111,72 +76,20 @@ void ft8_osd_kernel(const uint8_t *__restrict__ mag, const ft8gpu_candidate *__r
     uint32_t *info32 = reinterpret_cast<uint32_t *>(info + rec_index);
     static_assert(sizeof(ft8gpu_decode_status) == 48 && sizeof(ft8gpu_osd_info) == 8, "record sizes");
 
-    // ---- which candidates: ok == 0 and ldpc_errors != 0 (status_out may be status_in: read first) -------------------
-    const uint32_t mine = lane < 12 ? in32[lane] : 0u;
-    const uint32_t dw0 = (uint32_t)__builtin_amdgcn_readlane((int)mine, 0);
-    const uint32_t dw2 = (uint32_t)__builtin_amdgcn_readlane((int)mine, 2);
-    const bool attempt = ((dw2 >> 8) & 0xFFu) == 0u && (dw0 & 0xFFFFu) != 0u;
-    if (!attempt) {
-        if (lane < 12 && out32 != in32) out32[lane] = mine;
-        if (lane < 2) info32[lane] = 0u;
+    uint32_t mine, dw0;
+    if (!read_record(in32, lane, mine, dw0)) {                        // does not qualify
+        leave_record(out32, in32, info32, mine, 0u, lane);
         return;
     }
 
     uint32_t *s = s_mem[wave];
-    float *llr = reinterpret_cast<float *>(s);
     uint32_t *perm = s + kOffPerm;
     uint32_t *rows = s + kOffRows;
 
-    const ft8gpu_candidate cand = cands[rec_index];
-
-    // ---- ft8_extract_likelihood, ftx_normalize_logl: the LDPC kernel's arithmetic (decode.hip) ------------------------
-    if (lane < 58) {
-        const int k = lane;
-        const int sym = k + ((k < 29) ? 7 : 14);
-        const int block = cand.time_offset + sym;
-        int l0 = 0, l1 = 0, l2 = 0;
-        if (block >= 0 && block < kNumBlocks) {
-            const int index = ((cand.time_offset * 2 + cand.time_sub) * 2 + cand.freq_sub) * kNumBin + cand.freq_offset;
-            const uint8_t *ps = mag + (size_t)frame * kMagArray + index + sym * kBlockStride;
-            int s2[8];
-#pragma unroll
-            for (int j = 0; j < 8; ++j) s2[j] = ps[c_osd_gray[j]];
-            l0 = max(max(s2[4], s2[5]), max(s2[6], s2[7])) - max(max(s2[0], s2[1]), max(s2[2], s2[3]));
-            l1 = max(max(s2[2], s2[3]), max(s2[6], s2[7])) - max(max(s2[0], s2[1]), max(s2[4], s2[5]));
-            l2 = max(max(s2[1], s2[3]), max(s2[5], s2[7])) - max(max(s2[0], s2[2]), max(s2[4], s2[6]));
-        }
-        llr[3 * k + 0] = (float)l0;
-        llr[3 * k + 1] = (float)l1;
-        llr[3 * k + 2] = (float)l2;
-    }
-    wave_lds_sync();
-
     float cw[3];
     bool has[3];
-    int isum = 0, isum2 = 0;
-#pragma unroll
-    for (int r = 0; r < 3; ++r) {
-        const int n = lane + 64 * r;
-        has[r] = n < kLdpcN;
-        cw[r] = has[r] ? llr[n] : 0.0f;
-        const int v = (int)cw[r];
-        isum += v;
-        isum2 += v * v;
-    }
-    const float sum = (float)wave_sum(isum);
-    const float sum2 = (float)wave_sum(isum2);
-    const float inv_n = 1.0f / 174;
-    const float variance = (sum2 - (sum * sum * inv_n)) * inv_n;
-    const float norm_factor = bpm::llr_norm_factor(variance);
-    bool finite = true;
-#pragma unroll
-    for (int r = 0; r < 3; ++r) {
-        cw[r] = has[r] ? cw[r] * norm_factor : 0.0f;
-        finite = finite && (__float_as_uint(cw[r]) & 0x7F800000u) != 0x7F800000u;
-    }
-    if (!__all(finite)) {                                             // wave-uniform: nothing is searched
-        if (lane < 12 && out32 != in32) out32[lane] = mine;
-        if (lane < 2) info32[lane] = lane == 0 ? 6u : 0u;
+    if (!soft_bits(mag, frame, cands[rec_index], reinterpret_cast<float *>(s), lane, cw, has)) {      // wave-uniform: nothing is searched
+        leave_record(out32, in32, info32, mine, 6u, lane);
         return;
     }
 
@@ -367,45 +280,11 @@ void ft8_osd_kernel(const uint8_t *__restrict__ mag, const ft8gpu_candidate *__r
 
     // ---- judge the best pattern: all-zero, hard errors, CRC, unpack77 -------------------------------------------------
     uint32_t *rec32 = s + kOffRec;
-    char *rec = reinterpret_cast<char *>(rec32);
-    const uint64_t w0 = __brevll(B0);                                 // codeword bits 0..63, MSB first
-    const uint64_t w1 = __brevll(B1) & 0xFFFFFFE000000000ull;         // bits 64..90
     int result;
     if ((B0 | B1 | B2) == 0ull) result = 5;
     else if (nhard > max_hard_errors) result = 2;
-    else {
-        uint32_t c = ((B0 >> lane) & 1ull) ? d_osd.crc_bit[lane] : 0u;
-        if (lane < 13 && ((B1 >> lane) & 1ull)) c ^= d_osd.crc_bit[64 + lane];
-        const uint32_t crc_calc = wave_xor(c);
-        const uint32_t crc_extracted = (uint32_t)(w1 >> 37) & 0x3FFFu;
-        if (crc_extracted != crc_calc) result = 3;
-        else {
-            // the record of a BP success (decode.hip), iters as it was
-            static_assert(offsetof(ft8gpu_decode_status, a91) == 10 && offsetof(ft8gpu_decode_status, text) == 22, "record layout");
-            if (lane < 12) {
-                const uint32_t hi0 = (uint32_t)(w0 >> 32), lo0 = (uint32_t)w0, hi1 = (uint32_t)(w1 >> 32);
-                uint32_t v = 0;
-                if (lane == 0) v = dw0 & 0xFFFF0000u;
-                else if (lane == 1) v = crc_extracted | (crc_calc << 16);
-                else if (lane == 2) v = (__builtin_bswap32(hi0) & 0xFFFFu) << 16;
-                else if (lane == 3) v = (__builtin_bswap32(hi0) >> 16) | (__builtin_bswap32(lo0) << 16);
-                else if (lane == 4) v = (__builtin_bswap32(lo0) >> 16) | (__builtin_bswap32(hi1) << 16);
-                else if (lane == 5) v = __builtin_bswap32(hi1) >> 16;
-                rec32[lane] = v;
-            }
-            wave_lds_sync();
-            int rc = 0;
-            if (lane == 0) {
-                rc = ft8dev::unpack77(w0, w1 & 0xFFF8000000000000ull, rec + offsetof(ft8gpu_decode_status, text));
-                rec[offsetof(ft8gpu_decode_status, unpack_status)] = (char)rc;
-                rec[offsetof(ft8gpu_decode_status, ok)] = 1;
-            }
-            rc = __builtin_amdgcn_readfirstlane(rc);
-            wave_lds_sync();
-            result = rc < 0 ? 4 : 1;
-        }
-    }
-    if (lane < 12 && (result == 1 || out32 != in32)) out32[lane] = result == 1 ? rec32[lane] : mine;
+    else result = compose_success_record(B0, B1, dw0, d_osd.crc_bit, rec32, lane);
+    store_record(out32, in32, rec32, mine, result == 1, lane);
     if (lane == 0) {
         info32[0] = (uint32_t)result | ((uint32_t)nhard << 8) | ((uint32_t)pattern << 16);
         info32[1] = metric;
@@ -442,15 +321,7 @@ hipError_t osd_tables_init(hipStream_t s) {
         }
         for (int j = 0; j < 4; ++j) h.col[c][j] = m[j];
     }
-    for (int i = 0; i < 77; ++i) {
-        // CRC-14, polynomial 0x2757, of the 82-bit message (77 payload bits, five zeros) whose only set bit is i
-        uint32_t rem = 0;
-        for (int bit = 0; bit < 82; ++bit) {
-            if (bit == i) rem ^= 0x2000u;
-            rem = (rem & 0x2000u) ? ((rem << 1) ^ 0x2757u) & 0x3FFFu : (rem << 1) & 0x3FFFu;
-        }
-        h.crc_bit[i] = (uint16_t)rem;
-    }
+    fill_crc_bits(h.crc_bit);
     return hipMemcpyToSymbolAsync(HIP_SYMBOL(d_osd), &h, sizeof(h), 0, hipMemcpyHostToDevice, s);
 }
 
