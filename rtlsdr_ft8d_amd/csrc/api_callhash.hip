@@ -3,11 +3,10 @@
 // plain C in ft8_pack.c).
 //
 // A receiver is sequential in its slots and independent of every other receiver, so work is cut along exactly those two
-// lines: whole receivers (all their slots) while a receiver fits into max_frames frames, else runs of consecutive slots of
-// one receiver, each run starting from the state the previous one left.  Either cut leaves the bytes of one launch.  The host
-// form stages a piece through for_each_chunk with a receiver as its unit; records and counts use the staging buffers of the
-// messages path, the resolved records and the states (80 KB each) the context's growable RX staging buffers, which no other
-// entry uses while this one holds the context's mutex.
+// lines (Pieces, ft8gpu_ctx.h), each run of slots starting from the state the previous one left.  Either cut leaves the bytes of
+// one launch.  The host form stages a piece through for_each_chunk with a receiver as its unit; records and counts use the
+// staging buffers of the messages path, the resolved records and the states (80 KB each) the context's RX buffers
+// (ensure_rx_scratch).
 #include "callhash.h"
 #include "ft8gpu_ctx.h"
 
@@ -32,38 +31,22 @@ int ft8gpu_resolve_calls(ft8gpu_ctx *c, const ft8gpu_message *msgs, const int32_
     if (dev && (((uintptr_t)msgs | (uintptr_t)state | (uintptr_t)resolved) & 15) != 0)
         return ft8_fail("msgs, state and resolved must be 16-byte aligned");
     if (dev && ((uintptr_t)n_msgs & 3) != 0) return ft8_fail("n_msgs must be 4-byte aligned");
-    // a piece: rg receivers with all their slots, or one receiver with ns of its slots.  The device form needs no staging,
-    // so nothing bounds a piece there.
-    const int mf = c->max_frames;
-    const int ns_max = dev || nslots <= mf ? nslots : mf;
-    const int rg_max = dev ? nstreams : (nslots <= mf ? mf / nslots : 1);
-    if (!dev) {
-        const size_t piece = (size_t)rg_max * ns_max;
-        const size_t res_bytes = piece * kMaxMessages * sizeof(ft8gpu_resolved), state_bytes = (size_t)rg_max * sizeof(ft8gpu_callhash_state);
-        if (res_bytes > c->rx_iq_cap || state_bytes > c->rx_p2_cap) HIP_TRY(hipStreamSynchronize(c->stream));
-        if (grow_buffer((void **)&c->d_rx_iq, &c->rx_iq_cap, res_bytes)) return -1;
-        if (grow_buffer(&c->d_rx_p2, &c->rx_p2_cap, state_bytes)) return -1;
-        if (!c->d_msgs) HIP_TRY(hipMalloc(&c->d_msgs, (size_t)mf * kMaxMessages * sizeof(ft8gpu_message)));
-    }
-    for (int r0 = 0; r0 < nstreams; r0 += rg_max) {
-        const int rg = nstreams - r0 < rg_max ? nstreams - r0 : rg_max;
-        for (int s0 = 0; s0 < nslots; s0 += ns_max) {
-            const int ns = nslots - s0 < ns_max ? nslots - s0 : ns_max;      // ns < nslots only with rg == 1
-            const size_t f0 = (size_t)r0 * nslots + s0;
-            // slots at and above a frame's count keep the caller's bytes (resolved is uploaded in the host form)
-            const StageArg a[] = { { msgs + f0 * kMaxMessages, c->d_msgs, (size_t)ns * kMaxMessages * sizeof(ft8gpu_message), kIn },
-                                   { n_msgs + f0, c->d_nres, (size_t)ns * sizeof(int32_t), kIn },
-                                   { state + r0, c->d_rx_p2, sizeof(ft8gpu_callhash_state), kInOut },
-                                   { resolved + f0 * kMaxMessages, c->d_rx_iq, (size_t)ns * kMaxMessages * sizeof(ft8gpu_resolved), kInOut } };
-            const int rc = for_each_chunk(c, rg, flags & FT8GPU_DEVICE_PTRS, a, [&](int n, void *const *p) {
-                HIP_TRY(launch_callhash((const ft8gpu_message *)p[0], (const int32_t *)p[1], n, ns, (ft8gpu_callhash_state *)p[2],
-                                        max_age, (ft8gpu_resolved *)p[3], c->stream));
-                return 0;
-            });
-            if (rc) return rc;
-        }
-    }
-    return 0;
+    const Pieces cut(nstreams, nslots, dev ? kNoBound : c->max_frames);      // the device form needs no staging: nothing bounds a piece
+    if (!dev && (ensure_rx_scratch(c, 0, (size_t)cut.rg_max * sizeof(ft8gpu_callhash_state),
+                                   (size_t)cut.rg_max * cut.ns_max * kMaxMessages * sizeof(ft8gpu_resolved), 0) || ensure_msgs_staging(c)))
+        return -1;
+    return cut.each([&](int r0, int rg, int, int ns, size_t f0) {
+        // slots at and above a frame's count keep the caller's bytes (resolved is uploaded in the host form)
+        const StageArg a[] = { { msgs + f0 * kMaxMessages, c->d_msgs, (size_t)ns * kMaxMessages * sizeof(ft8gpu_message), kIn },
+                               { n_msgs + f0, c->d_nres, (size_t)ns * sizeof(int32_t), kIn },
+                               { state + r0, c->d_rx_p2, sizeof(ft8gpu_callhash_state), kInOut },
+                               { resolved + f0 * kMaxMessages, c->d_rx_iq, (size_t)ns * kMaxMessages * sizeof(ft8gpu_resolved), kInOut } };
+        return for_each_chunk(c, rg, flags & FT8GPU_DEVICE_PTRS, a, [&](int n, void *const *p) {
+            HIP_TRY(launch_callhash((const ft8gpu_message *)p[0], (const int32_t *)p[1], n, ns, (ft8gpu_callhash_state *)p[2],
+                                    max_age, (ft8gpu_resolved *)p[3], c->stream));
+            return 0;
+        });
+    });
 }
 
 int ft8gpu_decode_messages_resolved(ft8gpu_ctx *c, const float *iq, int nstreams, int nslots, const ft8gpu_ap_params *ap_params,

@@ -2,20 +2,17 @@
 // and the whole path ft8gpu_decode_messages_combined (DESIGN.md "Soft-bit memory"; the kernels are combine.hip, the reset
 // of a state is plain C in ft8_pack.c).
 //
-// Buffers.  As for the expected messages, everything this file needs beyond the messages path lives in the context's
-// growable RX buffers, which no other entry uses while this one holds the context's mutex: the update kernel's read-only
-// copy of the entry states (rx_sums), the host form's staging of the states (rx_p2) and of status_out (rx_iq), the info
-// records (rx_raw).  A state is 92 176 bytes, so a call over n receivers needs n of them once or twice; they grow on the
-// first call that needs them.
+// Buffers.  As for the expected messages, everything this file needs beyond the messages path lives in the context's RX
+// buffers (ensure_rx_scratch): the update kernel's read-only copy of the entry states (rx_sums), the host form's staging of the
+// states (rx_p2) and of status_out (rx_iq), the info records (rx_raw).  A state is 92 176 bytes, so a call over n receivers
+// needs n of them once or twice; they grow on the first call that needs them.
 //
 // Update.  The rule forms every sum from the state as it was at entry to the slot, while the ring may overwrite a partner in
 // the same slot.  The kernel therefore never reads what it writes: the states are copied (device to device), the kernel reads
 // the copy and writes the entries it stores, cursor and slot into the states themselves.
 //
-// The whole path cuts its [nstreams][nslots] frames exactly as ft8gpu_decode_messages_expected does (api_match.hip): whole
-// receivers while a receiver fits into max_frames frames, else runs of consecutive slots of one receiver; a piece is gathered
-// slot-major so that the slot-by-slot part -- combine, append, update, each one frame per receiver wide -- works on
-// contiguous frames.
+// The whole path is the slot-major one of api_match.hip (decode_messages_slot_major) with combine, append, update as the
+// slot-by-slot part.
 #include "combine.h"
 #include "ft8gpu_ctx.h"
 
@@ -30,34 +27,13 @@ int check_combine_args(int min_agree, int store_per_slot) {
     return 0;
 }
 
-// the kernels' constant tables, once per device and process (the context object has no field for them)
+// the kernels' constant tables, on the context's first call
 int ensure_combine_tables(ft8gpu_ctx *c) {
-    static std::mutex mu;
-    static bool done[64];
-    std::lock_guard<std::mutex> lock(mu);
-    const bool known = c->device >= 0 && c->device < 64;
-    if (known && done[c->device]) return 0;
+    if (c->combine_tables) return 0;
     HIP_TRY(combine_tables_init(c->stream));
     HIP_TRY(hipStreamSynchronize(c->stream));                       // the upload reads a static host object
-    if (known) done[c->device] = true;
+    c->combine_tables = true;
     return 0;
-}
-
-// the context's RX buffers as scratch of at least these sizes (0: not needed)
-int ensure_combine_buffers(ft8gpu_ctx *c, size_t copies, size_t states, size_t status, size_t info) {
-    if (copies > c->rx_sums_cap || states > c->rx_p2_cap || status > c->rx_iq_cap || info > c->rx_raw_cap)
-        HIP_TRY(hipStreamSynchronize(c->stream));                   // the old buffers may still be in use
-    if (grow_buffer(&c->d_rx_sums, &c->rx_sums_cap, copies)) return -1;
-    if (grow_buffer(&c->d_rx_p2, &c->rx_p2_cap, states)) return -1;
-    if (grow_buffer((void **)&c->d_rx_iq, &c->rx_iq_cap, status)) return -1;
-    if (grow_buffer((void **)&c->d_rx_raw, &c->rx_raw_cap, info)) return -1;
-    return 0;
-}
-
-// rows of `width` bytes between two arrays with different strides (host or device on either side)
-hipError_t copy_rows(void *dst, size_t dpitch, const void *src, size_t spitch, size_t width, int rows, hipStream_t s) {
-    if (rows == 1 || (dpitch == width && spitch == width)) return hipMemcpyAsync(dst, src, width * rows, hipMemcpyDefault, s);
-    return hipMemcpy2DAsync(dst, dpitch, src, spitch, width, (size_t)rows, hipMemcpyDefault, s);
 }
 
 // one slot of n receivers: states (device memory) in-out, through the read-only copy in the context's buffer
@@ -87,8 +63,8 @@ int ft8gpu_combine_candidates(ft8gpu_ctx *c, const uint8_t *mag, const ft8gpu_ca
     if (ensure_messages_buffers(c) || ensure_combine_tables(c)) return -1;
     const int mc = c->params.max_candidates;
     const size_t piece = (size_t)(nframes < c->max_frames ? nframes : c->max_frames);
-    if (ensure_combine_buffers(c, 0, dev ? 0 : piece * kStateBytes, dev ? 0 : piece * mc * sizeof(ft8gpu_decode_status),
-                               dev ? 0 : piece * mc * sizeof(ft8gpu_combine_info)))
+    if (ensure_rx_scratch(c, 0, dev ? 0 : piece * kStateBytes, dev ? 0 : piece * mc * sizeof(ft8gpu_decode_status),
+                          dev ? 0 : piece * mc * sizeof(ft8gpu_combine_info)))
         return -1;
     // records at and behind a frame's count keep the caller's bytes (both outputs are uploaded in the host form)
     const StageArg a[] = { { mag, c->d_mag, kMagArray, kIn }, { cands, c->d_cands, mc * sizeof(ft8gpu_candidate), kIn },
@@ -117,8 +93,7 @@ int ft8gpu_softmem_update(ft8gpu_ctx *c, const uint8_t *mag, const ft8gpu_candid
     if (dev && ((uintptr_t)states & 15) != 0) return ft8_fail("states must be 16-byte aligned");
     const int mc = c->params.max_candidates;
     const size_t piece = (size_t)(nframes < c->max_frames ? nframes : c->max_frames);
-    if (ensure_combine_buffers(c, piece * kStateBytes, dev ? 0 : piece * kStateBytes, 0,
-                               dev ? 0 : piece * mc * sizeof(ft8gpu_combine_info)))
+    if (ensure_rx_scratch(c, piece * kStateBytes, dev ? 0 : piece * kStateBytes, 0, dev ? 0 : piece * mc * sizeof(ft8gpu_combine_info)))
         return -1;
     const StageArg a[] = { { mag, c->d_mag, kMagArray, kIn }, { cands, c->d_cands, mc * sizeof(ft8gpu_candidate), kIn },
                            { counts, c->d_counts, sizeof(int32_t), kIn },
@@ -147,70 +122,25 @@ int ft8gpu_decode_messages_combined(ft8gpu_ctx *c, const float *iq, int nstreams
     const bool dev = flags & FT8GPU_DEVICE_PTRS;
     if (dev && (((uintptr_t)msgs | (uintptr_t)state | (uintptr_t)iq) & 15) != 0) return ft8_fail("iq, msgs and state must be 16-byte aligned");
     if (ensure_messages_buffers(c) || ensure_combine_tables(c)) return -1;
-    const int mf = c->max_frames, mc = c->params.max_candidates;
-    const size_t F = 2 * (size_t)kNSamples * sizeof(float), M = kMaxMessages * sizeof(ft8gpu_message);
-    if (!c->d_iq) HIP_TRY(hipMalloc(&c->d_iq, (size_t)mf * F));
-    if (!c->d_msgs) HIP_TRY(hipMalloc(&c->d_msgs, (size_t)mf * M));
-    if (!c->d_nbs) HIP_TRY(hipMalloc(&c->d_nbs, (size_t)mf * FT8GPU_MAX_PASSES * 2 * sizeof(int32_t)));
-    const int ns_max = nslots <= mf ? nslots : mf;
-    const int rg_max = nslots <= mf ? (nstreams < mf / nslots ? nstreams : mf / nslots) : 1;
-    if (ensure_combine_buffers(c, (size_t)rg_max * kStateBytes, dev ? 0 : (size_t)rg_max * kStateBytes, 0,
-                               (size_t)rg_max * mc * sizeof(ft8gpu_combine_info)))
+    const int mc = c->params.max_candidates, rg_max = Pieces(nstreams, nslots, c->max_frames).rg_max;
+    if (ensure_rx_scratch(c, (size_t)rg_max * kStateBytes, dev ? 0 : (size_t)rg_max * kStateBytes, 0,
+                          (size_t)rg_max * mc * sizeof(ft8gpu_combine_info)))
         return -1;
     const int gate = params->min_agree, store = params->store_per_slot;
     const uint32_t max_age = params->max_age;
     hipStream_t s = c->stream;
-    for (int r0 = 0; r0 < nstreams; r0 += rg_max) {
-        const int rg = nstreams - r0 < rg_max ? nstreams - r0 : rg_max;
-        ft8gpu_softmem_state *st = dev ? state + r0 : (ft8gpu_softmem_state *)c->d_rx_p2;
-        if (!dev) HIP_TRY(hipMemcpyAsync(st, state + r0, (size_t)rg * kStateBytes, hipMemcpyHostToDevice, s));
-        for (int s0 = 0; s0 < nslots; s0 += ns_max) {
-            const int ns = nslots - s0 < ns_max ? nslots - s0 : ns_max;      // ns < nslots only with rg == 1
-            const int nfr = rg * ns;
-            const size_t f0 = (size_t)r0 * nslots + s0;                      // the piece's first frame; receiver r's slot t is f0 + r * nslots + t
-            // A piece whose frames are consecutive in the caller's arrays (one receiver, or one slot per receiver) is slot-major
-            // as it stands: the device form works on the caller's arrays.  Otherwise gather slot-major; slots past a frame's
-            // count keep the caller's bytes, so msgs travels both ways.
-            const bool direct = dev && (rg == 1 || nslots == 1);
-            const float *piq = direct ? iq + f0 * 2 * (size_t)kNSamples : c->d_iq;
-            ft8gpu_message *pm = direct ? msgs + f0 * kMaxMessages : c->d_msgs;
-            int32_t *pn = direct ? n_msgs + f0 : c->d_nres;
-            int32_t *pb = direct && n_by_stage ? n_by_stage + 2 * f0 : c->d_nbs;
-            for (int t = 0; t < ns && !direct; ++t) {
-                HIP_TRY(copy_rows((char *)c->d_iq + (size_t)t * rg * F, F, (const char *)iq + (f0 + t) * F, (size_t)nslots * F, F, rg, s));
-                HIP_TRY(copy_rows((char *)c->d_msgs + (size_t)t * rg * M, M, (const char *)msgs + (f0 + t) * M, (size_t)nslots * M, M, rg, s));
-            }
-            if (run_pipeline_messages(c, piq, nfr, pm, pn)) return -1;
-            HIP_TRY(hipMemcpy2DAsync(pb, 2 * sizeof(int32_t), pn, sizeof(int32_t), sizeof(int32_t), (size_t)nfr, hipMemcpyDeviceToDevice, s));
-            for (int t = 0; t < ns; ++t) {
-                const size_t o = (size_t)t * rg;
-                ft8gpu_decode_status *status = c->d_status + o * mc;
-                ft8gpu_message *dm = pm + o * kMaxMessages;
-                ft8gpu_combine_info *inf = (ft8gpu_combine_info *)c->d_rx_raw;
-                HIP_TRY(launch_combine(c->d_mag + o * kMagArray, c->d_cands + o * mc, c->d_counts + o, status, status, inf, rg, mc, st,
-                                       max_age, gate, c->params.ldpc_iters, force_ieee(c), s));
-                HIP_TRY(launch_append(c->d_mag + o * kMagArray, c->d_base + o * 2 * kNumBin, c->d_cands + o * mc, c->d_counts + o, status,
-                                      c->d_msgtab, nullptr, rg, mc, c->params.min_score, dm, pn + o, s));
-                HIP_TRY(launch_combine_tag(pb + 2 * o, 2, pn + o, rg, dm, s));
-                if (update_slot(c, c->d_mag + o * kMagArray, c->d_cands + o * mc, c->d_counts + o, status, inf, rg, st, store)) return -1;
-            }
-            HIP_TRY(hipMemcpy2DAsync(pb + 1, 2 * sizeof(int32_t), pn, sizeof(int32_t), sizeof(int32_t), (size_t)nfr, hipMemcpyDeviceToDevice, s));
-            for (int t = 0; t < ns && !direct; ++t) {
-                const size_t o = (size_t)t * rg;
-                HIP_TRY(copy_rows((char *)msgs + (f0 + t) * M, (size_t)nslots * M, (const char *)c->d_msgs + o * M, M, M, rg, s));
-                HIP_TRY(copy_rows(n_msgs + f0 + t, (size_t)nslots * sizeof(int32_t), c->d_nres + o, sizeof(int32_t), sizeof(int32_t), rg, s));
-                if (n_by_stage)
-                    HIP_TRY(copy_rows(n_by_stage + 2 * (f0 + t), (size_t)nslots * 2 * sizeof(int32_t), c->d_nbs + 2 * o, 2 * sizeof(int32_t),
-                                      2 * sizeof(int32_t), rg, s));
-            }
-            HIP_TRY(hipStreamSynchronize(s));                                // the staging buffers are free for the next piece
-        }
-        if (!dev) {
-            HIP_TRY(hipMemcpyAsync(state + r0, st, (size_t)rg * kStateBytes, hipMemcpyDeviceToHost, s));
-            HIP_TRY(hipStreamSynchronize(s));
-        }
-    }
-    return 0;
+    return decode_messages_slot_major(c, iq, nstreams, nslots, state, kStateBytes, msgs, n_msgs, n_by_stage, flags,
+                                      [=](size_t o, int rg, void *st, ft8gpu_message *dm, int32_t *pn, int32_t *pb) {
+        ft8gpu_softmem_state *states = (ft8gpu_softmem_state *)st;
+        ft8gpu_decode_status *status = c->d_status + o * mc;
+        ft8gpu_combine_info *inf = (ft8gpu_combine_info *)c->d_rx_raw;
+        HIP_TRY(launch_combine(c->d_mag + o * kMagArray, c->d_cands + o * mc, c->d_counts + o, status, status, inf, rg, mc, states,
+                               max_age, gate, c->params.ldpc_iters, force_ieee(c), s));
+        HIP_TRY(launch_append(c->d_mag + o * kMagArray, c->d_base + o * 2 * kNumBin, c->d_cands + o * mc, c->d_counts + o, status,
+                              c->d_msgtab, nullptr, rg, mc, c->params.min_score, dm, pn, s));
+        HIP_TRY(launch_combine_tag(pb, 2, pn, rg, dm, s));
+        return update_slot(c, c->d_mag + o * kMagArray, c->d_cands + o * mc, c->d_counts + o, status, inf, rg, states, store);
+    });
 }
 
 }  // extern "C"

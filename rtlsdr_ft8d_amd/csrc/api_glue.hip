@@ -1,5 +1,5 @@
-// api_glue.hip -- host glue of the stages either side of the decode path: RX front end (f-1), PSKreporter datagrams
-// (f-4), synthetic frames (f-3).
+// api_glue.hip -- the buffer helpers the host files share (declared in ft8gpu_ctx.h), and the host glue of the stages either
+// side of the decode path: RX front end (f-1), PSKreporter datagrams (f-4), synthetic frames (f-3).
 #include "ft8gpu_ctx.h"
 
 #include <string.h>
@@ -11,6 +11,45 @@ int grow_buffer(void **buf, size_t *cap, size_t need) {
     *cap = 0;
     HIP_TRY(hipMalloc(buf, need));
     *cap = need;
+    return 0;
+}
+
+int ensure_rx_scratch(ft8gpu_ctx *c, size_t sums, size_t p2, size_t iq, size_t raw) {
+    if (sums > c->rx_sums_cap || p2 > c->rx_p2_cap || iq > c->rx_iq_cap || raw > c->rx_raw_cap)
+        HIP_TRY(hipStreamSynchronize(c->stream));                   // the old buffers may still be in use
+    if (grow_buffer(&c->d_rx_sums, &c->rx_sums_cap, sums)) return -1;
+    if (grow_buffer(&c->d_rx_p2, &c->rx_p2_cap, p2)) return -1;
+    if (grow_buffer((void **)&c->d_rx_iq, &c->rx_iq_cap, iq)) return -1;
+    if (grow_buffer((void **)&c->d_rx_raw, &c->rx_raw_cap, raw)) return -1;
+    return 0;
+}
+
+int follow_cap(ft8gpu_ctx *c, int *cap, void **a, size_t a_bytes, void **b, size_t b_bytes) {
+    if (*cap >= c->cap_candidates) return 0;
+    HIP_TRY(hipStreamSynchronize(c->stream));                       // the old pair may still be in use
+    if (*a) (void)hipFree(*a);
+    if (*b) (void)hipFree(*b);
+    *a = *b = nullptr;
+    *cap = 0;
+    const size_t records = (size_t)c->max_frames * c->cap_candidates;
+    HIP_TRY(hipMalloc(a, records * a_bytes));
+    HIP_TRY(hipMalloc(b, records * b_bytes));
+    *cap = c->cap_candidates;
+    return 0;
+}
+
+int ensure_msgs_staging(ft8gpu_ctx *c) {
+    if (!c->d_msgs) HIP_TRY(hipMalloc(&c->d_msgs, (size_t)c->max_frames * kMaxMessages * sizeof(ft8gpu_message)));
+    return 0;
+}
+
+int ensure_host_staging(ft8gpu_ctx *c) {
+    if (!c->d_iq) HIP_TRY(hipMalloc(&c->d_iq, (size_t)c->max_frames * 2 * kNSamples * sizeof(float)));
+    return ensure_msgs_staging(c);
+}
+
+int ensure_counts_staging(ft8gpu_ctx *c) {
+    if (!c->d_nbs) HIP_TRY(hipMalloc(&c->d_nbs, (size_t)c->max_frames * FT8GPU_MAX_PASSES * 3 * sizeof(int32_t)));
     return 0;
 }
 

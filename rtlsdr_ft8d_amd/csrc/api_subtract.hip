@@ -50,11 +50,8 @@ int ensure_subtract_buffers(ft8gpu_ctx *c, bool host, bool work, bool info) {
     if ((host || work) && !c->d_sub_x) HIP_TRY(hipMalloc(&c->d_sub_x, mf * kFrameBytes));
     if ((host || work) && !c->d_sub_ref) HIP_TRY(hipMalloc(&c->d_sub_ref, mf * kRefBytes));
     if (work && !c->d_sub_nref) HIP_TRY(hipMalloc(&c->d_sub_nref, mf * sizeof(int32_t)));
-    if (host) {
-        if (!c->d_iq) HIP_TRY(hipMalloc(&c->d_iq, mf * kFrameBytes));
-        if (!c->d_msgs) HIP_TRY(hipMalloc(&c->d_msgs, mf * kMsgBytes));
-        if (info && !c->d_sub_info) HIP_TRY(hipMalloc(&c->d_sub_info, mf * kInfoBytes));
-    }
+    if (host && ensure_host_staging(c)) return -1;
+    if (host && info && !c->d_sub_info) HIP_TRY(hipMalloc(&c->d_sub_info, mf * kInfoBytes));
     return 0;
 }
 
@@ -148,10 +145,10 @@ int ft8gpu_decode_messages_subtracted(ft8gpu_ctx *c, const float *iq, int nframe
     if (dev && (((uintptr_t)iq | (uintptr_t)residual) & 15) != 0) return ft8_fail("iq and residual must be 16-byte aligned");
     if (ensure_multipass_buffers(c)) return -1;
     if (ensure_subtract_buffers(c, !dev, true, false)) return -1;
-    if (!dev && n_by_pass && !c->d_nbp) HIP_TRY(hipMalloc(&c->d_nbp, (size_t)c->max_frames * FT8GPU_MAX_PASSES * sizeof(int32_t)));
+    if (!dev && n_by_pass && ensure_counts_staging(c)) return -1;
     // slots past a frame's count keep the caller's bytes (msgs is uploaded in the host form)
     const StageArg a[] = { { iq, c->d_iq, kFrameBytes, kIn }, { msgs, c->d_msgs, kMsgBytes, kInOut }, { n_msgs, c->d_nres, sizeof(int32_t), kOut },
-                           { n_by_pass, c->d_nbp, (size_t)passes * sizeof(int32_t), kOut }, { residual, c->d_sub_x, kFrameBytes, kOut } };
+                           { n_by_pass, c->d_nbs, (size_t)passes * sizeof(int32_t), kOut }, { residual, c->d_sub_x, kFrameBytes, kOut } };
     return for_each_chunk(c, nframes, flags & FT8GPU_DEVICE_PTRS, a, [&](int n, void *const *p) {
         const float *x = (const float *)p[0];
         float *work = p[4] ? (float *)p[4] : c->d_sub_x;            // the caller's residual is the frame buffer of the passes

@@ -1,8 +1,11 @@
-// ft8gpu_ctx.h -- the context object and the helpers every host-side translation unit of the C ABI shares
-// (api_context.hip, api_pipeline.hip, api_multi.hip, api_stages.hip, api_glue.hip).  Not installed.
+// ft8gpu_ctx.h -- the context object and the helpers every host-side translation unit of the C ABI shares: api_context.hip,
+// api_pipeline.hip, api_multi.hip, api_stages.hip, api_messages.hip, api_multipass.hip, api_osd.hip, api_ap.hip, api_glue.hip,
+// api_rx_stream.hip, api_callhash.hip, api_match.hip, api_combine.hip, api_refine.hip, api_subtract.hip.  Not installed.
 #pragma once
 #include "ft8gpu_internal.h"
 
+#include <functional>
+#include <limits.h>
 #include <mutex>
 #include <stddef.h>
 
@@ -67,19 +70,18 @@ struct ft8gpu_ctx {
     int32_t *d_counts2 = nullptr;
     ft8gpu_decode_status *d_status2 = nullptr;
     int cap2 = 0;
-    int32_t *d_nbp = nullptr;              //   host-pointer staging of the per-pass counts [max_frames][FT8GPU_MAX_PASSES]
+    int32_t *d_nbs = nullptr;              //   staging of n_by_pass / n_by_stage, whatever its width [max_frames][FT8GPU_MAX_PASSES][3]
     bool osd_tables = false;               // OSD, lazily on its first call: the constant tables are uploaded,
     ft8gpu_osd_info *d_osd_info = nullptr; //   the info records [max_frames][osd_cap] and the host form's staging of status_out,
     ft8gpu_decode_status *d_osd_out = nullptr;
     int osd_cap = 0;
-    int32_t *d_nosd = nullptr;             //   the counts before the OSD append [max_frames], host staging of n_by_stage
-    int32_t *d_nbs = nullptr;              //   [max_frames][FT8GPU_MAX_PASSES][2]
+    int32_t *d_nosd = nullptr;             //   the counts before the OSD append [max_frames]
     bool ap_tables = false;                // AP, lazily on its first call: the constant tables are uploaded,
     ft8gpu_ap_info *d_ap_info = nullptr;   //   the info records [max_frames][ap_cap] and the host form's staging of status_out,
     ft8gpu_decode_status *d_ap_out = nullptr;
     int ap_cap = 0;
-    int32_t *d_nap = nullptr;              //   the counts before the AP append [max_frames], host staging of n_by_stage
-    int32_t *d_nbs3 = nullptr;             //   [max_frames][FT8GPU_MAX_PASSES][3]
+    int32_t *d_nap = nullptr;              //   the counts before the AP append [max_frames]
+    bool combine_tables = false;           // soft-bit memory: the constant tables are uploaded (on its first call)
     struct SubTables *d_subtab = nullptr;  // subtraction in the I/Q samples, lazily on its first call: the constant tables,
     uint32_t *d_sub_scratch = nullptr;     //   what the estimate kernel leaves for the apply kernel [sub_frames][50][2560],
     int sub_frames = 0;
@@ -159,6 +161,59 @@ int for_each_chunk(ft8gpu_ctx *c, int nframes, int flags, const StageArg (&a)[N]
     return 0;
 }
 
+// The pieces of [nstreams][nslots] frames that hold at most `bound` frames each: whole receivers (all their slots) while a
+// receiver fits, else runs of consecutive slots of one receiver.  each(fn) calls fn(r0, rg, s0, ns, f0) piece by piece, in the
+// order of the frames: rg receivers from r0, their slots [s0, s0 + ns), first frame f0 = r0 * nslots + s0; ns < nslots only
+// with rg == 1.  fn returns 0 to go on.
+constexpr long long kNoBound = LLONG_MAX;
+struct Pieces {
+    int nstreams, nslots, rg_max, ns_max;
+    Pieces(int nstreams_, int nslots_, long long bound) : nstreams(nstreams_), nslots(nslots_) {
+        const long long fit = bound / nslots;                        // whole receivers per piece
+        ns_max = fit >= 1 ? nslots : (int)bound;
+        rg_max = fit >= 1 ? (int)(fit < nstreams ? fit : nstreams) : 1;
+    }
+    template <class Fn>
+    int each(Fn fn) const {
+        for (int r0 = 0; r0 < nstreams; r0 += rg_max) {
+            const int rg = nstreams - r0 < rg_max ? nstreams - r0 : rg_max;
+            for (int s0 = 0; s0 < nslots; s0 += ns_max) {
+                const int ns = nslots - s0 < ns_max ? nslots - s0 : ns_max;
+                if (const int rc = fn(r0, rg, s0, ns, (size_t)r0 * nslots + s0)) return rc;
+            }
+        }
+        return 0;
+    }
+};
+
+// One chunk of a whole-path call, on the device: n frames, their records so far and, if wanted, their n_by_stage rows of
+// passes * cols counts.
+struct Chunk {
+    ft8gpu_ctx *c;
+    int n, passes, cols;
+    ft8gpu_message *msgs;
+    int32_t *n_msgs, *nbs;
+    // nbs[f][col..] = n_msgs[f]: the count after a stage, carried into the columns of the stages that may not run
+    int counts_to(int col) const {
+        if (nbs) HIP_TRY(launch_pass_counts(n_msgs, nbs, n, passes * cols, col, c->stream));
+        return 0;
+    }
+};
+// One pass of a chunk: its waterfall, candidates, counts and statuses, its slot -> frame map (nullptr: slot f is frame f) and
+// number of slots.  A Rescue runs on the pass's failures, in place; col is the first n_by_stage column of its stages.
+struct PassSet {
+    const uint8_t *mag;
+    const ft8gpu_candidate *cands;
+    const int32_t *counts;
+    ft8gpu_decode_status *status;
+    const int32_t *map;
+    int nslots;
+};
+using Rescue = std::function<int(const Chunk &k, const PassSet &f, int col)>;
+// One slot of a piece of the slot-major whole path: the slot's rg frames start at frame o of the pipeline's buffers; their
+// records dm, counts pn and n_by_stage rows pb ([rg][2], column 0 filled); st: the rg receivers' states (device memory).
+using SlotStages = std::function<int(size_t o, int rg, void *st, ft8gpu_message *dm, int32_t *pn, int32_t *pb)>;
+
 // api_context.hip
 int probe_streams(ft8gpu_ctx *c);             // (re)establishes c->overlap_ok for the current main stream
 // api_pipeline.hip: the whole path on device pointers; all intermediates in the context's HBM buffers
@@ -167,13 +222,22 @@ int run_pipeline(ft8gpu_ctx *c, const float *d_iq, int n, struct decoder_results
 int run_pipeline_messages(ft8gpu_ctx *c, const float *d_iq, int n, ft8gpu_message *d_msgs, int32_t *d_nmsgs);
 // api_messages.hip: allocates d_base / d_msgtab on the first messages call
 int ensure_messages_buffers(ft8gpu_ctx *c);
-// api_multipass.hip: frees the multi-pass buffers (ft8gpu_destroy); allocates them on the first multi-pass call
+// api_multipass.hip: frees the multi-pass buffers and the n_by_stage staging (ft8gpu_destroy); allocates them on the first
+// multi-pass call; the masking whole path behind ft8gpu_decode_messages_passes / _deep / _ap (checked arguments, buffers of
+// the rescue stages in place): pass 1, then masking passes up to `passes`, `rescue` (may be empty) on every pass's failures
 void free_multipass_buffers(ft8gpu_ctx *c);
 int ensure_multipass_buffers(ft8gpu_ctx *c);
-// api_osd.hip: frees the OSD buffers (ft8gpu_destroy); allocates them on the first OSD call; refuses arguments out of range
+int decode_messages_masked(ft8gpu_ctx *c, const float *iq, int nframes, int passes, int cols, ft8gpu_message *msgs, int32_t *n_msgs,
+                           int32_t *n_by_stage, int flags, const Rescue &rescue);
+// api_osd.hip: frees the OSD buffers (ft8gpu_destroy); allocates them on the first OSD call; refuses arguments out of range;
+// the OSD rescue step, whose count goes to column col
 void free_osd_buffers(ft8gpu_ctx *c);
 int ensure_osd_buffers(ft8gpu_ctx *c);
 int check_osd_args(int order, int max_hard_errors);
+int osd_step(const Chunk &k, const PassSet &f, int col, int order, int max_hard_errors);
+// api_match.hip: the slot-major whole path behind ft8gpu_decode_messages_expected / _combined
+int decode_messages_slot_major(ft8gpu_ctx *c, const float *iq, int nstreams, int nslots, void *state, size_t state_bytes,
+                               ft8gpu_message *msgs, int32_t *n_msgs, int32_t *n_by_stage, int flags, const SlotStages &slot);
 // api_ap.hip: frees the AP buffers (ft8gpu_destroy)
 void free_ap_buffers(ft8gpu_ctx *c);
 // api_subtract.hip: frees the subtraction buffers (ft8gpu_destroy)
@@ -184,3 +248,12 @@ constexpr int kIqOnDevice = 2;
 int decode_batch(ft8gpu_ctx *c, const float *iq, int nframes, struct decoder_results *decodes, int32_t *n_results, int flags);
 // api_glue.hip: (re)allocates *buf when `need` exceeds *cap (the caller has synchronised the stream)
 int grow_buffer(void **buf, size_t *cap, size_t need);
+// the context's RX buffers as scratch of at least these sizes (0: not needed); no other entry uses them while this one holds
+// the context's mutex
+int ensure_rx_scratch(ft8gpu_ctx *c, size_t sums, size_t p2, size_t iq, size_t raw);
+// a lazily allocated pair of [max_frames][*cap] records of a_bytes / b_bytes follows cap_candidates when ft8gpu_set_params grows it
+int follow_cap(ft8gpu_ctx *c, int *cap, void **a, size_t a_bytes, void **b, size_t b_bytes);
+// the host form's staging, on the first call that needs it: the records; the frames and the records; the n_by_stage rows
+int ensure_msgs_staging(ft8gpu_ctx *c);
+int ensure_host_staging(ft8gpu_ctx *c);
+int ensure_counts_staging(ft8gpu_ctx *c);
