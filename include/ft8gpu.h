@@ -1010,6 +1010,129 @@ int ft8gpu_subtract_messages(ft8gpu_ctx *ctx, const float *iq, const ft8gpu_mess
 int ft8gpu_decode_messages_subtracted(ft8gpu_ctx *ctx, const float *iq, int nframes, int passes, ft8gpu_message *msgs,
                                       int32_t *n_msgs, int32_t *n_by_pass, float *residual, int flags);
 
+/* ---- demodulation from the I/Q samples: undecoded candidates demodulated again from the frame itself ----------------------------
+ * (DESIGN.md "Demodulation from the I/Q samples"; not in the reference.)  OSD, AP, matching and combining all start from the
+ * soft bits of ft8_extract_likelihood: one byte per waterfall cell in half-decibel steps, a 1024-sample Hann window over
+ * 512-sample symbols, a grid of 256 samples by 3.125 Hz, one symbol at a time.  For a candidate BP has given up on, this stage
+ * goes back to the float samples: a fine Costas sync within the candidate's cell, a matched 512-sample correlation per tone with
+ * a phase that is continuous over the signal, and max-log soft bits over blocks of one, two and three symbols (WSJT-X ft8b's
+ * nsym = 1, 2, 3), each set tried with bp_decode.  This text is the rule; tests/ft8_spec_demod.py restates it in numpy, and the
+ * device output equals the restatement byte for byte.  float32 throughout, one IEEE operation per step, nothing fused, every
+ * phase an exact table index formed in uint32 (4096 divides 2^32, so wrapping is harmless).
+ *
+ * Inputs: the frame x[j] = (I[j], Q[j]), j < 48000, zero for every other j; a candidate with T = 2 * time_offset + time_sub and
+ * F = 2 * freq_offset + freq_sub; w4 of the subtraction rule (ft8gpu_subtract_twiddles).  Complex products are
+ * (a * b) = (ar * br - ai * bi,  ar * bi + ai * br), with b the table entry.
+ * A candidate qualifies as for OSD, AP, matching and combining: ok == 0 and ldpc_errors != 0.  Of a frame's qualifying
+ * candidates, in candidate order, the first max_per_frame are attempted; every other record below counts[f] gets status_out =
+ * status_in and an all-zero info record.
+ * (a) Correlation.  C(m, t; S, k4), the correlation of symbol m (m < 79) of a signal that starts at sample S with tone t at table
+ *     step k4 + 8 t, is formed by 64 lanes l:  n = 512 m + l + 64 a, a < 8;
+ *       y_a = x[S + n] * w4[(k4 * n) mod 4096]                       (the base frequency, phase counted from the signal's start)
+ *       U_t = the sum over a of y_a * exp(-2 pi i t a / 8), as the radix-2 DFT below
+ *       V_t(l) = U_t * w4[(8 t l) mod 4096]
+ *       C = V_t summed over the lanes by the xor butterfly: for mask = 1, 2, 4, 8, 16, 32 in turn, v(l) = v(l) + v(l xor mask)
+ *           for every lane at once, both components (addition commutes, so all lanes end with the same value)
+ *     This is x[S + n] times exp(-2 pi i (k4 + 8 t) n / 4096) because 8 t * (512 m + 64 a + l) = 8 t l + 512 t a modulo 4096.  For
+ *     a CPFSK signal that starts at S with tone 0 at k4, every symbol's correlation at its own tone has the same phase, the
+ *     signal's initial one (8 t * 512 m is a whole number of turns; the subtraction rule's Theta recurrence is the same fact),
+ *     which is what makes sums across symbols coherent.
+ *     DFT, with c = 0.70710677f (0x3F3504F3) and every line one operation per component:
+ *       p_a = y_a + y_(a+4),  q_a = y_a - y_(a+4),  a < 4
+ *       q'_0 = q_0;  q'_1 = ((q_1r + q_1i) * c, (q_1i - q_1r) * c);  q'_2 = (q_2i, -q_2r);
+ *       q'_3 = ((q_3i - q_3r) * c, -((q_3r + q_3i) * c))
+ *       DFT4(v): e0 = v0 + v2, e1 = v0 - v2, o0 = v1 + v3, o1 = v1 - v3;  out0 = e0 + o0,  out1 = (e1r + o1i, e1i - o1r),
+ *                out2 = e0 - o0,  out3 = (e1r - o1i, e1i + o1r)
+ *       U_(2s) = DFT4(p)_s,  U_(2s+1) = DFT4(q')_s
+ * (b) Fine sync.  S(e) = 256 T + FT8GPU_REFINE_LEAD + 32 e.  Psync(e, d) = the sum over the 21 Costas symbols (m = 0..6, 36..42,
+ *     72..78, ascending from +0) of re * re + im * im of C(m, costas[m mod 36]; S(e), 4 F + d).  Time first: e = -4 .. 4 at d = 0;
+ *     e* = the first e in ascending order whose power is strictly greater than every earlier one (-4 when none is).  Then
+ *     frequency: d = -2 .. 2 at e*, d* likewise.  That covers the candidate's own cell, +-128 samples and +-1.5625 Hz.
+ *     psync = Psync(e*, d*); a NaN is stored as 0x7FC00000.  (Every hypothesis is correlated anew from the samples with its own
+ *     phase origin S(e); segment sums on the absolute index, which refine slides over e, would give every e another phase
+ *     reference than Z has and a second definition of C.)
+ * (c) Spectra.  Z[m][t] = C(m, t; S(e*), 4 F + d*), m < 79, t < 8.
+ * (d) Three sets of soft bits, n = 1, 2, 3.  Each half has 29 data symbols, m = 7 + i or 43 + i, i < 29, and is cut from i = 0
+ *     into consecutive blocks of n symbols, the last one shorter (n = 2: 14 pairs and a single; n = 3: 9 triples and a pair).  For
+ *     a block of b symbols m1 .. mb and each of the 8^b tone tuples:  s = Z[m1][t1] + ... + Z[mb][tb], added in symbol order,
+ *     A = sqrtf(sr * sr + si * si), the correctly rounded root.  The 3 b bits of a tuple are the inverse Gray map of each tone,
+ *     MSB first, symbols in order; data symbol i of half h owns codeword bits 87 h + 3 i .. + 2.
+ *       llr[bit] = max(A over the tuples with the bit set) - max(A over the tuples with it clear)
+ *     -- the sign of ft8_extract_likelihood.  Every A is >= +0 or not finite, so the maxima do not depend on an order.  A set
+ *     with an A that is not finite (infinite or NaN) has result 6.  x = ftx_normalize_logl(llr) exactly as the soft-bit memory
+ *     writes it (sum and sum of squares in index order); a non-finite x[i]: result 6.
+ * (e) Decoding.  For the sets named in `sets` (bit n - 1), in ascending n: bp_decode(x, ldpc_iters), bit-exact to the LDPC
+ *     kernel's iteration.  The first failing check names the set's result: 6 non-finite, 7 no codeword within ldpc_iters,
+ *     5 all-zero (kept for the numbering; bp_decode leaves at an all-zero word before it counts), 2 nhard > max_hard_errors
+ *     (nhard = the positions where the codeword differs from x > 0), 3 CRC, 4 unpack77 < 0, else 1 = accepted.  The first accepted
+ *     set ends the candidate; otherwise result is the last attempted set's.  info.set is the set `result` speaks of, info.nhard
+ *     that set's (0 without a codeword).  On acceptance the status record becomes that of a BP success, exactly as OSD, AP,
+ *     matching and combining write it; otherwise it is unchanged. */
+#define FT8GPU_DEMOD_TSTEP     32      /* samples per step of the fine time search */
+#define FT8GPU_DEMOD_TRANGE    4       /* e = -4 .. 4 */
+#define FT8GPU_DEMOD_FRANGE    2       /* d = -2 .. 2, in steps of 0.78125 Hz */
+typedef struct {
+    uint8_t result;          /*  0  0 not attempted, 1 accepted, 2 .. 7 the failing check of `set` */
+    uint8_t set;             /*  1  1 .. 3, or 0 */
+    uint8_t nhard;           /*  2 */
+    int8_t  e_best;          /*  3  e* */
+    int8_t  d_best;          /*  4  d* */
+    uint8_t pad0[3];         /*  5  zero */
+    float   psync;           /*  8  Psync(e*, d*) */
+    uint8_t pad[4];          /* 12  zero */
+} ft8gpu_demod_info;
+typedef struct {
+    int32_t sets;            /* 1 .. 7: bit n - 1 = set n is tried; FT8GPU_DEMOD_SETS is the recommended value */
+    int32_t max_hard_errors; /* 0 .. 174; FT8GPU_DEMOD_MAX_HARD_ERRORS is the recommended value */
+    int32_t max_per_frame;   /* 0 .. max_candidates: the qualifying candidates attempted per frame */
+} ft8gpu_demod_params;
+#ifndef __cplusplus
+_Static_assert(sizeof(ft8gpu_demod_info) == 16 && offsetof(ft8gpu_demod_info, set) == 1 && offsetof(ft8gpu_demod_info, nhard) == 2 &&
+               offsetof(ft8gpu_demod_info, e_best) == 3 && offsetof(ft8gpu_demod_info, d_best) == 4 &&
+               offsetof(ft8gpu_demod_info, pad0) == 5 && offsetof(ft8gpu_demod_info, psync) == 8 &&
+               offsetof(ft8gpu_demod_info, pad) == 12, "ft8gpu_demod_info layout");
+_Static_assert(sizeof(ft8gpu_demod_params) == 12 && offsetof(ft8gpu_demod_params, max_hard_errors) == 4 &&
+               offsetof(ft8gpu_demod_params, max_per_frame) == 8, "ft8gpu_demod_params layout");
+#else
+static_assert(sizeof(ft8gpu_demod_info) == 16 && offsetof(ft8gpu_demod_info, set) == 1 && offsetof(ft8gpu_demod_info, nhard) == 2 &&
+              offsetof(ft8gpu_demod_info, e_best) == 3 && offsetof(ft8gpu_demod_info, d_best) == 4 &&
+              offsetof(ft8gpu_demod_info, pad0) == 5 && offsetof(ft8gpu_demod_info, psync) == 8 &&
+              offsetof(ft8gpu_demod_info, pad) == 12, "ft8gpu_demod_info layout");
+static_assert(sizeof(ft8gpu_demod_params) == 12 && offsetof(ft8gpu_demod_params, max_hard_errors) == 4 &&
+              offsetof(ft8gpu_demod_params, max_per_frame) == 8, "ft8gpu_demod_params layout");
+#endif
+/* Recommended values, from profiles/demod_gain.json (tools/demod_gain.py, on the CPU with the oracle's stages and the
+ * restatement: the 96 CQ frames of 20 stations at -22 .. 0 dB of the OSD, AP and match figures, where BP alone decodes 1046 of
+ * the 1920 planted messages and leaves 7119 failing candidates; one station per frame at -24 .. -16 dB in steps of 1 dB, 64
+ * frames each, start and frequency off the grid; 96 frames of noise; gates 20, 25, 30, 36, 40, 45, 50, 60, 174; every mask).
+ * max_hard_errors: no row accepts a message that was not on the air at any gate under any mask, and a gate only costs messages
+ * (107, 119, 120 gained on the CQ frames at 20, 25, 30 and 120 from there to 174: a word BP converges to lies within 30
+ * positions of its soft bits), so the largest swept gate, 174 -- no gate -- is the recommended one.  What keeps a wrong word out is BP itself with the CRC and unpack77 behind
+ * it; on noise (942 failing candidates) nothing is accepted.
+ * sets: the CQ frames gain 63, 93, 99 with set 1, 2, 3 alone, 99, 110, 116 with masks 3, 5, 6 and 120 with all three; the
+ * smallest mask within 2 % of 120 is 7.  Sets 2 and 3 are not idle: the coherent blocks gain half as much again as set 1.
+ * One station per frame, decoded fraction BP / set 1 / set 2 / set 3 / all: -21 dB 0 / .03 / .16 / .14 / .16; -20 dB .09 /
+ * .28 / .52 / .56 / .64; -19 dB .23 / .80 / .78 / .72 / .88; -18 dB .77 / 1 / 1 / .98 / 1; all 1 from -17 dB, all 0 to -23 dB
+ * but for one of 64 at -22 dB with set 3: the half-decode point moves from about -18.5 dB to about -20.2 dB. */
+#define FT8GPU_DEMOD_MAX_HARD_ERRORS 174
+#define FT8GPU_DEMOD_SETS 7
+/* stage entry: iq [nframes][2][48000], cands / status_in / status_out / info [nframes][max_candidates], counts [nframes]; host
+ * or device pointers by `flags` (device form: iq 16-byte aligned).  ldpc_iters is the context's.  Records below counts[f] are
+ * written, records at and behind it are not touched.  status_out may be status_in.  Any candidate gives defined output. */
+int ft8gpu_demod_candidates(ft8gpu_ctx *ctx, const float *iq, const ft8gpu_candidate *cands, const int32_t *counts,
+                            const ft8gpu_decode_status *status_in, int nframes, const ft8gpu_demod_params *params,
+                            ft8gpu_decode_status *status_out, ft8gpu_demod_info *info, int flags);
+/* The whole path over iq [nframes][2][48000]:
+ *   1. the records [0, n1) are byte for byte those of ft8gpu_decode_messages;
+ *   2. ft8gpu_demod_candidates runs in place on the frame's BP status records;
+ *   3. the append step of the multi-pass path adds, in candidate order, every unique gained message not yet among the frame's
+ *      records, up to 50 in all; pad[3] of such a record is the accepted set (1 .. 3).
+ * n_by_stage [nframes][2] (NULL: not written): the count after BP and after the stage.  Host or device pointers by `flags`
+ * (device form: iq and msgs 16-byte aligned), chunked by max_frames.  Not composed with multi-pass, OSD, AP, matching or
+ * combining: feeding these soft bits to those stages is left to a later change. */
+int ft8gpu_decode_messages_demod(ft8gpu_ctx *ctx, const float *iq, int nframes, const ft8gpu_demod_params *params,
+                                 ft8gpu_message *msgs, int32_t *n_msgs, int32_t *n_by_stage, int flags);
+
 /* ---- tooling: encoder + synthetic frames (pack77 / ft8_encode / CPFSK synth of
  *      decoderSelfTest, rtlsdr_ft8d.c:924-955) --------------------------------------------- */
 /* Message text -> 77 bits in 10 bytes (pack77, :927); 0 = ok, -1 = the text fits no message type.  Tokens are separated

@@ -83,6 +83,12 @@ SUBTRACT_INFO_DTYPE = np.dtype([("k4", "<i4"), ("s_best", "<i4"), ("d_best", "i1
 SUBTRACT_TABLE = 4096            # FT8GPU_SUBTRACT_TABLE
 assert SUBTRACT_INFO_DTYPE.itemsize == 64
 assert SOFTMEM_ENTRY_DTYPE.itemsize == 720 and SOFTMEM_STATE_DTYPE.itemsize == 92176 and COMBINE_INFO_DTYPE.itemsize == 8
+# demodulation from the I/Q samples (ft8gpu_demod_candidates): what the second demodulation found for a candidate
+DEMOD_INFO_DTYPE = np.dtype([("result", "u1"), ("set", "u1"), ("nhard", "u1"), ("e_best", "i1"), ("d_best", "i1"), ("pad0", "u1", (3,)),
+                             ("psync", "<f4"), ("pad", "u1", (4,))])
+DEMOD_MAX_HARD_ERRORS = 174      # FT8GPU_DEMOD_MAX_HARD_ERRORS, the recommended gate
+DEMOD_SETS = 7                   # FT8GPU_DEMOD_SETS, the recommended mask of soft-bit sets
+assert DEMOD_INFO_DTYPE.itemsize == 16
 
 
 class Params(C.Structure):
@@ -114,6 +120,11 @@ class ExpectParams(C.Structure):
 class CombineParams(C.Structure):
     """ft8gpu_combine_params: min_agree 0..174, max_age in slots (0: never expires), store_per_slot 0..128"""
     _fields_ = [("min_agree", C.c_int32), ("max_age", C.c_uint32), ("store_per_slot", C.c_int32)]
+
+
+class DemodParams(C.Structure):
+    """ft8gpu_demod_params: sets 1..7 (bit n - 1: set n), max_hard_errors 0..174, max_per_frame 0..max_candidates"""
+    _fields_ = [("sets", C.c_int32), ("max_hard_errors", C.c_int32), ("max_per_frame", C.c_int32)]
 
 
 class Timings(C.Structure):
@@ -162,6 +173,7 @@ ABI_SYMBOLS = [
     "ft8gpu_combine_candidates", "ft8gpu_softmem_update", "ft8gpu_decode_messages_combined", "ft8gpu_softmem_reset",
     "ft8gpu_refine_messages", "ft8gpu_decode_messages_refined", "ft8gpu_refined_estimate", "ft8gpu_format_messages_refined",
     "ft8gpu_subtract_messages", "ft8gpu_decode_messages_subtracted", "ft8gpu_subtract_twiddles",
+    "ft8gpu_demod_candidates", "ft8gpu_decode_messages_demod",
     "ft8_find_sync", "ft8_decode", "ft8_encode", "pack77",            # ft8_lib level (include/ft8_lib/ft8/*.h)
     "initFFTW", "freeFFTW", "ft8_subsystem", "ft8gpu_read_raw_iq", "ft8gpu_read_c2", "ft8gpu_write_raw_iq",
 ]
@@ -323,6 +335,9 @@ def _declare(L):
         L.ft8gpu_decode_messages_combined.argtypes = [vp, vp, C.c_int, C.c_int, vp, C.POINTER(CombineParams), vp, vp, vp, C.c_int]
         L.ft8gpu_softmem_reset.argtypes = [vp]
         L.ft8gpu_softmem_reset.restype = None
+    if hasattr(L, "ft8gpu_demod_candidates"):             # absent from older builds loaded by load_library_at
+        L.ft8gpu_demod_candidates.argtypes = [vp, vp, vp, vp, vp, C.c_int, C.POINTER(DemodParams), vp, vp, C.c_int]
+        L.ft8gpu_decode_messages_demod.argtypes = [vp, vp, C.c_int, C.POINTER(DemodParams), vp, vp, vp, C.c_int]
     if hasattr(L, "ft8gpu_refine_messages"):              # absent from older builds loaded by load_library_at
         L.ft8gpu_refine_messages.argtypes = [vp, vp, vp, vp, C.c_int, vp, C.c_int]
         L.ft8gpu_decode_messages_refined.argtypes = [vp, vp, C.c_int, vp, vp, vp, C.c_int]
@@ -1046,6 +1061,53 @@ class Decoder:
         self._ck(self.lib.ft8gpu_decode_messages_combined(self.h, _ptr(iq_dev), nstreams, nslots, _ptr(state_dev), C.byref(p),
                                                           _ptr(msgs_dev), _ptr(n_msgs_dev),
                                                           None if n_by_stage_dev is None else _ptr(n_by_stage_dev), DEVICE_PTRS))
+
+    def demod_candidates(self, iq, cands, counts, status_in, sets=DEMOD_SETS, max_hard_errors=DEMOD_MAX_HARD_ERRORS,
+                         max_per_frame=None, status_out=None, info=None):
+        """ft8gpu_demod_candidates -> (status_out [B][cap] STATUS_DTYPE, info [B][cap] DEMOD_INFO_DTYPE), new arrays; records at
+        and behind counts[f] keep what status_out / info held (zeros when None).  max_per_frame None: max_candidates"""
+        iq = np.ascontiguousarray(iq, np.float32).reshape(-1, 2, NSAMPLES)
+        B = iq.shape[0]
+        cands = np.ascontiguousarray(cands)
+        counts = np.ascontiguousarray(counts, np.int32)
+        status_in = np.ascontiguousarray(status_in).view(np.uint8).reshape(B, self.max_candidates, 48)
+        assert cands.shape == (B, self.max_candidates) and cands.dtype == CAND_DTYPE and counts.shape == (B,)
+        out = np.zeros((B, self.max_candidates, 48), np.uint8) if status_out is None else \
+            np.array(status_out, copy=True, order="C").view(np.uint8).reshape(B, self.max_candidates, 48)
+        inf = np.zeros((B, self.max_candidates), DEMOD_INFO_DTYPE) if info is None else \
+            np.array(info, copy=True, order="C").view(DEMOD_INFO_DTYPE).reshape(B, self.max_candidates)
+        p = DemodParams(int(sets), int(max_hard_errors), int(self.max_candidates if max_per_frame is None else max_per_frame))
+        self._ck(self.lib.ft8gpu_demod_candidates(self.h, iq.ctypes.data, cands.ctypes.data, counts.ctypes.data, status_in.ctypes.data,
+                                                  B, C.byref(p), out.ctypes.data, inf.ctypes.data, HOST_PTRS))
+        return out.view(STATUS_DTYPE).reshape(B, self.max_candidates), inf
+
+    def demod_candidates_dev(self, iq_dev, cands_dev, counts_dev, status_in_dev, nframes, sets, max_hard_errors, max_per_frame,
+                             status_out_dev, info_dev):
+        """status_out_dev may be status_in_dev; iq_dev 16-byte aligned; info_dev: 16-byte records"""
+        p = DemodParams(int(sets), int(max_hard_errors), int(max_per_frame))
+        self._ck(self.lib.ft8gpu_demod_candidates(self.h, _ptr(iq_dev), _ptr(cands_dev), _ptr(counts_dev), _ptr(status_in_dev), int(nframes),
+                                                  C.byref(p), _ptr(status_out_dev), _ptr(info_dev), DEVICE_PTRS))
+
+    def decode_messages_demod(self, iq, sets=DEMOD_SETS, max_hard_errors=DEMOD_MAX_HARD_ERRORS, max_per_frame=None, msgs=None):
+        """ft8gpu_decode_messages_demod -> (msgs [B][50], n_msgs [B], n_by_stage [B][2]: the count after BP and after the second
+        demodulation); pad[3] of a record the stage gained is the accepted set"""
+        iq = np.ascontiguousarray(iq, np.float32).reshape(-1, 2, NSAMPLES)
+        B = iq.shape[0]
+        if msgs is None:
+            msgs = np.zeros((B, MAX_MESSAGES), MESSAGE_DTYPE)
+        assert msgs.dtype == MESSAGE_DTYPE and msgs.shape == (B, MAX_MESSAGES) and msgs.flags["C_CONTIGUOUS"]
+        n = np.zeros(B, np.int32)
+        nbs = np.zeros((B, 2), np.int32)
+        p = DemodParams(int(sets), int(max_hard_errors), int(self.max_candidates if max_per_frame is None else max_per_frame))
+        self._ck(self.lib.ft8gpu_decode_messages_demod(self.h, iq.ctypes.data, B, C.byref(p), msgs.ctypes.data, n.ctypes.data,
+                                                       nbs.ctypes.data, HOST_PTRS))
+        return msgs, n, nbs
+
+    def decode_messages_demod_dev(self, iq_dev, nframes, sets, max_hard_errors, max_per_frame, msgs_dev, n_msgs_dev, n_by_stage_dev=None):
+        """the same with every array in HBM (iq and msgs 16-byte aligned); n_by_stage_dev: [nframes][2] or None"""
+        p = DemodParams(int(sets), int(max_hard_errors), int(max_per_frame))
+        self._ck(self.lib.ft8gpu_decode_messages_demod(self.h, _ptr(iq_dev), int(nframes), C.byref(p), _ptr(msgs_dev), _ptr(n_msgs_dev),
+                                                       None if n_by_stage_dev is None else _ptr(n_by_stage_dev), DEVICE_PTRS))
 
     # ---- device-pointer API (inputs and outputs resident in HBM) --------------------------------
     def refine_messages(self, iq, msgs, n_msgs, refined=None):

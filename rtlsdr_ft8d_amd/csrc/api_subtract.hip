@@ -27,21 +27,7 @@ constexpr int kSubFrames = 256;
 int ensure_subtract_buffers(ft8gpu_ctx *c, bool host, bool work, bool info) {
     if (ensure_messages_buffers(c)) return -1;
     const size_t mf = (size_t)c->max_frames;
-    if (!c->d_subtab) {
-        SubTables *h = (SubTables *)calloc(1, sizeof(SubTables));
-        if (!h) return ft8_fail("out of memory");
-        ft8gpu_subtract_twiddles(&h->w4[0].x);
-        ft8_subtract_inv_table(h->inv);
-        SubTables *d = nullptr;
-        hipError_t e = hipMalloc(&d, sizeof(SubTables));
-        if (e == hipSuccess) e = hipMemcpy(d, h, sizeof(SubTables), hipMemcpyHostToDevice);
-        free(h);
-        if (e != hipSuccess) {
-            if (d) (void)hipFree(d);
-            return ft8_fail("subtraction tables: %s", hipGetErrorString(e));
-        }
-        c->d_subtab = d;
-    }
+    if (ensure_subtract_tables(c)) return -1;
     if (!c->d_sub_scratch) {
         const int sf = c->max_frames < kSubFrames ? c->max_frames : kSubFrames;
         HIP_TRY(hipMalloc(&c->d_sub_scratch, (size_t)sf * kMaxMessages * kSubStride * sizeof(uint32_t)));
@@ -106,6 +92,25 @@ int run_subtracted_passes(ft8gpu_ctx *c, const float *iq, int n, int passes, ft8
 }
 
 }  // namespace
+
+// the constant tables (w4, inv), on the first call that needs them; api_demod.hip reads w4 too
+int ensure_subtract_tables(ft8gpu_ctx *c) {
+    if (c->d_subtab) return 0;
+    SubTables *h = (SubTables *)calloc(1, sizeof(SubTables));
+    if (!h) return ft8_fail("out of memory");
+    ft8gpu_subtract_twiddles(&h->w4[0].x);
+    ft8_subtract_inv_table(h->inv);
+    SubTables *d = nullptr;
+    hipError_t e = hipMalloc(&d, sizeof(SubTables));
+    if (e == hipSuccess) e = hipMemcpy(d, h, sizeof(SubTables), hipMemcpyHostToDevice);
+    free(h);
+    if (e != hipSuccess) {
+        if (d) (void)hipFree(d);
+        return ft8_fail("subtraction tables: %s", hipGetErrorString(e));
+    }
+    c->d_subtab = d;
+    return 0;
+}
 
 void free_subtract_buffers(ft8gpu_ctx *c) {
     void *bufs[] = { c->d_subtab, c->d_sub_scratch, c->d_sub_x, c->d_sub_ref, c->d_sub_info, c->d_sub_nref };

@@ -1,6 +1,6 @@
 // ft8gpu_ctx.h -- the context object and the helpers every host-side translation unit of the C ABI shares: api_context.hip,
 // api_pipeline.hip, api_multi.hip, api_stages.hip, api_messages.hip, api_multipass.hip, api_osd.hip, api_ap.hip, api_glue.hip,
-// api_rx_stream.hip, api_callhash.hip, api_match.hip, api_combine.hip, api_refine.hip, api_subtract.hip.  Not installed.
+// api_rx_stream.hip, api_callhash.hip, api_match.hip, api_combine.hip, api_refine.hip, api_subtract.hip, api_demod.hip.  Not installed.
 #pragma once
 #include "ft8gpu_internal.h"
 
@@ -82,6 +82,7 @@ struct ft8gpu_ctx {
     int ap_cap = 0;
     int32_t *d_nap = nullptr;              //   the counts before the AP append [max_frames]
     bool combine_tables = false;           // soft-bit memory: the constant tables are uploaded (on its first call)
+    bool demod_tables = false;             // demodulation from the I/Q samples: likewise
     struct SubTables *d_subtab = nullptr;  // subtraction in the I/Q samples, lazily on its first call: the constant tables,
     uint32_t *d_sub_scratch = nullptr;     //   what the estimate kernel leaves for the apply kernel [sub_frames][50][2560],
     int sub_frames = 0;
@@ -240,8 +241,10 @@ int decode_messages_slot_major(ft8gpu_ctx *c, const float *iq, int nstreams, int
                                ft8gpu_message *msgs, int32_t *n_msgs, int32_t *n_by_stage, int flags, const SlotStages &slot);
 // api_ap.hip: frees the AP buffers (ft8gpu_destroy)
 void free_ap_buffers(ft8gpu_ctx *c);
-// api_subtract.hip: frees the subtraction buffers (ft8gpu_destroy)
+// api_subtract.hip: frees the subtraction buffers (ft8gpu_destroy); uploads the subtraction's constant tables (d_subtab) on the
+// first call that needs them
 void free_subtract_buffers(ft8gpu_ctx *c);
+int ensure_subtract_tables(ft8gpu_ctx *c);
 // ft8gpu_decode_batch with one more form: kIqOnDevice, frames resident on the context's GPU and records to host arrays
 // (used by the multi-GPU entries; not part of the ABI, whose entry passes on FT8GPU_DEVICE_PTRS only)
 constexpr int kIqOnDevice = 2;
