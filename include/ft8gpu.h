@@ -1063,8 +1063,9 @@ int ft8gpu_decode_messages_subtracted(ft8gpu_ctx *ctx, const float *iq, int nfra
  *     writes it (sum and sum of squares in index order); a non-finite x[i]: result 6.
  * (e) Decoding.  For the sets named in `sets` (bit n - 1), in ascending n: bp_decode(x, ldpc_iters), bit-exact to the LDPC
  *     kernel's iteration.  The first failing check names the set's result: 6 non-finite, 7 no codeword within ldpc_iters,
- *     5 all-zero (kept for the numbering; bp_decode leaves at an all-zero word before it counts), 2 nhard > max_hard_errors
- *     (nhard = the positions where the codeword differs from x > 0), 3 CRC, 4 unpack77 < 0, else 1 = accepted.  The first accepted
+ *     5 all-zero (kept for the numbering and never produced: bp_decode leaves at an all-zero word before it counts, so such a
+ *     word ends in 7), 2 nhard > max_hard_errors (nhard = the positions where the codeword differs from x > 0), 3 CRC,
+ *     4 unpack77 < 0, else 1 = accepted.  The first accepted
  *     set ends the candidate; otherwise result is the last attempted set's.  info.set is the set `result` speaks of, info.nhard
  *     that set's (0 without a codeword).  On acceptance the status record becomes that of a BP success, exactly as OSD, AP,
  *     matching and combining write it; otherwise it is unchanged. */

@@ -229,7 +229,8 @@ def demod_candidates(oracle, iq, cands, counts, status_in, sets=SETS, gate=MAX_H
                      info=None, iters=20, bp=None, w4=None, cache=None):
     """ft8gpu_demod_candidates: iq [B][2][48000], cands [B][cap], counts [B], status_in uint8 [B][cap][48] (or STATUS_DTYPE) ->
     (status_out uint8 [B][cap][48], info INFO_DTYPE [B][cap]).  Records at and behind counts[f] keep what status_out / info held
-    (zeros when None).  cache: a dict that keeps analyse() of (frame, candidate) between calls on the same frames."""
+    (zeros when None).  cache: a dict that keeps analyse() of (frame, candidate bytes) between calls on the same frames with the
+    same iters."""
     import rtlsdr_ft8d_amd as ft8
     iq = np.ascontiguousarray(iq, F32).reshape(-1, 2, NSAMPLES)
     B = iq.shape[0]
@@ -248,7 +249,7 @@ def demod_candidates(oracle, iq, cands, counts, status_in, sets=SETS, gate=MAX_H
             if not (st[f, i]["ok"] == 0 and st[f, i]["ldpc_errors"] != 0) or attempted >= max_per_frame:
                 continue
             attempted += 1
-            key = (f, i, cands[f, i].tobytes())
+            key = (f, cands[f, i].tobytes())                         # the analysis is the frame's and the record's, wherever it stands
             if cache is None or key not in cache:
                 analysis = analyse(iq[f, 0], iq[f, 1], cands[f, i], w4, iters, bp)
                 if cache is not None:

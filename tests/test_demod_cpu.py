@@ -1,16 +1,21 @@
 """CPU tests of the demodulation from the I/Q samples (include/ft8gpu.h "demodulation from the I/Q samples"): the record and
 parameter layouts against gcc, the properties of the restatement tests/ft8_spec_demod.py on noiseless signals that start off
 the grid, the first-strict-maximum rule, frames of zeros and with a NaN, the hand-made inputs of tests/demod_craft.py (which the
-device is held to in tests/test_gpu_demod.py), and a seeded sensitivity row.  No GPU is used here."""
+device is held to in tests/test_gpu_demod.py), the constructed signals and long lists of tests/demod_edges_craft.py, each named
+case asserted by name (results 3 and 4, acceptance by set 2 and set 3, the soft-bit bounds around the division guard, the float
+edges of the powers, extreme records and the frame's edges), and a seeded sensitivity row.  No GPU is used here."""
 import os
 import subprocess
 
 import numpy as np
 import pytest
 
+import combine_craft as cc
 import demod_craft as dc
+import demod_edges_craft as de
 import ft8_spec_combine as sc
 import ft8_spec_demod as sdm
+import ft8_spec_osd as so
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 F32 = np.float32
@@ -153,6 +158,157 @@ def test_hand_made_candidates_are_what_they_are_named_for(oracle, ft8):
         if mpf == 1:
             assert [(inf[f]["set"] != 0).sum() for f in range(4)] == [1, 1, 1, 0]
     assert {0, 1, 2, 6, 7} <= results
+
+
+def test_tones_of_any_codeword_are_the_encoder_s(oracle, ft8):
+    for text in dc.TEXTS:
+        tones, _payload = dc.tones_of(oracle, text)
+        assert (de.tones_of_codeword(cc.codeword_of(text)) == np.asarray(tones)).all(), text
+    word = de.word_with_crc(np.ones(77, np.uint8), flip=0)
+    assert int("".join(map(str, word[77:91])), 2) == so.crc14(word[:77]) ^ 0x2000
+    assert not (so.parity_check_matrix().astype(np.int64) @ word & 1).any()
+
+
+@pytest.fixture(scope="module")
+def edges(oracle, ft8):
+    iq, cands, counts, status, where = de.constructed(ft8, oracle)
+    return dict(iq=iq, cands=cands, counts=counts, status=status, where=where, cache={})
+
+
+def test_constructed_edges_are_what_they_are_named_for(oracle, ft8, edges):
+    """every named case of tests/demod_edges_craft.py, by name, with the restatement and the library's twiddles"""
+    x = edges
+    where, nh = x["where"], x["where"]["nhard"]
+    B = len(x["iq"])
+
+    def run(sets=7, gate=174):
+        st, info = sdm.demod_candidates(oracle, x["iq"], x["cands"], x["counts"], x["status"], sets, gate, bp=oracle.bp_decode, cache=x["cache"])
+        return st.view(ft8.STATUS_DTYPE).reshape(B, -1), info
+
+    def sets_of(name):
+        """what each set gives at gate 174: {n: (result, nhard)} and {n: x}"""
+        _e, _d, _psync, per_set = x["cache"][(where[name][0], x["cands"][where[name]].tobytes())]
+        out = {}
+        for n, (_llr, xs, plain, errors) in per_set.items():
+            out[n] = (6, 0) if xs is None else sdm.judge(oracle, plain, errors, xs, 174)[:2]
+        return out, {n: per_set[n][1] for n in per_set}
+
+    def bits_of(v):
+        return int(np.float32(v).view(np.uint32))
+
+    st7, info7 = run()
+    results = set(int(r) for f in range(B) for r in info7[f, :x["counts"][f]]["result"])
+    accepted = set(int(r["set"]) for f in range(B) for r in info7[f, :x["counts"][f]] if r["result"] == 1)
+    assert all(r["set"] != 0 or name == "does_not_qualify" for name, at in where.items() if name != "nhard" for r in [info7[at]])
+    assert info7[where["does_not_qualify"]].tobytes() == bytes(16)
+
+    # (a) BP converges and a check behind it refuses, whichever sets are tried; the all-zero word is never counted
+    for sets in (1, 2, 4, 7):
+        st, info = run(sets)
+        last = sets.bit_length()
+        for name, code in (("crc_refuses", 3), ("crc_refuses_last", 3), ("unpack_refuses", 4), ("all_zero_word", 7)):
+            r = info[where[name]]
+            assert (r["result"], r["set"], r["nhard"]) == (code, last, 0), (name, sets, r)
+            assert st[where[name]].tobytes() == x["status"][where[name]].tobytes()
+        r = info[where["good_behind_a_refusal"]]
+        assert (r["result"], r["set"], r["nhard"]) == (1, (sets & -sets).bit_length(), 0)
+        assert st[where["good_behind_a_refusal"]]["text"] == dc.TEXTS[1].encode() and st[where["good_behind_a_refusal"]]["ok"] == 1
+        results |= set(int(r) for f in range(B) for r in info[f, :x["counts"][f]]["result"])
+    for name in ("crc_refuses", "crc_refuses_last", "unpack_refuses"):
+        assert [sets_of(name)[0][n][0] for n in (1, 2, 3)] == [3 if "crc" in name else 4] * 3, name
+    assert where["crc_refuses"][0] == where["good_behind_a_refusal"][0] and where["crc_refuses"][1] < where["good_behind_a_refusal"][1]
+
+    # (b) the named set accepts after the sets before it found no codeword; the gate at its nhard and one below
+    per2, per3 = sets_of("set2_accepts")[0], sets_of("set3_accepts")[0]
+    assert (per2[1], per2[2], per2[3]) == ((7, 0), (1, nh["set2_accepts"]), (7, 0))
+    assert (per3[1], per3[2], per3[3]) == ((7, 0), (7, 0), (1, nh["set3_accepts"]))
+    for name, n, after in (("set2_accepts", 2, (7, 3, 0)), ("set3_accepts", 3, (2, 3, nh["set3_accepts"]))):
+        r = info7[where[name]]
+        assert (r["result"], r["set"], r["nhard"]) == (1, n, nh[name]), (name, r)
+        st, info = run(7, nh[name])
+        r = info[where[name]]
+        assert (r["result"], r["set"], r["nhard"]) == (1, n, nh[name]) and st[where[name]]["ok"] == 1, (name, r)
+        st, info = run(7, nh[name] - 1)
+        r = info[where[name]]
+        assert (r["result"], r["set"], r["nhard"]) == after and st[where[name]]["ok"] == 0, (name, r)
+        _st, info = run(1 << (n - 1), nh[name] - 1)
+        assert (info[where[name]]["result"], info[where[name]]["nhard"]) == (2, nh[name])
+        results |= set(int(r) for f in range(B) for r in info[f, :x["counts"][f]]["result"])
+    assert nh["set2_accepts"] >= 1 and nh["set3_accepts"] >= 1
+
+    # (c) set 1's smallest nonzero normalised soft bit against the guard's 2^-58; the symbol's soft bits in sets 2 and 3 are zeros
+    own = slice(3 * sdm.data_index(de.TINY_SYMBOL), 3 * sdm.data_index(de.TINY_SYMBOL) + 3)
+    for name, lo, hi in (("soft_bits_just_above", 2.0 ** -58, 2.0 ** -57), ("tiny_soft_bits", 2.0 ** -59, 2.0 ** -58),
+                         ("tiny_soft_bits_deepest", 2.0 ** -82, 2.0 ** -80), ("tiny_soft_bits_below_tanh_domain", 2.0 ** -126, 2.0 ** -82),
+                         ("subnormal_soft_bit", 2.0 ** -149, 2.0 ** -126)):
+        per, xs = sets_of(name)
+        a = np.abs(xs[1].astype(np.float64))
+        assert (a != 0).all() and lo <= a.min() < hi and a[own].min() == a.min(), (name, a.min())
+        assert np.sort(a)[3] > 1.0, "only the scaled symbol's three soft bits are small"
+        assert (xs[2][own] == 0).all() and (xs[3][own] == 0).all() and (xs[2] != 0).sum() == 171 and (xs[3] != 0).sum() == 171
+        r = info7[where[name]]
+        assert (r["result"], r["set"], r["nhard"], r["e_best"], r["d_best"]) == (1, 1, 0, 0, 0) and per[2][0] == 1 and per[3][0] == 1, name
+
+    # (d) every sample times a power of two
+    def scaled(name):
+        r = info7[where["scaled_" + name]]
+        return int(r["result"]), int(r["e_best"]), int(r["d_best"]), bits_of(r["psync"]), float(r["psync"])
+    res, e, d, bits, p = scaled("accepted_tiny_psync")
+    assert res == 1 and (e, d) == (1, -1) and 0x00800000 <= bits and p < 2.0 ** -100
+    res, e, d, bits, p = scaled("subnormal_psync")
+    assert res == 6 and (e, d) == (1, -1) and 0 < bits < 0x00800000
+    res, e, d, bits, p = scaled("last_nonzero_psync")
+    assert res == 6 and 0 < bits < 0x00000100
+    res, e, d, bits, p = scaled("accepted_top")
+    assert res == 1 and (e, d) == (1, -1) and 2.0 ** 120 < p < np.inf
+    res, e, d, bits, p = scaled("variance_overflows")
+    assert res == 7 and (e, d) == (1, -1) and np.isfinite(p)
+    for n, (llr, xs, _plain, errors) in x["cache"][(where["scaled_variance_overflows"][0], x["cands"][where["scaled_variance_overflows"]].tobytes())][3].items():
+        assert np.isfinite(llr).all() and (np.abs(llr) > 2.0 ** 50).all() and (xs == 0).all() and errors != 0, "finite soft bits, a norm factor of zero"
+    res, e, d, bits, p = scaled("not_finite")
+    assert res == 6 and (e, d) == (1, -1) and np.isfinite(p)
+    res, e, d, bits, p = scaled("inf_psync")
+    assert res == 6 and e > -4 and bits == 0x7F800000
+    res, e, d, bits, p = scaled("nan_psync")
+    assert res == 6 and (e, d) == (-4, -2) and bits == 0x7FC00000
+    f = where["scaled_nan_psync"][0]
+    assert np.isfinite(x["iq"][f]).all(), "the NaN comes from the arithmetic, not from a sample"
+    assert st7[where["scaled_accepted_tiny_psync"]]["text"] == st7[where["scaled_accepted_top"]]["text"] == dc.TEXTS[1].encode()
+
+    # (e) a NaN with a sign and a payload, and -inf beside +inf, inside a Costas symbol: one canonical NaN
+    f, i = where["nan_payload"]
+    assert (x["iq"][f].view(np.uint32) == de.NAN_BITS).sum() == 1
+    for name in ("nan_payload", "inf_beside_minus_inf"):
+        r = info7[where[name]]
+        assert bits_of(r["psync"]) == 0x7FC00000 and (r["e_best"], r["d_best"]) == (-4, -2), (name, r)
+
+    # (f) extreme fields and the frame's edges
+    out_of_reach = [f"field_extremes_{k}" for k in range(len(de.EXTREMES))] + [f"edge_T{T}_fo{fo}" for T in (-160, 187) for fo in (0, 255)]
+    for name in out_of_reach:
+        r = info7[where[name]]
+        assert (r["result"], r["set"], r["e_best"], r["d_best"], bits_of(r["psync"])) == (6, 3, -4, -2, 0), (name, r)
+    for T in (-159, 186):
+        for fo in (0, 255):
+            r = info7[where[f"edge_T{T}_fo{fo}"]]
+            assert r["psync"] > 0 and (r["e_best"] >= 1 if T < 0 else r["e_best"] <= 3), (T, fo, r)      # the e whose window is inside
+    assert [tuple(int(v) for v in x["cands"][where[f"field_extremes_{k}"]].tolist()) for k in range(4)] == [tuple(r) for r in de.EXTREMES]
+
+    assert {0, 1, 2, 3, 4, 6, 7} <= results and 5 not in results and accepted == {1, 2, 3}, (results, accepted)
+
+
+def test_long_lists_are_what_they_are_made_for(ft8):
+    for cap, counts in de.LONG.items():
+        iq, cands, got_counts, status = de.long_lists(ft8, cap)
+        assert tuple(got_counts) == counts and cands.shape == (len(counts), cap)
+        for f, n in enumerate(counts):
+            q = (status[f, :n]["ok"] == 0) & (status[f, :n]["ldpc_errors"] != 0)
+            assert (~q).sum() == n // 3 and not q[2::3].any() and len(set(c.tobytes() for c in cands[f, :n])) <= len(de.LONG_RECORDS)
+            assert (status[f, n:].view(np.uint8) == dc.FILL).all() and (cands[f, n:].view(np.uint8) == dc.FILL).all()
+        assert (status[0]["ok"] == 1).any() and ((status[0]["ok"] == 0) & (status[0]["ldpc_errors"] == 0)).any()
+    iq, cands, counts, status = de.long_lists(ft8, 70)
+    q = np.flatnonzero((status[0]["ok"] == 0) & (status[0]["ldpc_errors"] != 0))
+    assert len(q) == 47 and q[42] == 63 and q[43] == 64, "max_per_frame = 43 ends with the first chunk of 64, 44 begins the second"
+    assert not iq[0].any() and iq[1].any()
 
 
 def test_seeded_sensitivity_row(oracle, ft8, w4):
