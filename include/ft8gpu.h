@@ -876,8 +876,14 @@ void ft8gpu_softmem_reset(ft8gpu_softmem_state *state);
  * greater than every earlier one (-16 when none is).  The range is +-512 samples because the record's candidate is the first
  * that carried the message, not the best one.
  * At e_best:  pf[u + 2] = P(u, e_best), u = -2 .. 2 (pf[2] is pt_all[e_best + 16]);  noise = the same sum with
- * k = F + 2 * ((tone[m] + 4) & 7) in place of k_m: the tone four away, which this message leaves empty in that symbol. */
-#define FT8GPU_REFINE_LEAD     256     /* samples from the first sample of waterfall row T to the symbol it is centred on */
+ * k = F + 2 * ((tone[m] + 4) & 7) in place of k_m: the tone four away, which this message leaves empty in that symbol.
+ * Samples: any float32 values give defined output, infinities and NaNs included.  Subnormal products, sums and powers are kept,
+ * never flushed to zero, and a sum that overflows is the IEEE infinity.  The decisions (e_best, valid, the padding) are exact
+ * for every input.  A comparison with a NaN is false, so a NaN power is never taken as a maximum over an earlier value, and no
+ * later value is taken over a NaN in P(0, -16), where the scan starts (e_best is -16 then).  A float output that is a NaN by
+ * this rule is a NaN in every implementation, with unspecified sign and payload (inf - inf has its sign bit set on x86 and
+ * clear on gfx950); every other output is byte for byte. */
+#define FT8GPU_REFINE_LEAD    256     /* samples from the first sample of waterfall row T to the symbol it is centred on */
 #define FT8GPU_REFINE_STEP     32      /* samples per time-search step */
 #define FT8GPU_REFINE_RANGE    16      /* the search covers e = -16 .. 16 */
 typedef struct {
@@ -961,7 +967,15 @@ int ft8gpu_format_messages_refined(const ft8gpu_message *msgs, const ft8gpu_refi
  *       x'r[j] = x'r[j] - (Ar wr + Ai wi);   x'i[j] = x'i[j] - (Ai wr - Ar wi)                      (A = A_i(q); A conj(w))
  *     Every A_i comes from the INPUT frame, not from a partly subtracted one; only this accumulation is ordered.  Samples
  *     outside every record are copied bit for bit.
- * A record with R.valid == 0 is skipped (its info is all zero); every other cand, a91 and R give defined output. */
+ * A record with R.valid == 0 is skipped (its info is all zero); every other cand, a91 and R give defined output.
+ * Samples: any float32 values give defined output, infinities and NaNs included.  Subnormal products, sums, powers and
+ * amplitudes are kept, never flushed to zero (powers that underflow to +0 under amplitudes that do not: d* = t* = -2 and the
+ * record is still subtracted), and a sum that overflows is the IEEE infinity.  The decisions (u*, k4, s_best, d_best, t_best,
+ * valid, the padding) are exact for every input.  A comparison with a NaN is false, so a NaN is never taken as a maximum over
+ * an earlier value -- in R.pf[2] or R.pf[3], in pf or in pt -- and no later value is taken over a NaN in the position a scan
+ * starts from (R.pf[1], pf[0], pt[0]).  A float output (pf, pt, a sample of iq_out) that is a NaN by this rule is a NaN in every
+ * implementation, with unspecified sign and payload; every other output is byte for byte, and a sample outside every record is
+ * copied with the bits it has, a NaN's sign and payload included. */
 #define FT8GPU_SUBTRACT_TABLE   4096    /* entries of w4 */
 #define FT8GPU_SUBTRACT_SMOOTH  8       /* the amplitude is averaged over q - 8 .. q + 8: 17 segments of 32 samples */
 #define FT8GPU_SUBTRACT_RANGE   2       /* both fine searches cover -2 .. 2 */

@@ -2,14 +2,16 @@
 restatement tests/ft8_spec_refine.py, byte for byte: radio frames through the whole path on a context of two frames (three
 chunks, the last ragged), host and device pointers; the constructed records of tests/refine_craft.py through the stage entry
 (windows that leave the frame at both ends, the truth on either edge of the search, counts of 0 and 50, a frame of zeros);
-and the product path's records before and after a refine call on the same context.  tests/test_refine_cpu.py proves on the CPU
-that the constructed records are what they are named for."""
+the float edges, samples that are not finite and ties of tests/iq_edges_craft.py; the radio frames spread over 259 frames on a
+context of 260; and the product path's records before and after a refine call on the same context.  tests/test_refine_cpu.py
+and tests/test_iq_edges_cpu.py prove on the CPU that the constructed records are what they are named for."""
 import hashlib
 
 import numpy as np
 import pytest
 
 import ft8_spec_refine as sr
+import iq_edges_craft as ec
 import refine_craft as rc
 
 pytestmark = pytest.mark.gpu
@@ -146,6 +148,75 @@ def test_stage_entry_equals_the_restatement_on_constructed_records(constructed, 
     z = got[2, 0]
     assert z["e_best"] == -16 and z["valid"] == 1 and z.tobytes()[4:] == bytes(44)             # all zeros in: every power is +0
     assert got[where["truth_at_plus16"]]["e_best"] == 16 and got[where["truth_at_minus16"]]["e_best"] == -16
+
+
+# ---- float edges, ties and 259 frames -------------------------------------------------------------------------------------------------------
+
+@pytest.fixture(scope="module")
+def edges(oracle):
+    """tests/iq_edges_craft.edges and the refine restatement on it (tests/test_iq_edges_cpu.py proves what each case is)"""
+    import rtlsdr_ft8d_amd as ft8
+    iq, msgs, _refined, _first, n, where = ec.edges(ft8)
+    fill = ec.filled(ft8.REFINED_DTYPE, len(n))
+    with np.errstate(all="ignore"):
+        want = sr.refine(iq, msgs, n, sr.twiddles(oracle), refined=fill)
+    for a in (iq, msgs, n, fill, want):
+        a.setflags(write=False)
+    return iq, msgs, n, where, fill, want
+
+
+@pytest.mark.parametrize("form", ["host", "device"])
+def test_stage_entry_on_float_edges_and_ties(edges, form):
+    """subnormal, vanishing and infinite powers, samples that are not finite, and thirteen equal non-zero maxima from e = 4 on:
+    byte for byte, but that a NaN of the restatement is any NaN on the device (only in the cases listed in
+    iq_edges_craft.NAN_OUTPUT_CASES)"""
+    import torch
+    import rtlsdr_ft8d_amd as ft8
+    iq, msgs, n, where, fill, want = edges
+    B = len(n)
+    with ft8.Decoder(device=0, max_frames=8 if form == "host" else B) as dec:
+        if form == "host":
+            got = dec.refine_messages(iq, msgs, n, refined=fill.copy())
+        else:
+            ins = [up(a) for a in (iq, msgs, n)]
+            r_b = guarded(fill)
+            torch.cuda.synchronize()
+            dec.refine_messages_dev(ins[0], ins[1], ins[2], B, r_b[GUARD:])
+            dec.synchronize()
+            for a, b in zip((iq, msgs, n), ins):
+                assert b.cpu().numpy().tobytes() == np.ascontiguousarray(a).tobytes()          # inputs are inputs
+            got = unguard(r_b, fill.nbytes).view(ft8.REFINED_DTYPE).reshape(B, 50)
+    print("NaN against NaN:", ec.hold(got, want, where))
+    behind = np.arange(50)[None, :] >= n[:, None]
+    assert (got.view(np.uint8).reshape(B, 50, 48)[behind] == FILL).all()
+    assert got[where["refine_tie"]]["e_best"] == 4 and got[where["nan_behind_window_edge_inside"]]["e_best"] == 0
+    assert got[where["scaled_subnormal_powers"]]["e_best"] == 0 and got[where["scaled_zero_powers"]]["e_best"] == -16
+
+
+@pytest.mark.parametrize("form", ["host", "device"])
+def test_whole_path_over_259_frames(radio, form):
+    """the radio frames at 0, 130, 255, 256 and 258 of 259 frames, zeros elsewhere, in one chunk on a context of 260: a grid of
+    259 x 13 workgroups; a zero frame has no records and its refined slots keep their 0xA5"""
+    import torch
+    import rtlsdr_ft8d_amd as ft8
+    iq5, msgs5, n5, want5 = radio
+    B, at = ec.PIECES_FRAMES, ec.WHOLE_AT
+    iq, msgs, n, want = ec.placed(iq5, at), ec.placed(msgs5, at, fill=FILL), ec.placed(n5, at), ec.placed(want5, at, fill=FILL)
+    msgs0, ref0 = filled(ft8, B)
+    with ft8.Decoder(device=0, max_frames=ec.PIECES_CONTEXT) as dec:
+        if form == "host":
+            got_m, got_n, got_r = dec.decode_messages_refined(iq, msgs=msgs0, refined=ref0)
+        else:
+            iq_d, m_b, r_b, n_b = up(iq), guarded(msgs0), guarded(ref0), guarded(np.zeros(B, np.int32))
+            torch.cuda.synchronize()
+            dec.decode_messages_refined_dev(iq_d, B, m_b[GUARD:], n_b[GUARD:], r_b[GUARD:])
+            dec.synchronize()
+            got_m = unguard(m_b, msgs0.nbytes).view(ft8.MESSAGE_DTYPE).reshape(B, 50)
+            got_r = unguard(r_b, ref0.nbytes).view(ft8.REFINED_DTYPE).reshape(B, 50)
+            got_n = unguard(n_b, 4 * B).view(np.int32)
+    assert got_n.tolist() == n.tolist() and got_n[255] >= 1 and got_n[256] >= 1 and got_n.sum() == n5.sum()
+    assert got_m.tobytes() == msgs.tobytes(), first_difference(got_m, msgs, n)
+    assert got_r.tobytes() == want.tobytes(), first_difference(got_r, want, n)
 
 
 # ---- the product path is not moved ---------------------------------------------------------------------------------------------------------

@@ -2,15 +2,19 @@
 restatement tests/ft8_spec_subtract.py, byte for byte: crowded frames through the whole path at three passes on a context of two
 frames (three chunks, the last ragged), host and device pointers; the committed uncovering seeds; the hand-made records of
 tests/subtract_craft.py through the stage entry (windows that leave the frame, every choice of the fine search, R.valid = 0,
-counts of 0, 3 and 50, first > 0, overlapping records, a frame of zeros, in place); and the product paths' records before and
-after subtraction calls on the same context.  tests/test_subtract_cpu.py proves on the CPU that the hand-made records are what
-they are named for."""
+counts of 0, 3 and 50, first > 0, overlapping records, a frame of zeros, in place); the product paths' records before and
+after subtraction calls on the same context; and the constructions of tests/iq_edges_craft.py: float edges, samples that are not
+finite, non-zero ties and every order of R.pf[1 .. 3] with hand-made R and with the refine kernel's own, first >= 4 with records
+behind it, and 259 frames on a context of 260 through the stage entry and the whole path (subtract_chunk's pieces of 256 and 3).
+tests/test_subtract_cpu.py and tests/test_iq_edges_cpu.py prove on the CPU that the hand-made records are what they are named
+for."""
 import hashlib
 
 import numpy as np
 import pytest
 
 import ft8_spec_subtract as ss
+import iq_edges_craft as ec
 import subtract_craft as sc
 
 pytestmark = pytest.mark.gpu
@@ -236,3 +240,200 @@ def test_product_records_are_unchanged_by_subtraction_calls():
         print("records after 3 passes: masking", masked_total, "subtraction", int(sn.sum().item()), "first pass", int(nm.sum().item()))
         after, _m, _n, _t = digest(dec, iq)
     assert before == after
+
+
+# ---- (v) float edges, ties and u* -------------------------------------------------------------------------------------------------------------
+
+@pytest.fixture(scope="module")
+def edges(oracle):
+    """tests/iq_edges_craft.edges and the restatements on it (tests/test_iq_edges_cpu.py proves what each case is)"""
+    import rtlsdr_ft8d_amd as ft8
+    batch = ec.edges(ft8)
+    want = ec.edges_expected(oracle, batch)
+    for a in batch[:5] + tuple(want.values()):
+        a.setflags(write=False)
+    return batch, want
+
+
+def subtract_stage(dec, form, iq, msgs, refined, first, n, fill):
+    """ft8gpu_subtract_messages in one of three forms -> (iq_out, info); the device forms between guard bands"""
+    import torch
+    B = len(n)
+    if form == "host":
+        return dec.subtract_messages(iq, msgs, refined, first, n, info=fill.copy())
+    ins = [up(a) for a in (msgs, refined, first, n)]
+    x_b, i_b = guarded(iq), guarded(fill)
+    o_b = x_b if form == "device_in_place" else guarded(np.zeros_like(iq))
+    torch.cuda.synchronize()
+    dec.subtract_messages_dev(x_b[GUARD:], ins[0], ins[1], ins[2], ins[3], B, o_b[GUARD:], i_b[GUARD:])
+    dec.synchronize()
+    for a, b in zip((msgs, refined, first, n), ins):
+        assert b.cpu().numpy().tobytes() == np.ascontiguousarray(a).tobytes()              # inputs are inputs
+    if form == "device":
+        assert unguard(x_b, iq.nbytes).tobytes() == iq.tobytes()
+    return (unguard(o_b, iq.nbytes).view(np.float32).reshape(iq.shape), unguard(i_b, fill.nbytes).view(ss.INFO_DTYPE).reshape(B, 50))
+
+
+@pytest.mark.parametrize("form", ["host", "device", "device_in_place"])
+def test_stage_entry_on_float_edges_ties_and_ustar(edges, form):
+    """subnormal, vanishing and infinite powers, samples that are not finite, non-zero ties and every order of R.pf[1 .. 3], with
+    the hand-made R: byte for byte, but that a NaN of the restatement is any NaN on the device (only in the cases listed in
+    iq_edges_craft.NAN_OUTPUT_CASES)"""
+    import rtlsdr_ft8d_amd as ft8
+    (iq, msgs, refined, first, n, where), want = edges
+    B = len(n)
+    with ft8.Decoder(device=0, max_frames=8 if form == "host" else B) as dec:
+        got_out, got_info = subtract_stage(dec, form, iq, msgs, refined, first, n, ec.filled(ss.INFO_DTYPE, B))
+    in_info, in_out = ec.hold(got_info, want["info"], where), ec.hold(got_out, want["out"], where)
+    print("NaN against NaN, hand-made R:", {k: (in_info[k], in_out[k]) for k in in_info})
+    for name, (_pf, us) in ec.USTAR.items():
+        r = got_info[where[name]]
+        assert int(r["k4"]) - int(r["d_best"]) == 4 * (ec.F_SIG + us - 2), name
+    behind = np.arange(50)[None, :] >= n[:, None]
+    assert (got_info.view(np.uint8).reshape(B, 50, 64)[behind] == FILL).all()
+
+
+@pytest.mark.parametrize("form", ["host", "device"])
+def test_refine_then_subtract_on_float_edges_ties_and_ustar(edges, form):
+    """the same frames with R from the refine kernel itself, as the pass loop pairs the two stages"""
+    import torch
+    import rtlsdr_ft8d_amd as ft8
+    (iq, msgs, _hand_made, first, n, where), want = edges
+    B = len(n)
+    with ft8.Decoder(device=0, max_frames=8 if form == "host" else B) as dec:
+        if form == "host":
+            got_ref = dec.refine_messages(iq, msgs, n, refined=ec.filled(ft8.REFINED_DTYPE, B))
+            got_out, got_info = dec.subtract_messages(iq, msgs, got_ref, first, n, info=ec.filled(ss.INFO_DTYPE, B))
+        else:
+            ins = [up(a) for a in (iq, msgs, first, n)]
+            r_b, o_b, i_b = guarded(ec.filled(ft8.REFINED_DTYPE, B)), guarded(np.zeros_like(iq)), guarded(ec.filled(ss.INFO_DTYPE, B))
+            torch.cuda.synchronize()
+            dec.refine_messages_dev(ins[0], ins[1], ins[3], B, r_b[GUARD:])
+            dec.subtract_messages_dev(ins[0], ins[1], r_b[GUARD:], ins[2], ins[3], B, o_b[GUARD:], i_b[GUARD:])
+            dec.synchronize()
+            got_ref = unguard(r_b, B * 50 * 48).view(ft8.REFINED_DTYPE).reshape(B, 50)
+            got_out = unguard(o_b, iq.nbytes).view(np.float32).reshape(iq.shape)
+            got_info = unguard(i_b, B * 50 * 64).view(ss.INFO_DTYPE).reshape(B, 50)
+    in_ref, in_info, in_out = ec.hold(got_ref, want["refined"], where), ec.hold(got_info, want["pair_info"], where), ec.hold(got_out, want["pair_out"], where)
+    print("NaN against NaN, the refine kernel's R:", {k: (in_ref[k], in_info[k], in_out[k]) for k in in_ref})
+
+
+# ---- (vi) late firsts ------------------------------------------------------------------------------------------------------------------------
+
+@pytest.fixture(scope="module")
+def late():
+    import rtlsdr_ft8d_amd as ft8
+    batch = ec.late_firsts(ft8)
+    out, info = ec.late_expected(batch)
+    for a in batch[:5] + (out, info):
+        a.setflags(write=False)
+    return batch, out, info
+
+
+@pytest.mark.parametrize("form", ["host", "device"])
+def test_stage_entry_on_late_firsts(late, form):
+    """first >= 4 with records behind it: estimate workgroups skipped whole and in part, the apply kernel's headers read from
+    record `first` on, a skipped record as the first header; info outside [first, n_msgs) keeps the caller's 0xA5"""
+    import rtlsdr_ft8d_amd as ft8
+    (iq, msgs, refined, first, n, names), want_out, want_info = late
+    B = len(n)
+    with ft8.Decoder(device=0, max_frames=3 if form == "host" else B) as dec:
+        got_out, got_info = subtract_stage(dec, form, iq, msgs, refined, first, n, ec.filled(ss.INFO_DTYPE, B))
+    raw = got_info.view(np.uint8).reshape(B, 50, 64)
+    for f, name in enumerate(names):
+        for i in range(50):
+            assert got_info[f, i].tobytes() == want_info[f, i].tobytes(), (name, i, got_info[f, i], want_info[f, i])
+        assert got_out[f].tobytes() == want_out[f].tobytes(), (name, sample_difference(got_out[f], want_out[f]))
+        assert (raw[f, :first[f]] == FILL).all() and (raw[f, n[f]:] == FILL).all(), name
+        if n[f] > first[f]:
+            assert got_info[f, n[f] - 1]["valid"] == 1 and got_out[f].tobytes() != iq[f].tobytes(), name
+        else:
+            assert got_out[f].tobytes() == iq[f].tobytes(), name
+    assert got_info[names.index("late_48_50_invalid_48"), 48].tobytes() == bytes(64)
+
+
+# ---- (vii) the 256-frame pieces ------------------------------------------------------------------------------------------------------------------
+
+def equal_bits(got, want):
+    got, want = np.ascontiguousarray(got).reshape(-1).view(np.uint8), np.ascontiguousarray(want).reshape(-1).view(np.uint8)
+    return got.shape == want.shape and bool((got == want).all())
+
+
+@pytest.fixture(scope="module")
+def pieces(constructed, late):
+    """259 frames: zeros with n_msgs = 0, but the six frames of `constructed` and the late-firsts frame (5, 11) at
+    iq_edges_craft.STAGE_AT; the expected outputs are those fixtures' own, placed (frames are independent)"""
+    import rtlsdr_ft8d_amd as ft8
+    _iq, _msgs, _refined, _first, _n, _where, _fill, c_out, c_info = constructed
+    (_l_iq, _l_m, _l_R, _l_first, _l_n, l_names), l_out, l_info = late
+    k = l_names.index("late_5_11")
+    pick = lambda a, l: np.stack([l[k] if s == "late" else a[s] for s in ec.STAGE_ORDER])
+    iq, msgs, refined, first, n = ec.pieces_stage(ft8)
+    assert iq[4].tobytes() == _l_iq[k].tobytes() and iq[3].tobytes() == _iq[0].tobytes() and first.tolist() == [2, 0, 0, -3, 5, 7, 0]
+    at = ec.STAGE_AT
+    full = (ec.placed(iq, at), ec.placed(msgs, at, fill=FILL), ec.placed(refined, at, fill=FILL), ec.placed(first, at), ec.placed(n, at))
+    want_out, want_info = ec.placed(pick(c_out, l_out), at), ec.placed(pick(c_info, l_info), at, fill=FILL)
+    for a in full + (want_out, want_info):
+        a.setflags(write=False)
+    return full, want_out, want_info
+
+
+@pytest.mark.parametrize("form", ["host", "device"])
+def test_stage_entry_in_pieces_of_256_frames(pieces, form):
+    """one chunk of 259 frames on a context of 260: subtract_chunk's pieces of 256 and 3, with records in frames 255 and 256"""
+    import rtlsdr_ft8d_amd as ft8
+    (iq, msgs, refined, first, n), want_out, want_info = pieces
+    B = ec.PIECES_FRAMES
+    assert B == len(n) == 259 and n[255] == 70 and (first[256], n[256]) == (5, 11)
+    with ft8.Decoder(device=0, max_frames=ec.PIECES_CONTEXT) as dec:
+        got_out, got_info = subtract_stage(dec, form, iq, msgs, refined, first, n, ec.filled(ss.INFO_DTYPE, B))
+        if form == "host":
+            no_info, none = dec.subtract_messages(iq, msgs, refined, first, n, want_info=False)
+            assert none is None and equal_bits(no_info, want_out)
+    for f in ec.STAGE_AT:
+        assert got_info[f].tobytes() == want_info[f].tobytes(), (f, first_difference(got_info[f:f + 1], want_info[f:f + 1], n[f:f + 1]))
+        assert got_out[f].tobytes() == want_out[f].tobytes(), (f, sample_difference(got_out[f], want_out[f]))
+    assert equal_bits(got_info, want_info) and equal_bits(got_out, want_out)
+    assert not equal_bits(got_out[255], iq[255]) and not equal_bits(got_out[256], iq[256])      # both pieces carried work
+
+
+def place_whole(radio, B, at):
+    iq, msgs, n, nbp, res = radio
+    return (ec.placed(iq, at, B), ec.placed(msgs, at, B, fill=FILL), ec.placed(n, at, B), ec.placed(nbp, at, B), ec.placed(res, at, B))
+
+
+@pytest.mark.parametrize("form", ["host", "device"])
+def test_whole_path_in_pieces_of_256_frames(radio, form):
+    """the radio frames at 0, 130, 255, 256 and 258 of 259 frames, zeros elsewhere, at three passes on a context of 260: the pass
+    loop's subtract_chunk in pieces of 256 and 3; with and without the residual"""
+    import torch
+    import rtlsdr_ft8d_amd as ft8
+    B = ec.PIECES_FRAMES
+    iq, msgs, n, nbp, res = place_whole(radio, B, ec.WHOLE_AT)
+    assert nbp[255].tolist() == [1, 3, 4] and nbp[256].tolist() == [2, 3, 4]                    # both pieces subtract in both later passes
+    with ft8.Decoder(device=0, max_frames=ec.PIECES_CONTEXT) as dec:
+        if form == "host":
+            got_m, got_n, got_nbp, got_res = dec.decode_messages_subtracted(iq, passes=3, msgs=filled_msgs(ft8, B))
+            m2, n2, nbp2, none = dec.decode_messages_subtracted(iq, passes=3, msgs=filled_msgs(ft8, B), want_residual=False)
+            assert none is None
+        else:
+            iq_d = up(iq)
+            def run(with_residual):
+                m_b, n_b, nbp_b = guarded(filled_msgs(ft8, B)), guarded(np.zeros(B, np.int32)), guarded(np.zeros((B, 3), np.int32))
+                r_b = guarded(np.zeros_like(iq)) if with_residual else None
+                torch.cuda.synchronize()
+                dec.decode_messages_subtracted_dev(iq_d, B, 3, m_b[GUARD:], n_b[GUARD:], nbp_b[GUARD:], r_b[GUARD:] if with_residual else None)
+                dec.synchronize()
+                return (unguard(m_b, B * 50 * 64).view(ft8.MESSAGE_DTYPE).reshape(B, 50), unguard(n_b, 4 * B).view(np.int32),
+                        unguard(nbp_b, 12 * B).view(np.int32).reshape(B, 3),
+                        unguard(r_b, iq.nbytes).view(np.float32).reshape(iq.shape) if with_residual else None)
+            got_m, got_n, got_nbp, got_res = run(True)
+            m2, n2, nbp2, _none = run(False)
+            assert equal_bits(iq_d.cpu().numpy(), iq)
+    assert got_n.tolist() == n.tolist() and got_nbp.tolist() == nbp.tolist()
+    assert equal_bits(got_m, msgs), first_difference(got_m, msgs, n)
+    for f in ec.WHOLE_AT:
+        assert got_res[f].tobytes() == res[f].tobytes(), (f, sample_difference(got_res[f], res[f]))
+    assert equal_bits(got_res, res)                                       # a zero frame: no records, itself as residual
+    assert equal_bits(m2, msgs) and n2.tolist() == n.tolist() and nbp2.tolist() == nbp.tolist()
+    assert not equal_bits(got_res[255], iq[255]) and not equal_bits(got_res[256], iq[256])
