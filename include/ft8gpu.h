@@ -1148,6 +1148,67 @@ int ft8gpu_demod_candidates(ft8gpu_ctx *ctx, const float *iq, const ft8gpu_candi
 int ft8gpu_decode_messages_demod(ft8gpu_ctx *ctx, const float *iq, int nframes, const ft8gpu_demod_params *params,
                                  ft8gpu_message *msgs, int32_t *n_msgs, int32_t *n_by_stage, int flags);
 
+/* ---- 12 kHz audio: a resampler in front of the decoder ------------------------------------------------------------------------
+ * (DESIGN.md "Audio front end"; not in the reference, whose frames come from the RTL-SDR front end or from .iq / .c2 files.)
+ * Recordings, WSJT-X .wav saves and web receivers deliver 12 000 sps real audio.  A band of such a clip becomes one frame of the
+ * decoder: mixed down from the band's centre, low-pass filtered, resampled by 4/15 to 3200 sps and moved back to the band's lower
+ * edge.  The decoder reads FFT bins 0 .. 511 of a frame, 1600 Hz, so the usual 200 .. 3100 Hz passband takes two bands.
+ * The rule is exact: float32, one IEEE operation per step, nothing fused; every sum is sequential from +0 in the stated order;
+ * every index is integer arithmetic.
+ *
+ * Input.  a[n], 0 <= n < nsamples, 1 <= nsamples <= FT8GPU_AUDIO_NSAMPLES, zero outside.  FT8GPU_AUDIO_S16: a[n] = (float)pcm[n] *
+ * 2^-15 (exact); FT8GPU_AUDIO_F32: the caller's floats as they are.
+ * Band.  base_bin in [0, FT8GPU_AUDIO_MAX_BASE], in units of 6.25 Hz: the band covers 6.25 base_bin .. 6.25 base_bin + 1600 Hz of
+ * the audio (704 is the last base whose band ends at or below 6000 Hz).
+ * Mixer.  wm[i] = (cos, -sin)(2 pi i / 1920), each the float of the double value (ft8gpu_audio_mixer);
+ *   z[n] = a[n] * wm[(n * (base_bin + 128)) mod 1920], two products.  The mixer frequency is the band's centre, 6.25 base_bin + 800
+ *   Hz; 12000 / 6.25 = 1920, so the table is periodic and the phase exact.
+ * Taps.  h[k], k = 0 .. 158, and h[159] = 0 (ft8gpu_audio_taps): with d = k - 79, in double,
+ *   h[k] = (float)(((8 * (3200 / 48000)) * sinc((3200 * d) / 48000) * I0(8 * sqrt(1 - (d / 80)^2))) / I0(8)),
+ *   sinc(u) = sin(pi u) / (pi u) and 1 at u = 0;  I0(x) = 1 + sum over k = 1 .. 39 of T_k, T_0 = 1, T_k = T_(k-1) * (x / (2 k))^2.
+ *   A Kaiser low-pass (beta 8) at the 48 kHz up-sampled rate with its cutoff at 1600 Hz; the gain is 4 for the zero stuffing times
+ *   2, so that a real cosine of amplitude A arrives as a complex tone of amplitude A.  Passband (0 .. 800 Hz either side of the
+ *   centre) within -0.0004 .. +0.0007 dB; stopband (2400 Hz and beyond, the only offsets that alias into the bins the decoder
+ *   reads) at most -82.6 dB.
+ * Resampler.  For m = 0 .. 47999: t = 15 m + 79, r = t mod 4, N = t div 4;
+ *   y[m] = sum over j = 0 .. 39, ascending, of h[r + 4 j] * z[N - j], real and imaginary parts separately, each term a product
+ *   and then an add.  The filter is centred, so a record's dt_s refers to the clip's own time axis.
+ * Back to the band's lower edge.  x[m] = y[m] * j^m, exactly: m mod 4 = 0: (yr, yi); 1: (-yi, yr); 2: (-yr, -yi); 3: (yi, -yr).
+ *   Negation flips the sign bit, also that of a zero.  The frame is planar, [2][48000].
+ * Any float input is defined: infinities, NaNs and subnormals are kept, not flushed.  An output that is a NaN by this rule is a NaN
+ * in every implementation (sign and payload unspecified); every other output is the same bytes everywhere.  Every clip starts from
+ * reset: no filter state is carried from one clip into the next. */
+#define FT8GPU_AUDIO_RATE      12000
+#define FT8GPU_AUDIO_NSAMPLES  180000  /* 15 s */
+#define FT8GPU_AUDIO_TAPS      160
+#define FT8GPU_AUDIO_MIX       1920
+#define FT8GPU_AUDIO_MAX_BANDS 4
+#define FT8GPU_AUDIO_MAX_BASE  704
+#define FT8GPU_AUDIO_S16       0       /* pcm: int16_t [nclips][nsamples] */
+#define FT8GPU_AUDIO_F32       1       /* pcm: float   [nclips][nsamples] */
+/* the tables of the rule (host, plain C): h[0 .. 159], and wm as 1920 (cos, -sin) pairs */
+void ft8gpu_audio_taps(float out[FT8GPU_AUDIO_TAPS]);
+void ft8gpu_audio_mixer(float out[2 * FT8GPU_AUDIO_MIX]);
+/* stage entry: pcm [nclips][nsamples] of `format`, base_bin [nbands] (host memory in both pointer forms) -> iq_out
+ * [nclips][nbands][2][48000].  Host or device pointers by `flags` (device form: iq_out 16-byte aligned), clips in chunks of
+ * max_frames.  nbands outside [1, 4], a base outside [0, 704], an unknown format and nsamples outside [1, 180000] are refused
+ * before anything is enqueued. */
+int ft8gpu_audio_frames(ft8gpu_ctx *ctx, const void *pcm, int format, int nclips, int nsamples, const int32_t *base_bin,
+                        int nbands, float *iq_out, int flags);
+/* The whole path: the frames of every (clip, band) go through the ft8gpu_decode_messages path, at most max_frames at a time, in a
+ * frame buffer the context allocates on the first call (max_frames frames; a failed allocation leaves the context usable) and
+ * frees at ft8gpu_destroy.  Then the bands of a clip are merged: walking the bands in the caller's order and a band's records in
+ * their order, a record whose 12 a91 bytes equal those of a record already kept for the clip is dropped; a kept record is the
+ * band's record with freq_hz = (cand.freq_offset + base_bin + (float)cand.freq_sub / 2) * 6.25f (the integer add first) and
+ * pad[0] = the band's index; the walk stops at 50 * nbands records.  msgs [nclips][50 * nbands], n_msgs [nclips]; slots at and
+ * behind n_msgs[c] are left untouched.  Arguments are refused as by ft8gpu_audio_frames. */
+int ft8gpu_decode_audio(ft8gpu_ctx *ctx, const void *pcm, int format, int nclips, int nsamples, const int32_t *base_bin,
+                        int nbands, ft8gpu_message *msgs, int32_t *n_msgs, int flags);
+/* Reads a RIFF/WAVE file of PCM (format tag 1), mono, 16 bit, 12000 Hz into out[0 .. cap): *nsamples = min(samples in the file,
+ * cap).  Chunks other than "fmt " and "data" (LIST, ...) are skipped, odd-sized chunks are padded to even.  Everything else is
+ * refused with a line on stderr that names what was found: 0 = ok, -1 = refused (*nsamples = 0). */
+int ft8gpu_read_wav(const char *path, int16_t *out, int32_t cap, int32_t *nsamples);
+
 /* ---- tooling: encoder + synthetic frames (pack77 / ft8_encode / CPFSK synth of
  *      decoderSelfTest, rtlsdr_ft8d.c:924-955) --------------------------------------------- */
 /* Message text -> 77 bits in 10 bytes (pack77, :927); 0 = ok, -1 = the text fits no message type.  Tokens are separated

@@ -88,6 +88,13 @@ DEMOD_INFO_DTYPE = np.dtype([("result", "u1"), ("set", "u1"), ("nhard", "u1"), (
                              ("psync", "<f4"), ("pad", "u1", (4,))])
 DEMOD_MAX_HARD_ERRORS = 174      # FT8GPU_DEMOD_MAX_HARD_ERRORS, the recommended gate
 DEMOD_SETS = 7                   # FT8GPU_DEMOD_SETS, the recommended mask of soft-bit sets
+AUDIO_RATE = 12000               # FT8GPU_AUDIO_RATE
+AUDIO_NSAMPLES = 180000          # FT8GPU_AUDIO_NSAMPLES
+AUDIO_TAPS = 160                 # FT8GPU_AUDIO_TAPS
+AUDIO_MIX = 1920                 # FT8GPU_AUDIO_MIX
+AUDIO_MAX_BANDS = 4              # FT8GPU_AUDIO_MAX_BANDS
+AUDIO_MAX_BASE = 704             # FT8GPU_AUDIO_MAX_BASE
+AUDIO_S16, AUDIO_F32 = 0, 1      # FT8GPU_AUDIO_S16 / _F32
 assert DEMOD_INFO_DTYPE.itemsize == 16
 
 
@@ -174,6 +181,7 @@ ABI_SYMBOLS = [
     "ft8gpu_refine_messages", "ft8gpu_decode_messages_refined", "ft8gpu_refined_estimate", "ft8gpu_format_messages_refined",
     "ft8gpu_subtract_messages", "ft8gpu_decode_messages_subtracted", "ft8gpu_subtract_twiddles",
     "ft8gpu_demod_candidates", "ft8gpu_decode_messages_demod",
+    "ft8gpu_audio_taps", "ft8gpu_audio_mixer", "ft8gpu_audio_frames", "ft8gpu_decode_audio", "ft8gpu_read_wav",
     "ft8_find_sync", "ft8_decode", "ft8_encode", "pack77",            # ft8_lib level (include/ft8_lib/ft8/*.h)
     "initFFTW", "freeFFTW", "ft8_subsystem", "ft8gpu_read_raw_iq", "ft8gpu_read_c2", "ft8gpu_write_raw_iq",
 ]
@@ -348,6 +356,14 @@ def _declare(L):
         L.ft8gpu_decode_messages_subtracted.argtypes = [vp, vp, C.c_int, C.c_int, vp, vp, vp, vp, C.c_int]
         L.ft8gpu_subtract_twiddles.argtypes = [vp]
         L.ft8gpu_subtract_twiddles.restype = None
+    if hasattr(L, "ft8gpu_audio_frames"):                 # absent from older builds loaded by load_library_at
+        L.ft8gpu_audio_taps.argtypes = [vp]
+        L.ft8gpu_audio_taps.restype = None
+        L.ft8gpu_audio_mixer.argtypes = [vp]
+        L.ft8gpu_audio_mixer.restype = None
+        L.ft8gpu_audio_frames.argtypes = [vp, vp, C.c_int, C.c_int, C.c_int, vp, C.c_int, vp, C.c_int]
+        L.ft8gpu_decode_audio.argtypes = [vp, vp, C.c_int, C.c_int, C.c_int, vp, C.c_int, vp, vp, C.c_int]
+        L.ft8gpu_read_wav.argtypes = [C.c_char_p, vp, C.c_int32, i32p]
     L.ft8gpu_rx_decimate.argtypes = [vp, vp, C.c_int, C.c_size_t, vp, C.c_int, C.c_int]
     if hasattr(L, "ft8gpu_rx_stream"):                    # absent from older builds loaded by load_library_at
         L.ft8gpu_rx_stream.argtypes = [vp, vp, C.c_int, C.c_int, C.c_size_t, vp, vp, vp, C.c_int, C.c_int]
@@ -1201,6 +1217,50 @@ class Decoder:
                                                           _ptr(n_msgs_dev), None if n_by_pass_dev is None else _ptr(n_by_pass_dev),
                                                           None if residual_dev is None else _ptr(residual_dev), DEVICE_PTRS))
 
+    @staticmethod
+    def _audio_clips(pcm):
+        """pcm [nclips][nsamples] int16 or float32 (anything else becomes float32) -> (array, format)"""
+        pcm = np.asarray(pcm)
+        pcm = np.ascontiguousarray(pcm, np.int16 if pcm.dtype == np.int16 else np.float32)
+        assert pcm.ndim == 2
+        return pcm, AUDIO_S16 if pcm.dtype == np.int16 else AUDIO_F32
+
+    def audio_frames(self, pcm, base_bins=(0, 240)):
+        """the audio front end (ft8gpu_audio_frames): 12 kHz clips [nclips][nsamples], int16 or float32 -> iq
+        [nclips][nbands][2][48000], the band of 1600 Hz above 6.25 * base_bin Hz of every clip as a frame of the decoder"""
+        pcm, fmt = self._audio_clips(pcm)
+        bases = np.ascontiguousarray(base_bins, np.int32).reshape(-1)
+        out = np.zeros((pcm.shape[0], len(bases), 2, NSAMPLES), np.float32)
+        self._ck(self.lib.ft8gpu_audio_frames(self.h, pcm.ctypes.data, fmt, pcm.shape[0], pcm.shape[1], bases.ctypes.data, len(bases),
+                                            out.ctypes.data, HOST_PTRS))
+        return out
+
+    def audio_frames_dev(self, pcm_dev, fmt, nclips, nsamples, base_bins, iq_out_dev):
+        """pcm_dev [nclips][nsamples] and iq_out_dev [nclips][nbands][2][48000] (16-byte aligned) in HBM; base_bins stay on the host"""
+        bases = np.ascontiguousarray(base_bins, np.int32).reshape(-1)
+        self._ck(self.lib.ft8gpu_audio_frames(self.h, _ptr(pcm_dev), int(fmt), int(nclips), int(nsamples), bases.ctypes.data, len(bases),
+                                            _ptr(iq_out_dev), DEVICE_PTRS))
+
+    def decode_audio(self, pcm, base_bins=(0, 240), msgs=None):
+        """the whole path from 12 kHz audio (ft8gpu_decode_audio) -> (msgs [nclips][50 * nbands], n_msgs [nclips]): every band's
+        messages, a message heard in two bands once, freq_hz on the clip's audio axis, pad[0] the band it was taken from"""
+        pcm, fmt = self._audio_clips(pcm)
+        bases = np.ascontiguousarray(base_bins, np.int32).reshape(-1)
+        shape = (pcm.shape[0], MAX_MESSAGES * max(len(bases), 1))
+        if msgs is None:
+            msgs = np.zeros(shape, MESSAGE_DTYPE)
+        assert msgs.dtype == MESSAGE_DTYPE and msgs.shape == shape and msgs.flags["C_CONTIGUOUS"]
+        n = np.zeros(pcm.shape[0], np.int32)
+        self._ck(self.lib.ft8gpu_decode_audio(self.h, pcm.ctypes.data, fmt, pcm.shape[0], pcm.shape[1], bases.ctypes.data, len(bases),
+                                            msgs.ctypes.data, n.ctypes.data, HOST_PTRS))
+        return msgs, n
+
+    def decode_audio_dev(self, pcm_dev, fmt, nclips, nsamples, base_bins, msgs_dev, n_msgs_dev):
+        """pcm_dev, msgs_dev [nclips][50 * nbands] and n_msgs_dev [nclips] in HBM; base_bins stay on the host"""
+        bases = np.ascontiguousarray(base_bins, np.int32).reshape(-1)
+        self._ck(self.lib.ft8gpu_decode_audio(self.h, _ptr(pcm_dev), int(fmt), int(nclips), int(nsamples), bases.ctypes.data, len(bases),
+                                            _ptr(msgs_dev), _ptr(n_msgs_dev), DEVICE_PTRS))
+
     def ap_candidates_dev(self, mag_dev, cands_dev, counts_dev, status_in_dev, nframes, hyps, max_hard_errors, status_out_dev, info_dev):
         """status_out_dev may be status_in_dev; info_dev: [nframes][max_candidates] 8-byte records; hyps stay on the host"""
         hyps = _ap_hyps(hyps)
@@ -1482,6 +1542,30 @@ def subtract_twiddles():
     out = np.zeros((SUBTRACT_TABLE, 2), np.float32)
     L.ft8gpu_subtract_twiddles(out.ctypes.data)
     return out
+
+
+def audio_taps():
+    """ft8gpu_audio_taps: the Kaiser low-pass of the audio front end as float32 [160]"""
+    out = np.zeros(AUDIO_TAPS, np.float32)
+    load_library().ft8gpu_audio_taps(out.ctypes.data)
+    return out
+
+
+def audio_mixer():
+    """ft8gpu_audio_mixer: wm[i] = (cos, -sin)(2 pi i / 1920) as float32 [1920][2]"""
+    out = np.zeros((AUDIO_MIX, 2), np.float32)
+    load_library().ft8gpu_audio_mixer(out.ctypes.data)
+    return out
+
+
+def read_wav(path, cap=AUDIO_NSAMPLES):
+    """ft8gpu_read_wav: a 12 kHz mono 16-bit PCM .wav -> int16 [min(samples, cap)].  Anything else raises; the library names
+    what it found on stderr."""
+    out = np.zeros(max(int(cap), 0), np.int16)
+    n = C.c_int32(0)
+    if load_library().ft8gpu_read_wav(os.fsencode(path), out.ctypes.data, int(cap), C.byref(n)) != 0:
+        raise Ft8GpuError(f"{path}: not a readable 12000 Hz mono 16-bit PCM .wav (the reason is on stderr)")
+    return out[:n.value].copy()
 
 
 def format_messages_refined(msgs, refined, n):

@@ -313,6 +313,86 @@ int32_t ft8gpu_write_raw_iq(const float *iSamples, const float *qSamples, const 
     return FT8GPU_NSAMPLES;
 }
 
+/* ---- .wav reader of the audio front end (include/ft8gpu.h "12 kHz audio"): RIFF/WAVE, PCM, mono, 16 bit, 12000 Hz -------------
+ * The file is walked chunk by chunk against its real length: nothing is read past a declared size or past the file.  Samples are
+ * little-endian on disk and read as they are, like the floats of the readers above. */
+static uint32_t le32(const unsigned char *b) { return (uint32_t)b[0] | (uint32_t)b[1] << 8 | (uint32_t)b[2] << 16 | (uint32_t)b[3] << 24; }
+static uint32_t le16(const unsigned char *b) { return (uint32_t)b[0] | (uint32_t)b[1] << 8; }
+
+static int wav_refuse(FILE *f, const char *path, const char *what) {
+    fprintf(stderr, "ft8gpu: %s: %s\n", path, what);
+    fclose(f);
+    return -1;
+}
+
+int ft8gpu_read_wav(const char *path, int16_t *out, int32_t cap, int32_t *nsamples) {
+    if (nsamples) *nsamples = 0;
+    if (!path || !out || !nsamples || cap < 0) { fprintf(stderr, "ft8gpu: ft8gpu_read_wav: NULL argument or negative cap\n"); return -1; }
+    FILE *f = open_or_complain(path, "rb");
+    if (!f) return -1;
+    char what[160];
+    long size = -1;
+    if (fseek(f, 0, SEEK_END) == 0) size = ftell(f);
+    if (size < 0 || fseek(f, 0, SEEK_SET) != 0) return wav_refuse(f, path, "cannot determine the file's length");
+    if (size == 0) return wav_refuse(f, path, "empty file");
+    unsigned char head[16];
+    if (size < 12 || fread(head, 1, 12, f) != 12) {
+        snprintf(what, sizeof what, "truncated header: %ld bytes, a RIFF/WAVE header takes 12", size);
+        return wav_refuse(f, path, what);
+    }
+    if (memcmp(head, "RIFF", 4) != 0 || memcmp(head + 8, "WAVE", 4) != 0) {
+        snprintf(what, sizeof what, "not a RIFF/WAVE file: it starts with bytes %02x %02x %02x %02x, form type %02x %02x %02x %02x",
+                 head[0], head[1], head[2], head[3], head[8], head[9], head[10], head[11]);
+        return wav_refuse(f, path, what);
+    }
+    long at = 12;                                           /* offset of the next chunk header */
+    int have_fmt = 0;
+    for (;;) {
+        if (at + 8 > size) {
+            if (at >= size) return wav_refuse(f, path, have_fmt ? "no data chunk" : "no fmt and no data chunk");
+            snprintf(what, sizeof what, "truncated header: %ld stray bytes where a chunk header takes 8", size - at);
+            return wav_refuse(f, path, what);
+        }
+        if (fseek(f, at, SEEK_SET) != 0 || fread(head, 1, 8, f) != 8) return wav_refuse(f, path, "read error in a chunk header");
+        const uint32_t len = le32(head + 4);
+        const long body = at + 8, left = size - body;
+        if (memcmp(head, "data", 4) == 0) {
+            if (!have_fmt) return wav_refuse(f, path, "data chunk in front of the fmt chunk");
+            if ((long long)len > (long long)left) {
+                snprintf(what, sizeof what, "data chunk declares %u bytes, the file holds %ld behind its header", (unsigned)len, left);
+                return wav_refuse(f, path, what);
+            }
+            uint32_t n = len / 2;
+            if (n > (uint32_t)cap) n = (uint32_t)cap;
+            if (n && fread(out, sizeof(int16_t), n, f) != n) return wav_refuse(f, path, "read error in the data chunk");
+            *nsamples = (int32_t)n;
+            fclose(f);
+            return 0;
+        }
+        if ((long long)len > (long long)left) {
+            char id[5] = { 0 };
+            for (int i = 0; i < 4; i++) id[i] = head[i] >= 0x20 && head[i] < 0x7f ? (char)head[i] : '?';
+            snprintf(what, sizeof what, "truncated header: chunk '%s' declares %u bytes, the file holds %ld behind its header",
+                     id, (unsigned)len, left);
+            return wav_refuse(f, path, what);
+        }
+        if (memcmp(head, "fmt ", 4) == 0) {
+            if (len < 16 || fread(head, 1, 16, f) != 16) {
+                snprintf(what, sizeof what, "truncated header: fmt chunk of %u bytes, PCM takes 16", (unsigned)len);
+                return wav_refuse(f, path, what);
+            }
+            const uint32_t tag = le16(head), channels = le16(head + 2), rate = le32(head + 4), bits = le16(head + 14);
+            if (tag != 1 || channels != 1 || rate != FT8GPU_AUDIO_RATE || bits != 16) {
+                snprintf(what, sizeof what, "format tag %u, %u channel(s), %u Hz, %u bit: only PCM (tag 1), mono, %d Hz, 16 bit is read",
+                         (unsigned)tag, (unsigned)channels, (unsigned)rate, (unsigned)bits, FT8GPU_AUDIO_RATE);
+                return wav_refuse(f, path, what);
+            }
+            have_fmt = 1;
+        }
+        at = body + (long)len + (long)(len & 1u);           /* chunks are padded to an even size */
+    }
+}
+
 /* ---- the stdout table of printSpots(), rtlsdr_ft8d.c:643-663 --------------------------------- */
 static void emit(char *out, size_t cap, size_t *at, const char *line, int len) {
     if (len < 0) return;

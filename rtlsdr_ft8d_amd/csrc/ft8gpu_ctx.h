@@ -1,6 +1,6 @@
 // ft8gpu_ctx.h -- the context object and the helpers every host-side translation unit of the C ABI shares: api_context.hip,
 // api_pipeline.hip, api_multi.hip, api_stages.hip, api_messages.hip, api_multipass.hip, api_osd.hip, api_ap.hip, api_glue.hip,
-// api_rx_stream.hip, api_callhash.hip, api_match.hip, api_combine.hip, api_refine.hip, api_subtract.hip, api_demod.hip.  Not installed.
+// api_rx_stream.hip, api_callhash.hip, api_match.hip, api_combine.hip, api_refine.hip, api_subtract.hip, api_demod.hip, api_audio.hip.  Not installed.
 #pragma once
 #include "ft8gpu_internal.h"
 
@@ -90,6 +90,12 @@ struct ft8gpu_ctx {
     ft8gpu_refined *d_sub_ref = nullptr;   //   the refined records [max_frames][50], the info records of the host form,
     ft8gpu_subtract_info *d_sub_info = nullptr;
     int32_t *d_sub_nref = nullptr;         //   and the counts a pass refines and subtracts [max_frames]
+    struct AudioTables *d_audiotab = nullptr;  // audio front end, lazily on its first call: the constant tables,
+    void *d_audio_pcm = nullptr;           //   host-pointer staging of the clips [max_frames][180000] floats,
+    float *d_audio_iq = nullptr;           //   the frame buffer of the whole path and of the host form [max_frames][2][48000],
+    ft8gpu_message *d_audio_bmsgs = nullptr;   // the bands' records [max_frames][4][50] and counts [max_frames][4],
+    int32_t *d_audio_bn = nullptr;
+    ft8gpu_message *d_audio_msgs = nullptr;    // and host-pointer staging of the merged records [max_frames][200]
     ft8gpu_synth_signal *d_sigs = nullptr;
     size_t sigs_cap = 0;
     void *d_rx_sums = nullptr, *d_rx_p2 = nullptr;     // RX front end scratch
@@ -245,6 +251,8 @@ void free_ap_buffers(ft8gpu_ctx *c);
 // first call that needs them
 void free_subtract_buffers(ft8gpu_ctx *c);
 int ensure_subtract_tables(ft8gpu_ctx *c);
+// api_audio.hip: frees the audio front end's buffers (ft8gpu_destroy)
+void free_audio_buffers(ft8gpu_ctx *c);
 // ft8gpu_decode_batch with one more form: kIqOnDevice, frames resident on the context's GPU and records to host arrays
 // (used by the multi-GPU entries; not part of the ABI, whose entry passes on FT8GPU_DEVICE_PTRS only)
 constexpr int kIqOnDevice = 2;
