@@ -1,6 +1,7 @@
 """The audio front end without a GPU (include/ft8gpu.h "12 kHz audio"): the tables of the rule against their formulas and against
-the filter bounds, the numpy restatement (tests/ft8_spec_audio.py) on a pure tone and through the CPU oracle, the merge rule on
-hand-made records, and the .wav reader -- also under AddressSanitizer / UBSan as a program of its own."""
+the filter bounds, the numpy restatement (tests/ft8_spec_audio.py) on a pure tone and through the CPU oracle, against the stage's
+definition in double and against single taps, the inputs of the GPU tests (table entries read, clip ends, the twelve-signal
+clip), the merge rule on hand-made records, and the .wav reader -- also under AddressSanitizer / UBSan as a program of its own."""
 import ctypes as C
 import os
 import struct
@@ -87,6 +88,94 @@ def test_restated_frames_decode_in_the_oracle(oracle, five):
         assert sorted(got) == sorted(ac.IN_BAND[base])
         for text, freq in got.items():
             assert freq + int(base * 6.25) == int(ac.planted_hz(text))
+
+
+# ---- the restatement against the definition, against single taps, and where the GPU tests aim -----------------------------------
+
+@pytest.mark.parametrize("nsamples", ac.REF64_LENGTHS)
+@pytest.mark.parametrize("fmt", [sa.S16, sa.F32])
+def test_restatement_lies_within_the_rounding_bound_of_the_definition(fmt, nsamples):
+    """ac.ref64 is the stage in double from its definition (zero-stuff, FIR at 48 kHz, every 15th sample), with none of the phase
+    arithmetic of the rule; the bound is 44 roundings of float32 on the window's magnitudes, derived there"""
+    a = sa.samples(ac.noise_clip(fmt, nsamples), fmt)
+    for base in ac.REF64_BASES:
+        worst = ac.worst_ratio(sa.frame(a, base), a, base)
+        print(f"format {fmt}, {nsamples} samples, base {base}: worst error {worst:.2f} u S (bound 44)")
+        assert 0 < worst <= 44
+
+
+@pytest.mark.parametrize("base", [3, 704])
+@pytest.mark.parametrize("fmt", [sa.S16, sa.F32])
+def test_impulse_clip_meets_every_tap_alone(fmt, base):
+    """impulses 41 samples apart: no window holds two, so an output is one product of the tables or +0, and the closed form needs
+    no sum.  The tap of an output has k mod 4 = r = (3 - m) mod 4, so a class of m mod 4 can meet only the taps of its own phase:
+    it meets every one of them, 0 .. 158 over the four classes (41 is coprime to 4 and to 15)."""
+    pcm = ac.impulse_clip(fmt)
+    assert pcm[0] != 0 and np.flatnonzero(pcm)[-1] == (ac.N - 1) // 41 * 41 and np.count_nonzero(pcm) == (ac.N - 1) // 41 + 1
+    want = ac.impulse_frame(pcm, fmt, base)
+    _, k, hit = ac.impulse_taps()
+    live = hit & ((want[0] != 0) | (want[1] != 0))
+    m = np.arange(sa.NSAMPLES)
+    used = set()
+    for q in range(4):
+        taps_q = set(k[live & (m % 4 == q)].tolist())
+        assert taps_q == set(range((3 - q) % 4, 159, 4)), q
+        used |= taps_q
+    assert used == set(range(159))
+    assert not want[:, ~hit].any()                                          # zeros elsewhere
+    got = sa.frame(sa.samples(pcm, fmt), base)
+    assert got.view(np.uint32).tobytes() == want.view(np.uint32).tobytes()
+
+
+def test_new_band_lists_read_the_whole_mixer_table():
+    """a band steps through the table by f = base + 128 and visits 1920 / gcd(f, 1920) entries: the band lists of the first GPU
+    tests read 225 entries at most, the ones added since read all 1920"""
+    old = set().union(*(ac.entries_read(b) for b in ac.OLD_BAND_LISTS))
+    assert len(old) <= 225
+    for base, visits in ((0, 15), (240, 120), (480, 60), (704, 30), (3, 1920)):
+        assert len(ac.entries_read((base,))) == visits == 1920 // np.gcd(base + 128, 1920)
+    lists = ac.OLD_BAND_LISTS + ac.WIDE_BAND_LISTS + (ac.SEAM_BANDS, ac.DOZEN_BANDS)
+    assert set().union(*(ac.entries_read(b) for b in lists)) == set(range(1920))
+    assert any(b % 2 for bl in ac.WIDE_BAND_LISTS for b in bl) and any(b % 4 == 0 and b % 16 for bl in ac.WIDE_BAND_LISTS for b in bl)
+
+
+@pytest.mark.parametrize("fmt", [sa.S16, sa.F32])
+@pytest.mark.parametrize("group", sorted(ac.SEAM_LENGTHS))
+def test_clip_ends_fall_where_the_seam_lengths_say(fmt, group):
+    """per length: the outputs all of whose taps lie past the clip are +0 under the rotation, bit for bit, and the output before
+    them is not zero (from 179978 samples on no output is past the clip, and the last output stands for it)"""
+    for nsamples in ac.SEAM_LENGTHS[group]:
+        pcm = ac.seam_clips(fmt, nsamples)
+        assert pcm.shape == (2, nsamples) and pcm[:, -1].all()
+        m0 = ac.first_silent_output(nsamples)
+        assert 1 <= m0 <= sa.NSAMPLES and (m0 == sa.NSAMPLES) == (nsamples >= 179978)
+        x = sa.frames(pcm, fmt, ac.SEAM_BANDS)
+        assert x[..., m0:].view(np.uint32).tobytes() == np.broadcast_to(ac.SILENCE[:, m0:], x[..., m0:].shape).view(np.uint32).tobytes()
+        assert (np.abs(x[:, :, :, m0 - 1]).max(axis=2) > 0).all(), nsamples
+
+
+@pytest.fixture(scope="module")
+def dozen(oracle):
+    pcm = ac.dozen_signal_clip(oracle)
+    distinct = sorted(set(ac.DOZEN_BANDS))
+    return pcm, dict(zip(distinct, sa.frames(pcm[None], sa.S16, distinct)[0]))
+
+
+def test_dozen_signal_clip_decodes_in_three_overlapping_bands(oracle, dozen):
+    """the clip of the merge test on the GPU: the oracle finds at least ten of the twelve signals in each of the three distinct
+    bands of DOZEN_BANDS, at their frequencies (the seed was chosen for that)"""
+    _, frames = dozen
+    texts = [t for t, _, _ in ac.DOZEN]
+    assert len(set(texts)) == 12 and len({f for _, f, _ in ac.DOZEN}) == 12 and len({s for _, _, s in ac.DOZEN}) == 12
+    assert all(700 <= f <= 1500 for _, f, _ in ac.DOZEN) and len(set(ac.DOZEN_BANDS)) == 3
+    for base, x in frames.items():
+        dec, n = oracle.subsystem(x[0], x[1])
+        got = {f"CQ {dec[k]['call'].decode()} {dec[k]['loc'].decode()}": int(dec[k]["freq"]) for k in range(n)}
+        planted = [t for t in got if t in texts]
+        print(f"band {base}: {len(planted)} of 12, {got}")
+        assert len(planted) >= 10
+        for t in planted:
+            assert got[t] + int(base * 6.25) == int(ac.dozen_hz(t))
 
 
 # ---- the merge rule ---------------------------------------------------------------------------------------------------------------
