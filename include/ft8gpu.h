@@ -254,10 +254,20 @@ int ft8gpu_collect_spots(ft8gpu_ctx *ctx, const ft8gpu_candidate *cands, const i
  * ft8gpu_decode_batch keeps the reference's contract: only CQ messages reach a record, and decoder_results.snr is the sync
  * score (rtlsdr_ft8d.c:1509-1520; the reference itself notes "score != snr", :1517).  The entries below number the unique
  * messages of a frame exactly as that path does (:1487-1520, the same dedup, order and cap of 50, so n_msgs[f] ==
- * n_results[f] for the same input and parameters) and write one record for EVERY one of them, CQ or not. */
+ * n_results[f] for the same input and parameters) and write one record for EVERY one of them, CQ or not.
+ * How the stage entries below (and ft8gpu_collect_spots) read a caller-made list: candidate idx of frame f is looked at when
+ * idx < max_candidates && idx < counts[f], so a count below 0 reads as 0 and one above max_candidates as max_candidates; a
+ * candidate counts when its score >= min_score and its status record's ok is NON-ZERO (any of 1..255); two candidates carry
+ * the same message when crc_extracted (all 16 bits) and the text up to its first NUL (all 25 bytes if there is none) agree.
+ * The tones under which the signal is measured (and which the mask and the refinement rebuild) are "re-encoded from a91":
+ * ALL 91 BITS AS STORED -- the 77 payload bits and the 14 bits of the CRC field the record carries, not a CRC recomputed
+ * from the payload -- through the generator, the Gray map and the Costas arrays; the low five bits of a91[11] play no
+ * part and are copied into the record as they are.  For a record the LDPC kernel wrote the two readings are the same. */
 typedef struct {
     char     text[25];       /*  0  message_t.text, as the LDPC kernel unpacked it (== ft8gpu_decode_status.text) */
-    int8_t   snr_db;         /* 25  estimated SNR in 2500 Hz, integer dB, [-30, 49] (DESIGN.md "Every decoded message") */
+    int8_t   snr_db;         /* 25  estimated SNR in 2500 Hz, integer dB, [-30, 49] (DESIGN.md "Every decoded message");
+                              *     49 when no symbol of the signal lies inside the waterfall (time_offset <= -79 or >= 92:
+                              *     the empty sum meets every threshold, 0 >= 0) */
     int16_t  score;          /* 26  sync score: what decoder_results.snr carries */
     float    freq_hz;        /* 28  (freq_offset + (float)freq_sub / 2) * 6.25f, rtlsdr_ft8d.c:1470, before the int cast */
     float    dt_s;           /* 32  (time_offset + (float)time_sub / 2) / 6.25f, the formula of rtlsdr_ft8d.c:1471, in float */

@@ -82,11 +82,12 @@ def snr_continuous(S, nsym, nb, k=0.0):
 
 
 def tones_of(a91):
-    """79 tones of a decoded message, from its 77-bit payload through ft8gpu_encode (host C)"""
-    import rtlsdr_ft8d_amd as ft8
-    p = np.frombuffer(bytes(a91), np.uint8)[:10].copy()
-    p[9] &= 0xF8
-    return ft8.encode(p)
+    """79 tones of a decoded message, encoded from the 91 bits of a91 AS STORED (payload and CRC field; the low five bits of
+    a91[11] play no part), as tone_dev.h and the two whole-codeword encoders of the device do.  For a record whose CRC field
+    matches its payload this is ft8_encode of the payload (tests/test_messages_cpu.py holds the two equal); a caller-made
+    record whose CRC field does not match is encoded from the field it carries, not from a recomputed one."""
+    import ft8_spec_refine
+    return ft8_spec_refine.tones_of_a91(a91).astype(np.uint8)
 
 
 def crc_of_payload(a91):
@@ -122,9 +123,10 @@ def collect(mag, cands, counts, status, min_score=10, msgs=None):
     n = np.zeros(B, np.int32)
     base = noise_baseline(mag)
     raw_status = st.view(np.uint8).reshape(B, -1, 48)
+    cap = st.shape[1]
     for f in range(B):
         seen = []                                        # (hash, text) of the unique messages, in order
-        for i in range(int(counts[f])):
+        for i in range(min(max(int(counts[f]), 0), cap)):              # idx < max_candidates && idx < counts[f]
             c = cands[f, i]
             r = st[f, i]
             if int(c["score"]) < min_score or r["ok"] == 0:           # :1467, :1476-1485

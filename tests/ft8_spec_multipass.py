@@ -63,7 +63,7 @@ def append(mag, base, cands, counts, status, msgs, n_msgs, min_score=10):
         n0 = _clamp(n_msgs[f], 0, MAX_MESSAGES)
         seen = [_key(out[f, r].tobytes()[:25], out[f, r]["hash"]) for r in range(n0)]
         kept = n0
-        for i in range(int(counts[f])):
+        for i in range(_clamp(counts[f], 0, st.shape[1])):            # idx < max_candidates && idx < counts[f]
             if kept >= MAX_MESSAGES:
                 break
             c, r = cands[f, i], st[f, i]

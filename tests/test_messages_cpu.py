@@ -138,7 +138,8 @@ def test_checker_fails_on_doctored_records(ft8, oracle):
 
 
 def test_restatement_tones_match_the_oracle_encoder(ft8, oracle):
-    """the host encoder the restatement uses for the SNR tones is ft8_encode (the oracle's own) on the payload of a91"""
+    """the restatement encodes the 91 stored bits of a91 (as the device does); where the CRC field matches the payload that is
+    ft8_encode (the oracle's own) on the payload of a91"""
     from rtlsdr_ft8d_amd import workload
     texts, tones = workload.mixed_message_pool(64, seed=11)
     for t in texts:
