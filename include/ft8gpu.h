@@ -1260,6 +1260,72 @@ int ft8gpu_synth_frames_at(ft8gpu_ctx *ctx, const ft8gpu_synth_signal *signals, 
                            int nsig_per_frame, float noise_sigma, uint64_t seed, uint64_t first_frame,
                            float *iq_dev);
 
+/* ---- GFSK synthesis: the signal as it is on the air, as I/Q frames and as 12 kHz audio -------------------------------------------
+ * (DESIGN.md "GFSK synthesis"; not in the reference, whose self-test frame is plain CPFSK.)  An FT8 transmitter sends GFSK: the
+ * frequency pulse of a symbol is a rectangle of one symbol smoothed by a Gaussian with BT = 2, cut to three symbols, and the
+ * amplitude is ramped over the first and the last eighth of a symbol.  This is WSJT-X's sampled pulse (gfsk_pulse, gen_ft8wave)
+ * and its running sum.  The rule is exact: the phase is integer arithmetic, the rest float32 with one IEEE operation per step,
+ * nothing fused, sums sequential from +0.
+ *
+ * Modes.  FT8GPU_GFSK_IQ: rate 3200, sps = 512 samples per symbol, output planar [2][48000] = (cos, sin).
+ *         FT8GPU_GFSK_AUDIO: rate 12000, sps = 1920, output real = cos, nsamples in [1, 180000].
+ * Pulse table Q_sps[0 .. 3 sps], uint32 in units of 2^-32 turn (ft8gpu_gfsk_pulse), in double:
+ *   c = M_PI * sqrt(2.0 / log(2.0));  t_i = ((double)i - 1.5 * (double)sps) / (double)sps;
+ *   p_i = 0.5 * (erf((2.0 * c) * (t_i + 0.5)) - erf((2.0 * c) * (t_i - 0.5))),  i = 0 .. 3 sps - 1;
+ *   Q[k] = llrint((4294967296.0 * (p_0 + ... + p_(k-1), sequential from 0.0)) / (double)sps) mod 2^32.
+ *   The pulses of neighbouring symbols sum to one, so Q[3 sps] is 0 mod 2^32 (the unreduced value is 2^32 for both sps).  Two
+ *   libms may round erf differently: an entry may differ by one unit between two hosts.  The device uses the table of its host.
+ * Twiddles (ft8gpu_gfsk_twiddles).  gc[i] = (cos, sin)(2.0 * M_PI * (double)i / 4096.0), gf[i] = (cos, sin)(2.0 * M_PI * (double)i /
+ *   16777216.0), i = 0 .. 4095, each entry the float of the double value.
+ * Ramp (ft8gpu_gfsk_ramp).  nr = sps / 8;  r[k] = (float)(0.5 * (1.0 - cos(M_PI * (double)k / (double)nr))), k = 0 .. nr - 1;
+ *   env(n') = r[n'] for n' < nr;  r[79 sps - 1 - n'] for n' >= 79 sps - nr;  1 otherwise.  This is the mirrored form: WSJT-X's
+ *   trailing ramp, 0.5 (1 + cos(pi k / nr)) from sample 79 sps - nr on, is this one a sample later.
+ * Per signal (an ft8gpu_synth_signal).  start = lrintf(t0_s * (float)rate);  step = (uint32_t)llrint((double)f0_hz * 4294967296.0 /
+ *   (double)rate), left to right, on the host; a negative f0_hz wraps (meaningful in the I/Q mode).  Extended tones: e[0] =
+ *   tones[0], e[j] = tones[j - 1] for j = 1 .. 79, e[80] = tones[78].  For the local sample n' in [0, 79 sps), m = n' div sps,
+ *   k = n' mod sps, in wrapping uint32 arithmetic
+ *     phi = step * n' + e[m] * Q[k + 2 sps] + e[m + 1] * Q[k + sps] + e[m + 2] * Q[k]
+ *   (the modulation index is 1, so symbols further back contribute whole turns and drop out);  ic = phi >> 20, jf = (phi >> 8) & 4095;
+ *     co = gc[ic].c * gf[jf].c - gc[ic].s * gf[jf].s;   si = gc[ic].s * gf[jf].c + gc[ic].c * gf[jf].s
+ *   (two products, then one subtraction or addition);  a = amplitude * env(n');  the contribution (a * co, a * si) goes to output
+ *   sample start + n' where that lies inside the clip: a signal may begin before sample 0 and end behind the clip's end, and is
+ *   cut there, not shifted.
+ * Output sample.  The contributions of the clip's signals are summed in signal order from +0.  If noise_sigma > 0 the noise is
+ *   added last.  If peak > 0: m = the largest |x| of the clip (both planes in the I/Q mode; a NaN is skipped as by fmaxf),
+ *   m = max(m, 1e-24f), s = peak / m, x = x * s; with peak 0.5 this is the decoder thread's convention (rtlsdr_ft8d.c:248-263).
+ *   FT8GPU_AUDIO_S16: rintf(x * 32768.0f), clamped to [-32768, 32767]; a NaN gives 0.
+ * Noise.  The counter generator of ft8gpu_synth_frames, keyed by (seed, first + clip index, sample index), with its Box-Muller:
+ *   one draw gives I and Q; the audio mode takes the cosine branch.  Noise is outside the exact contract (it need not match a
+ *   CPU), but a clip's noise is the same bytes on the device for any chunking and any partition of a job by first_*.  With
+ *   noise_sigma == 0 the generator is not evaluated and the output is the rule's bytes.
+ * Refused before anything is enqueued (and before the context is looked at): f0_hz, t0_s or amplitude not finite; |f0_hz| >=
+ *   rate, or f0_hz < 0 in the audio mode; |t0_s| > 60; a tone above 7; more than 64 signals per clip (0 is allowed); nsamples
+ *   outside [1, 180000]; an unknown format; peak < 0 or noise_sigma < 0, or either not finite. */
+#define FT8GPU_GFSK_IQ         0
+#define FT8GPU_GFSK_AUDIO      1
+#define FT8GPU_GFSK_SPS_IQ     512
+#define FT8GPU_GFSK_SPS_AUDIO  1920
+#define FT8GPU_GFSK_TWIDDLES   4096
+#define FT8GPU_GFSK_MAX_SIGNALS 64
+#define FT8GPU_GFSK_TILE       8192    /* output samples a workgroup of the kernel owns (not part of the rule; the tests aim at its seams) */
+/* the tables of the rule (host, plain C).  sps is 512 or 1920: out[3 sps + 1] resp. out[sps / 8]; 0 = ok, -1 = another sps or NULL */
+int ft8gpu_gfsk_pulse(int sps, uint32_t *out);
+int ft8gpu_gfsk_ramp(int sps, float *out);
+/* coarse = gc, fine = gf, each 4096 (cos, sin) pairs; a NULL table is left out */
+void ft8gpu_gfsk_twiddles(float *coarse, float *fine);
+/* signals: host array [nframes][nsig_per_frame] in both pointer forms; iq_out [nframes][2][48000], host or device memory by
+ * `flags`, frames in chunks of max_frames.  Frame k of the call is global frame first_frame + k (its noise depends on seed and
+ * the global index only).  Tables and buffers are allocated on the first GFSK call and freed at ft8gpu_destroy. */
+int ft8gpu_synth_gfsk_frames(ft8gpu_ctx *ctx, const ft8gpu_synth_signal *signals, int nframes, int nsig_per_frame,
+                             float noise_sigma, uint64_t seed, uint64_t first_frame, float peak, float *iq_out, int flags);
+/* the same as 12 kHz audio: pcm_out [nclips][nsamples] of `format` (FT8GPU_AUDIO_S16 or FT8GPU_AUDIO_F32) */
+int ft8gpu_synth_gfsk_audio(ft8gpu_ctx *ctx, const ft8gpu_synth_signal *signals, int nclips, int nsig_per_clip, int nsamples,
+                            float noise_sigma, uint64_t seed, uint64_t first_clip, float peak, int format, void *pcm_out, int flags);
+/* Writes pcm[0 .. nsamples) as a RIFF/WAVE file of PCM, mono, 16 bit, 12000 Hz with a 44-byte header, which ft8gpu_read_wav
+ * reads back to the same samples.  nsamples >= 0.  0 = ok, -1 = NULL argument, negative count or the file could not be written
+ * (a line on stderr says why). */
+int ft8gpu_write_wav(const char *path, const int16_t *pcm, int32_t nsamples);
+
 /* ---- RX front end: rtlsdr_callback(), rtlsdr_ft8d.c:76-202 ------------
  * Whole raw RTL-SDR captures (unsigned 8-bit I,Q interleaved at 2.4 Msps) -> the 15 s / ~3200 sps
  * float frames the decoder consumes: fs/4 mixer, CIC (N = 2, comb delay 2, effective ratio 751),

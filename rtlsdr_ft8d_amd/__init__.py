@@ -95,6 +95,11 @@ AUDIO_MIX = 1920                 # FT8GPU_AUDIO_MIX
 AUDIO_MAX_BANDS = 4              # FT8GPU_AUDIO_MAX_BANDS
 AUDIO_MAX_BASE = 704             # FT8GPU_AUDIO_MAX_BASE
 AUDIO_S16, AUDIO_F32 = 0, 1      # FT8GPU_AUDIO_S16 / _F32
+GFSK_IQ, GFSK_AUDIO = 0, 1       # FT8GPU_GFSK_IQ / _AUDIO
+GFSK_SPS_IQ, GFSK_SPS_AUDIO = 512, 1920   # FT8GPU_GFSK_SPS_IQ / _AUDIO
+GFSK_TWIDDLES = 4096             # FT8GPU_GFSK_TWIDDLES
+GFSK_MAX_SIGNALS = 64            # FT8GPU_GFSK_MAX_SIGNALS
+GFSK_TILE = 8192                 # FT8GPU_GFSK_TILE: output samples per workgroup of the kernel as built
 assert DEMOD_INFO_DTYPE.itemsize == 16
 
 
@@ -182,6 +187,8 @@ ABI_SYMBOLS = [
     "ft8gpu_subtract_messages", "ft8gpu_decode_messages_subtracted", "ft8gpu_subtract_twiddles",
     "ft8gpu_demod_candidates", "ft8gpu_decode_messages_demod",
     "ft8gpu_audio_taps", "ft8gpu_audio_mixer", "ft8gpu_audio_frames", "ft8gpu_decode_audio", "ft8gpu_read_wav",
+    "ft8gpu_gfsk_pulse", "ft8gpu_gfsk_ramp", "ft8gpu_gfsk_twiddles", "ft8gpu_synth_gfsk_frames", "ft8gpu_synth_gfsk_audio",
+    "ft8gpu_write_wav",
     "ft8_find_sync", "ft8_decode", "ft8_encode", "pack77",            # ft8_lib level (include/ft8_lib/ft8/*.h)
     "initFFTW", "freeFFTW", "ft8_subsystem", "ft8gpu_read_raw_iq", "ft8gpu_read_c2", "ft8gpu_write_raw_iq",
 ]
@@ -364,6 +371,15 @@ def _declare(L):
         L.ft8gpu_audio_frames.argtypes = [vp, vp, C.c_int, C.c_int, C.c_int, vp, C.c_int, vp, C.c_int]
         L.ft8gpu_decode_audio.argtypes = [vp, vp, C.c_int, C.c_int, C.c_int, vp, C.c_int, vp, vp, C.c_int]
         L.ft8gpu_read_wav.argtypes = [C.c_char_p, vp, C.c_int32, i32p]
+    if hasattr(L, "ft8gpu_synth_gfsk_frames"):            # absent from older builds loaded by load_library_at
+        L.ft8gpu_gfsk_pulse.argtypes = [C.c_int, vp]
+        L.ft8gpu_gfsk_ramp.argtypes = [C.c_int, vp]
+        L.ft8gpu_gfsk_twiddles.argtypes = [vp, vp]
+        L.ft8gpu_gfsk_twiddles.restype = None
+        L.ft8gpu_synth_gfsk_frames.argtypes = [vp, vp, C.c_int, C.c_int, C.c_float, C.c_uint64, C.c_uint64, C.c_float, vp, C.c_int]
+        L.ft8gpu_synth_gfsk_audio.argtypes = [vp, vp, C.c_int, C.c_int, C.c_int, C.c_float, C.c_uint64, C.c_uint64, C.c_float, C.c_int,
+                                              vp, C.c_int]
+        L.ft8gpu_write_wav.argtypes = [C.c_char_p, vp, C.c_int32]
     L.ft8gpu_rx_decimate.argtypes = [vp, vp, C.c_int, C.c_size_t, vp, C.c_int, C.c_int]
     if hasattr(L, "ft8gpu_rx_stream"):                    # absent from older builds loaded by load_library_at
         L.ft8gpu_rx_stream.argtypes = [vp, vp, C.c_int, C.c_int, C.c_size_t, vp, vp, vp, C.c_int, C.c_int]
@@ -1389,6 +1405,42 @@ class Decoder:
         self._ck(self.lib.ft8gpu_synth_frames_at(self.h, signals.ctypes.data, nframes, nsig, float(noise_sigma),
                                                int(seed), int(first_frame), _ptr(iq_dev)))
 
+    @staticmethod
+    def _gfsk_signals(signals, nclips, nsig):
+        signals = np.ascontiguousarray(signals)
+        assert signals.dtype == SIGNAL_DTYPE and signals.size == nclips * nsig
+        return signals
+
+    def synth_gfsk_frames(self, signals, nframes, nsig, noise_sigma=0.0, seed=0, first_frame=0, peak=0.0):
+        """ft8gpu_synth_gfsk_frames: signals [nframes][nsig] of SIGNAL_DTYPE -> iq float32 [nframes][2][48000], GFSK at 3200 sps;
+        frame k is global frame first_frame + k for the noise; peak > 0 normalises every frame's largest sample to it"""
+        signals = self._gfsk_signals(signals, nframes, nsig)
+        out = np.zeros((nframes, 2, NSAMPLES), np.float32)
+        self._ck(self.lib.ft8gpu_synth_gfsk_frames(self.h, signals.ctypes.data, int(nframes), int(nsig), float(noise_sigma), int(seed),
+                                                 int(first_frame), float(peak), out.ctypes.data, HOST_PTRS))
+        return out
+
+    def synth_gfsk_frames_dev(self, signals, nframes, nsig, noise_sigma, seed, first_frame, peak, iq_out_dev):
+        """iq_out_dev [nframes][2][48000] float32 in HBM; signals stay on the host"""
+        signals = self._gfsk_signals(signals, nframes, nsig)
+        self._ck(self.lib.ft8gpu_synth_gfsk_frames(self.h, signals.ctypes.data, int(nframes), int(nsig), float(noise_sigma), int(seed),
+                                                 int(first_frame), float(peak), _ptr(iq_out_dev), DEVICE_PTRS))
+
+    def synth_gfsk_audio(self, signals, nclips, nsig, nsamples=AUDIO_NSAMPLES, noise_sigma=0.0, seed=0, first_clip=0, peak=0.0,
+                         fmt=AUDIO_F32):
+        """ft8gpu_synth_gfsk_audio: signals [nclips][nsig] -> pcm [nclips][nsamples], int16 (AUDIO_S16) or float32, GFSK at 12 kHz"""
+        signals = self._gfsk_signals(signals, nclips, nsig)
+        out = np.zeros((nclips, max(int(nsamples), 0)), np.int16 if fmt == AUDIO_S16 else np.float32)
+        self._ck(self.lib.ft8gpu_synth_gfsk_audio(self.h, signals.ctypes.data, int(nclips), int(nsig), int(nsamples), float(noise_sigma),
+                                                int(seed), int(first_clip), float(peak), int(fmt), out.ctypes.data, HOST_PTRS))
+        return out
+
+    def synth_gfsk_audio_dev(self, signals, nclips, nsig, nsamples, noise_sigma, seed, first_clip, peak, fmt, pcm_out_dev):
+        """pcm_out_dev [nclips][nsamples] of fmt in HBM; signals stay on the host"""
+        signals = self._gfsk_signals(signals, nclips, nsig)
+        self._ck(self.lib.ft8gpu_synth_gfsk_audio(self.h, signals.ctypes.data, int(nclips), int(nsig), int(nsamples), float(noise_sigma),
+                                                int(seed), int(first_clip), float(peak), int(fmt), _ptr(pcm_out_dev), DEVICE_PTRS))
+
     # ---- device memory helpers of the C ABI (a plain C caller has no HIP headers) ---------------
     def dev_alloc(self, nbytes):
         p = self.lib.ft8gpu_dev_alloc(self.h, nbytes)
@@ -1566,6 +1618,36 @@ def read_wav(path, cap=AUDIO_NSAMPLES):
     if load_library().ft8gpu_read_wav(os.fsencode(path), out.ctypes.data, int(cap), C.byref(n)) != 0:
         raise Ft8GpuError(f"{path}: not a readable 12000 Hz mono 16-bit PCM .wav (the reason is on stderr)")
     return out[:n.value].copy()
+
+
+def gfsk_pulse(sps):
+    """ft8gpu_gfsk_pulse: Q_sps[0 .. 3 sps] as uint32, the running sum of the Gaussian frequency pulse in units of 2^-32 turn"""
+    out = np.zeros(3 * int(sps) + 1, np.uint32)
+    if load_library().ft8gpu_gfsk_pulse(int(sps), out.ctypes.data) != 0:
+        raise Ft8GpuError(f"gfsk_pulse: sps {sps} is neither {GFSK_SPS_IQ} nor {GFSK_SPS_AUDIO}")
+    return out
+
+
+def gfsk_ramp(sps):
+    """ft8gpu_gfsk_ramp: r[k] = 0.5 (1 - cos(pi k / nr)) as float32 [nr], nr = sps / 8"""
+    out = np.zeros(max(int(sps) // 8, 1), np.float32)
+    if load_library().ft8gpu_gfsk_ramp(int(sps), out.ctypes.data) != 0:
+        raise Ft8GpuError(f"gfsk_ramp: sps {sps} is neither {GFSK_SPS_IQ} nor {GFSK_SPS_AUDIO}")
+    return out
+
+
+def gfsk_twiddles():
+    """ft8gpu_gfsk_twiddles: (gc, gf), (cos, sin)(2 pi i / 4096) and (cos, sin)(2 pi i / 2^24), float32 [4096][2] each"""
+    gc, gf = np.zeros((GFSK_TWIDDLES, 2), np.float32), np.zeros((GFSK_TWIDDLES, 2), np.float32)
+    load_library().ft8gpu_gfsk_twiddles(gc.ctypes.data, gf.ctypes.data)
+    return gc, gf
+
+
+def write_wav(path, pcm):
+    """ft8gpu_write_wav: int16 samples -> a 12 kHz mono 16-bit PCM .wav that read_wav reads back"""
+    pcm = np.ascontiguousarray(pcm, np.int16).reshape(-1)
+    if load_library().ft8gpu_write_wav(os.fsencode(path), pcm.ctypes.data, pcm.size) != 0:
+        raise Ft8GpuError(f"{path}: could not be written (the reason is on stderr)")
 
 
 def format_messages_refined(msgs, refined, n):

@@ -288,6 +288,7 @@ void ft8gpu_destroy(ft8gpu_ctx *c) {
     free_ap_buffers(c);
     free_subtract_buffers(c);
     free_audio_buffers(c);
+    free_gfsk_buffers(c);
     if (c->side) (void)hipStreamSynchronize(c->side);
     for (auto &slot : c->ev) for (auto &e : slot) if (e) (void)hipEventDestroy(e);
     for (auto &e : c->dep) if (e) (void)hipEventDestroy(e);

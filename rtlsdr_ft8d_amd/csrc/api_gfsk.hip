@@ -1,0 +1,151 @@
+// api_gfsk.hip -- host side of the GFSK synthesiser: ft8gpu_synth_gfsk_frames and ft8gpu_synth_gfsk_audio (DESIGN.md "GFSK
+// synthesis"; the kernels are gfsk.hip, the tables plain C in ft8_gfsk.c).
+//
+// Both entries check their arguments first (a refusal needs no GPU), derive the signals' headers (step, start, extended tones)
+// on the host, and cut the clips with for_each_chunk.  With peak == 0 the kernel writes the caller's format directly; otherwise
+// it writes floats (into the output itself where that holds floats) and leaves the tiles' maxima, and a second launch scales.
+// Everything here is allocated on the first GFSK call, so ft8gpu_create's footprint is unchanged.
+#include "gfsk.h"
+#include "ft8gpu_ctx.h"
+
+#include <math.h>
+#include <stdlib.h>
+#include <vector>
+
+namespace {
+
+constexpr size_t kClipFloats = FT8GPU_AUDIO_NSAMPLES;       // the longest output of a clip in floats (an I/Q frame takes 96000)
+
+// a failed allocation is reported and forgotten, so that the launches of a later call do not see it
+template <class T>
+int gfsk_alloc(T **p, size_t bytes) {
+    if (*p) return 0;
+    const hipError_t e = hipMalloc(p, bytes);
+    if (e == hipSuccess) return 0;
+    *p = nullptr;
+    (void)hipGetLastError();
+    return ft8_fail("GFSK synthesis: hipMalloc(%zu) failed: %s", bytes, hipGetErrorString(e));
+}
+
+int ensure_gfsk_tables(ft8gpu_ctx *c) {
+    if (c->d_gfsktab) return 0;
+    GfskTables *h = (GfskTables *)calloc(1, sizeof(GfskTables));
+    if (!h) return ft8_fail("out of memory");
+    ft8gpu_gfsk_pulse(FT8GPU_GFSK_SPS_IQ, h->q_iq);
+    ft8gpu_gfsk_pulse(FT8GPU_GFSK_SPS_AUDIO, h->q_audio);
+    ft8gpu_gfsk_twiddles(&h->gc[0].x, &h->gf[0].x);
+    ft8gpu_gfsk_ramp(FT8GPU_GFSK_SPS_IQ, h->ramp_iq);
+    ft8gpu_gfsk_ramp(FT8GPU_GFSK_SPS_AUDIO, h->ramp_audio);
+    GfskTables *d = nullptr;
+    hipError_t e = hipMalloc(&d, sizeof(GfskTables));
+    if (e == hipSuccess) e = hipMemcpy(d, h, sizeof(GfskTables), hipMemcpyHostToDevice);
+    free(h);
+    if (e != hipSuccess) {
+        if (d) (void)hipFree(d);
+        (void)hipGetLastError();
+        return ft8_fail("GFSK tables: %s", hipGetErrorString(e));
+    }
+    c->d_gfsktab = d;
+    return 0;
+}
+
+// the refusals of both entries; on success hdr holds the nclips * nsig headers
+int check_gfsk_args(int mode, const ft8gpu_synth_signal *signals, int nclips, int nsig, int nsamples, float noise_sigma, float peak,
+                    int format, std::vector<GfskHeader> *hdr) {
+    const int rate = mode == FT8GPU_GFSK_IQ ? 3200 : FT8GPU_AUDIO_RATE;
+    if (format != FT8GPU_AUDIO_S16 && format != FT8GPU_AUDIO_F32) return ft8_fail("unknown audio format %d", format);
+    if (nsamples < 1 || nsamples > FT8GPU_AUDIO_NSAMPLES)
+        return ft8_fail("nsamples %d out of range [1, %d]", nsamples, FT8GPU_AUDIO_NSAMPLES);
+    if (nsig < 0 || nsig > FT8GPU_GFSK_MAX_SIGNALS) return ft8_fail("nsig %d out of range [0, %d]", nsig, FT8GPU_GFSK_MAX_SIGNALS);
+    if (!isfinite(noise_sigma) || noise_sigma < 0.0f) return ft8_fail("noise_sigma %g is negative or not finite", (double)noise_sigma);
+    if (!isfinite(peak) || peak < 0.0f) return ft8_fail("peak %g is negative or not finite", (double)peak);
+    if (nclips < 1 || nsig == 0) return 0;
+    if (!signals) return ft8_fail("NULL array argument");
+    const size_t total = (size_t)nclips * nsig;
+    hdr->resize(total);
+    for (size_t g = 0; g < total; ++g) {
+        const ft8gpu_synth_signal &sg = signals[g];
+        const int clip = (int)(g / nsig), s = (int)(g % nsig);
+        if (!isfinite(sg.f0_hz) || !isfinite(sg.t0_s) || !isfinite(sg.amplitude))
+            return ft8_fail("signal %d of clip %d: f0_hz, t0_s or amplitude is not finite", s, clip);
+        if (mode == FT8GPU_GFSK_AUDIO && (sg.f0_hz < 0.0f || sg.f0_hz >= (float)rate))
+            return ft8_fail("signal %d of clip %d: f0_hz %g out of range [0, %d)", s, clip, (double)sg.f0_hz, rate);
+        if (fabsf(sg.f0_hz) >= (float)rate)
+            return ft8_fail("signal %d of clip %d: f0_hz %g out of range (-%d, %d)", s, clip, (double)sg.f0_hz, rate, rate);
+        if (fabsf(sg.t0_s) > 60.0f) return ft8_fail("signal %d of clip %d: t0_s %g out of range [-60, 60]", s, clip, (double)sg.t0_s);
+        GfskHeader &h = (*hdr)[g];
+        h.step = (uint32_t)(unsigned long long)llrint((double)sg.f0_hz * 4294967296.0 / (double)rate);
+        h.start = (int32_t)lrintf(sg.t0_s * (float)rate);
+        h.amplitude = sg.amplitude;
+        for (int j = 0; j < FT8GPU_NN; ++j) {
+            if (sg.tones[j] > 7) return ft8_fail("signal %d of clip %d: tone %d is %d, above 7", s, clip, j, (int)sg.tones[j]);
+            h.e[j + 1] = sg.tones[j];
+        }
+        h.e[0] = sg.tones[0];
+        h.e[80] = sg.tones[FT8GPU_NN - 1];
+        h.e[81] = h.e[82] = h.e[83] = 0;
+    }
+    return 0;
+}
+
+int synth_gfsk(ft8gpu_ctx *c, int mode, const ft8gpu_synth_signal *signals, int nclips, int nsig, int nsamples, float noise_sigma,
+               uint64_t seed, uint64_t first, float peak, int format, void *out, int flags) {
+    std::vector<GfskHeader> hdr;
+    if (nclips >= 0 && check_gfsk_args(mode, signals, nclips, nsig, nsamples, noise_sigma, peak, format, &hdr)) return -1;
+    CHECK_COMMON(c, nclips);
+    if (nclips == 0) return 0;
+    if (!out) return ft8_fail("NULL array argument");
+    const bool dev = flags & FT8GPU_DEVICE_PTRS;
+    const bool iq = mode == FT8GPU_GFSK_IQ;
+    const size_t len = iq ? 2 * (size_t)kNSamples : (size_t)nsamples;               // values per clip
+    const size_t out_bytes = len * (format == FT8GPU_AUDIO_S16 ? sizeof(int16_t) : sizeof(float));
+    const int ntiles = gfsk_tiles(mode, nsamples);
+    const size_t mf = (size_t)c->max_frames;
+    if (ensure_gfsk_tables(c)) return -1;
+    if (!dev && gfsk_alloc(&c->d_gfsk_out, mf * kClipFloats * sizeof(float))) return -1;
+    if (peak > 0.0f && gfsk_alloc(&c->d_gfsk_max, mf * kGfskMaxTiles * sizeof(float))) return -1;
+    if (peak > 0.0f && format == FT8GPU_AUDIO_S16 && gfsk_alloc(&c->d_gfsk_x, mf * kClipFloats * sizeof(float))) return -1;
+    HIP_TRY(hipStreamSynchronize(c->stream));               // an earlier call's launches may still read the headers
+    if (!hdr.empty()) {
+        if (grow_buffer((void **)&c->d_gfsk_hdr, &c->gfsk_hdr_cap, hdr.size() * sizeof(GfskHeader))) return -1;
+        HIP_TRY(hipMemcpyAsync(c->d_gfsk_hdr, hdr.data(), hdr.size() * sizeof(GfskHeader), hipMemcpyHostToDevice, c->stream));
+        HIP_TRY(hipStreamSynchronize(c->stream));           // hdr is gone when this call returns
+    }
+    const StageArg a[] = { { out, c->d_gfsk_out, out_bytes, kOut } };
+    size_t done = 0;                                        // clips of the chunks before this one
+    return for_each_chunk(c, nclips, flags & FT8GPU_DEVICE_PTRS, a, [&](int n, void *const *p) {
+        const GfskHeader *h = c->d_gfsk_hdr + done * (size_t)nsig;
+        const uint64_t g0 = first + (uint64_t)done;
+        done += (size_t)n;
+        if (!(peak > 0.0f)) {
+            HIP_TRY(launch_gfsk(mode, format, h, n, nsig, nsamples, c->d_gfsktab, noise_sigma, seed, g0, p[0], nullptr, c->stream));
+            return 0;
+        }
+        float *x = format == FT8GPU_AUDIO_S16 ? c->d_gfsk_x : (float *)p[0];
+        HIP_TRY(launch_gfsk(mode, FT8GPU_AUDIO_F32, h, n, nsig, nsamples, c->d_gfsktab, noise_sigma, seed, g0, x, c->d_gfsk_max, c->stream));
+        HIP_TRY(launch_gfsk_normalise(format, x, c->d_gfsk_max, n, (int)len, ntiles, peak, p[0], c->stream));
+        return 0;
+    });
+}
+
+}  // namespace
+
+void free_gfsk_buffers(ft8gpu_ctx *c) {
+    void *bufs[] = { c->d_gfsktab, c->d_gfsk_hdr, c->d_gfsk_x, c->d_gfsk_out, c->d_gfsk_max };
+    for (void *b : bufs) if (b) (void)hipFree(b);
+}
+
+extern "C" {
+
+int ft8gpu_synth_gfsk_frames(ft8gpu_ctx *c, const ft8gpu_synth_signal *signals, int nframes, int nsig, float noise_sigma, uint64_t seed,
+                             uint64_t first_frame, float peak, float *iq_out, int flags) {
+    return synth_gfsk(c, FT8GPU_GFSK_IQ, signals, nframes, nsig, kNSamples, noise_sigma, seed, first_frame, peak, FT8GPU_AUDIO_F32,
+                      iq_out, flags);
+}
+
+int ft8gpu_synth_gfsk_audio(ft8gpu_ctx *c, const ft8gpu_synth_signal *signals, int nclips, int nsig, int nsamples, float noise_sigma,
+                            uint64_t seed, uint64_t first_clip, float peak, int format, void *pcm_out, int flags) {
+    return synth_gfsk(c, FT8GPU_GFSK_AUDIO, signals, nclips, nsig, nsamples, noise_sigma, seed, first_clip, peak, format, pcm_out, flags);
+}
+
+}  // extern "C"

@@ -1,6 +1,6 @@
 // ft8gpu_ctx.h -- the context object and the helpers every host-side translation unit of the C ABI shares: api_context.hip,
 // api_pipeline.hip, api_multi.hip, api_stages.hip, api_messages.hip, api_multipass.hip, api_osd.hip, api_ap.hip, api_glue.hip,
-// api_rx_stream.hip, api_callhash.hip, api_match.hip, api_combine.hip, api_refine.hip, api_subtract.hip, api_demod.hip, api_audio.hip.  Not installed.
+// api_rx_stream.hip, api_callhash.hip, api_match.hip, api_combine.hip, api_refine.hip, api_subtract.hip, api_demod.hip, api_audio.hip, api_gfsk.hip.  Not installed.
 #pragma once
 #include "ft8gpu_internal.h"
 
@@ -96,6 +96,12 @@ struct ft8gpu_ctx {
     ft8gpu_message *d_audio_bmsgs = nullptr;   // the bands' records [max_frames][4][50] and counts [max_frames][4],
     int32_t *d_audio_bn = nullptr;
     ft8gpu_message *d_audio_msgs = nullptr;    // and host-pointer staging of the merged records [max_frames][200]
+    struct GfskTables *d_gfsktab = nullptr;    // GFSK synthesiser, lazily on its first call: the constant tables,
+    struct GfskHeader *d_gfsk_hdr = nullptr;   //   the signal headers of a call (grown as needed),
+    size_t gfsk_hdr_cap = 0;
+    float *d_gfsk_x = nullptr;             //   the floats before normalisation where the output is int16 [max_frames][180000],
+    void *d_gfsk_out = nullptr;            //   host-pointer staging of the output [max_frames][180000] floats (I/Q: [2][48000]),
+    float *d_gfsk_max = nullptr;           //   and the tiles' maxima [max_frames][22]
     ft8gpu_synth_signal *d_sigs = nullptr;
     size_t sigs_cap = 0;
     void *d_rx_sums = nullptr, *d_rx_p2 = nullptr;     // RX front end scratch
@@ -253,6 +259,8 @@ void free_subtract_buffers(ft8gpu_ctx *c);
 int ensure_subtract_tables(ft8gpu_ctx *c);
 // api_audio.hip: frees the audio front end's buffers (ft8gpu_destroy)
 void free_audio_buffers(ft8gpu_ctx *c);
+// api_gfsk.hip: frees the GFSK synthesiser's buffers (ft8gpu_destroy)
+void free_gfsk_buffers(ft8gpu_ctx *c);
 // ft8gpu_decode_batch with one more form: kIqOnDevice, frames resident on the context's GPU and records to host arrays
 // (used by the multi-GPU entries; not part of the ABI, whose entry passes on FT8GPU_DEVICE_PTRS only)
 constexpr int kIqOnDevice = 2;
