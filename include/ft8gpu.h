@@ -113,7 +113,9 @@ typedef struct {
  * holds the context's mutex, so two host threads calling into ONE context serialise (use one context
  * per thread / per GPU for concurrency: contexts are independent, unlike the reference's process-global
  * FFTW state, rtlsdr_ft8d.c:57-60).  Entry points make the context's GPU current for their duration and
- * restore the caller's current device before returning. */
+ * restore the caller's current device before returning.
+ * ft8gpu_destroy waits for the context's streams and frees everything the context allocated.  It takes no lock: destroying a
+ * context while any entry on it is still running (on another thread, or inside a multi-context call) is a caller error. */
 int  ft8gpu_create(ft8gpu_ctx **out, int device, int max_frames, const ft8gpu_params *params);
 void ft8gpu_destroy(ft8gpu_ctx *ctx);
 /* Use an existing hipStream_t (passed as void*) for all work of this context.  NULL = the context

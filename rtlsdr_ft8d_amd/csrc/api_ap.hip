@@ -10,13 +10,9 @@ constexpr int kApMaxHard = kLdpcN, kOsdMaxOrder = 2;
 // the constant tables, the info records and the host form's staging of status_out, on the first AP call
 // (ft8gpu_create's footprint is unchanged)
 int ensure_ap_buffers(ft8gpu_ctx *c) {
-    if (!c->ap_tables) {
-        HIP_TRY(ap_tables_init(c->stream));
-        HIP_TRY(hipStreamSynchronize(c->stream));
-        c->ap_tables = true;
-    }
-    if (!c->d_nap) HIP_TRY(hipMalloc(&c->d_nap, (size_t)c->max_frames * sizeof(int32_t)));
-    return follow_cap(c, &c->ap_cap, (void **)&c->d_ap_info, sizeof(ft8gpu_ap_info), (void **)&c->d_ap_out, sizeof(ft8gpu_decode_status));
+    if (tables_once(c, &c->ap_tables, ap_tables_init)) return -1;
+    if (c->mem.once(&c->d_nap, (size_t)c->max_frames * sizeof(int32_t), "the counts before AP")) return -1;
+    return follow_cap(c, &c->d_ap_info, &c->d_ap_out, &c->ap_cap, "the AP records");
 }
 
 int popcount8(unsigned v) { int n = 0; for (; v; v &= v - 1) ++n; return n; }
@@ -53,11 +49,6 @@ int ap_step(const Chunk &k, const PassSet &f, int col, const ft8gpu_ap_params *q
 }
 
 }  // namespace
-
-void free_ap_buffers(ft8gpu_ctx *c) {
-    void *bufs[] = { c->d_ap_info, c->d_ap_out, c->d_nap };
-    for (void *b : bufs) if (b) (void)hipFree(b);
-}
 
 extern "C" {
 

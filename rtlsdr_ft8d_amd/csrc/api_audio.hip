@@ -7,42 +7,22 @@
 #include "audio.h"
 #include "ft8gpu_ctx.h"
 
-#include <stdlib.h>
-
 namespace {
 
 constexpr size_t kFrameFloats = 2 * (size_t)kNSamples;
 constexpr size_t kFrameBytes = kFrameFloats * sizeof(float);
 
-// a failed allocation is reported and forgotten, so that the launches of a later call do not see it
-template <class T>
-int audio_alloc(T **p, size_t bytes) {
-    if (*p) return 0;
-    const hipError_t e = hipMalloc(p, bytes);
-    if (e == hipSuccess) return 0;
-    *p = nullptr;
-    (void)hipGetLastError();
-    return ft8_fail("audio front end: hipMalloc(%zu) failed: %s", bytes, hipGetErrorString(e));
+int ensure_audio_tables(ft8gpu_ctx *c) {
+    return c->mem.table(&c->d_audiotab, "the audio tables", [](AudioTables *h) {
+        ft8gpu_audio_taps(h->h);
+        ft8gpu_audio_mixer(&h->wm[0].x);
+        return 0;
+    });
 }
 
-int ensure_audio_tables(ft8gpu_ctx *c) {
-    if (c->d_audiotab) return 0;
-    AudioTables *h = (AudioTables *)calloc(1, sizeof(AudioTables));
-    if (!h) return ft8_fail("out of memory");
-    ft8gpu_audio_taps(h->h);
-    ft8gpu_audio_mixer(&h->wm[0].x);
-    AudioTables *d = nullptr;
-    hipError_t e = hipMalloc(&d, sizeof(AudioTables));
-    if (e == hipSuccess) e = hipMemcpy(d, h, sizeof(AudioTables), hipMemcpyHostToDevice);
-    free(h);
-    if (e != hipSuccess) {
-        if (d) (void)hipFree(d);
-        (void)hipGetLastError();
-        return ft8_fail("audio tables: %s", hipGetErrorString(e));
-    }
-    c->d_audiotab = d;
-    return 0;
-}
+// the buffers of the audio front end, each on the first call that needs it
+int audio_pcm(ft8gpu_ctx *c) { return c->mem.once(&c->d_audio_pcm, (size_t)c->max_frames * FT8GPU_AUDIO_NSAMPLES * sizeof(float), "staging of the clips"); }
+int audio_iq(ft8gpu_ctx *c) { return c->mem.once(&c->d_audio_iq, (size_t)c->max_frames * kFrameBytes, "the audio front end's frames"); }
 
 // the refusals of both entries, before anything is enqueued
 int check_audio_args(int format, int nsamples, const int32_t *base_bin, int nbands, AudioBands *bands) {
@@ -65,11 +45,6 @@ size_t sample_bytes(int format) { return format == FT8GPU_AUDIO_S16 ? sizeof(int
 
 }  // namespace
 
-void free_audio_buffers(ft8gpu_ctx *c) {
-    void *bufs[] = { c->d_audiotab, c->d_audio_pcm, c->d_audio_iq, c->d_audio_bmsgs, c->d_audio_bn, c->d_audio_msgs };
-    for (void *b : bufs) if (b) (void)hipFree(b);
-}
-
 extern "C" {
 
 int ft8gpu_audio_frames(ft8gpu_ctx *c, const void *pcm, int format, int nclips, int nsamples, const int32_t *base_bin, int nbands,
@@ -82,9 +57,7 @@ int ft8gpu_audio_frames(ft8gpu_ctx *c, const void *pcm, int format, int nclips, 
     const bool dev = flags & FT8GPU_DEVICE_PTRS;
     if (dev && ((uintptr_t)iq_out & 15) != 0) return ft8_fail("iq_out must be 16-byte aligned");
     if (ensure_audio_tables(c)) return -1;
-    const size_t mf = (size_t)c->max_frames;
-    if (!dev && (audio_alloc(&c->d_audio_pcm, mf * FT8GPU_AUDIO_NSAMPLES * sizeof(float)) || audio_alloc(&c->d_audio_iq, mf * kFrameBytes)))
-        return -1;
+    if (!dev && (audio_pcm(c) || audio_iq(c))) return -1;
     const StageArg a[] = { { pcm, c->d_audio_pcm, (size_t)nsamples * sample_bytes(format), kIn } };
     size_t done = 0;                                        // frames of the chunks before this one
     return for_each_chunk(c, nclips, flags & FT8GPU_DEVICE_PTRS, a, [&](int n, void *const *p) {
@@ -116,11 +89,10 @@ int ft8gpu_decode_audio(ft8gpu_ctx *c, const void *pcm, int format, int nclips, 
     if (ensure_audio_tables(c)) return -1;
     const size_t mf = (size_t)c->max_frames;
     constexpr size_t kBandMsgBytes = kMaxMessages * sizeof(ft8gpu_message);
-    if (audio_alloc(&c->d_audio_iq, mf * kFrameBytes) || audio_alloc(&c->d_audio_bmsgs, mf * FT8GPU_AUDIO_MAX_BANDS * kBandMsgBytes) ||
-        audio_alloc(&c->d_audio_bn, mf * FT8GPU_AUDIO_MAX_BANDS * sizeof(int32_t)))
+    if (audio_iq(c) || c->mem.once(&c->d_audio_bmsgs, mf * FT8GPU_AUDIO_MAX_BANDS * kBandMsgBytes, "the bands' records") ||
+        c->mem.once(&c->d_audio_bn, mf * FT8GPU_AUDIO_MAX_BANDS * sizeof(int32_t), "the bands' counts"))
         return -1;
-    if (!dev && (audio_alloc(&c->d_audio_pcm, mf * FT8GPU_AUDIO_NSAMPLES * sizeof(float)) ||
-                 audio_alloc(&c->d_audio_msgs, mf * FT8GPU_AUDIO_MAX_BANDS * kBandMsgBytes)))
+    if (!dev && (audio_pcm(c) || c->mem.once(&c->d_audio_msgs, mf * FT8GPU_AUDIO_MAX_BANDS * kBandMsgBytes, "staging of the merged records")))
         return -1;
     // slots past a clip's count keep the caller's bytes (msgs is uploaded in the host form)
     const StageArg a[] = { { pcm, c->d_audio_pcm, (size_t)nsamples * sample_bytes(format), kIn },

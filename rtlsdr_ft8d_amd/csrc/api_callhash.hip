@@ -5,8 +5,8 @@
 // A receiver is sequential in its slots and independent of every other receiver, so work is cut along exactly those two
 // lines (Pieces, ft8gpu_ctx.h), each run of slots starting from the state the previous one left.  Either cut leaves the bytes of
 // one launch.  The host form stages a piece through for_each_chunk with a receiver as its unit; records and counts use the
-// staging buffers of the messages path, the resolved records and the states (80 KB each) the context's RX buffers
-// (ensure_rx_scratch).
+// staging buffers of the messages path, the states (80 KB each) and the resolved records the context's scratch blocks 1 and 2
+// (ensure_scratch).
 #include "callhash.h"
 #include "ft8gpu_ctx.h"
 
@@ -32,15 +32,15 @@ int ft8gpu_resolve_calls(ft8gpu_ctx *c, const ft8gpu_message *msgs, const int32_
         return ft8_fail("msgs, state and resolved must be 16-byte aligned");
     if (dev && ((uintptr_t)n_msgs & 3) != 0) return ft8_fail("n_msgs must be 4-byte aligned");
     const Pieces cut(nstreams, nslots, dev ? kNoBound : c->max_frames);      // the device form needs no staging: nothing bounds a piece
-    if (!dev && (ensure_rx_scratch(c, 0, (size_t)cut.rg_max * sizeof(ft8gpu_callhash_state),
+    if (!dev && (ensure_scratch(c, 0, (size_t)cut.rg_max * sizeof(ft8gpu_callhash_state),
                                    (size_t)cut.rg_max * cut.ns_max * kMaxMessages * sizeof(ft8gpu_resolved), 0) || ensure_msgs_staging(c)))
         return -1;
     return cut.each([&](int r0, int rg, int, int ns, size_t f0) {
         // slots at and above a frame's count keep the caller's bytes (resolved is uploaded in the host form)
         const StageArg a[] = { { msgs + f0 * kMaxMessages, c->d_msgs, (size_t)ns * kMaxMessages * sizeof(ft8gpu_message), kIn },
                                { n_msgs + f0, c->d_nres, (size_t)ns * sizeof(int32_t), kIn },
-                               { state + r0, c->d_rx_p2, sizeof(ft8gpu_callhash_state), kInOut },
-                               { resolved + f0 * kMaxMessages, c->d_rx_iq, (size_t)ns * kMaxMessages * sizeof(ft8gpu_resolved), kInOut } };
+                               { state + r0, c->d_scratch[1], sizeof(ft8gpu_callhash_state), kInOut },
+                               { resolved + f0 * kMaxMessages, c->d_scratch[2], (size_t)ns * kMaxMessages * sizeof(ft8gpu_resolved), kInOut } };
         return for_each_chunk(c, rg, flags & FT8GPU_DEVICE_PTRS, a, [&](int n, void *const *p) {
             HIP_TRY(launch_callhash((const ft8gpu_message *)p[0], (const int32_t *)p[1], n, ns, (ft8gpu_callhash_state *)p[2],
                                     max_age, (ft8gpu_resolved *)p[3], c->stream));

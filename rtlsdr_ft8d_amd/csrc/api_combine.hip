@@ -2,9 +2,9 @@
 // and the whole path ft8gpu_decode_messages_combined (DESIGN.md "Soft-bit memory"; the kernels are combine.hip, the reset
 // of a state is plain C in ft8_pack.c).
 //
-// Buffers.  As for the expected messages, everything this file needs beyond the messages path lives in the context's RX
-// buffers (ensure_rx_scratch): the update kernel's read-only copy of the entry states (rx_sums), the host form's staging of the
-// states (rx_p2) and of status_out (rx_iq), the info records (rx_raw).  A state is 92 176 bytes, so a call over n receivers
+// Buffers.  As for the expected messages, everything this file needs beyond the messages path lives in the context's
+// scratch blocks (ensure_scratch): the update kernel's read-only copy of the entry states (block 0), the host form's staging of
+// the states (1) and of status_out (2), the info records (3).  A state is 92 176 bytes, so a call over n receivers
 // needs n of them once or twice; they grow on the first call that needs them.
 //
 // Update.  The rule forms every sum from the state as it was at entry to the slot, while the ring may overwrite a partner in
@@ -29,20 +29,16 @@ int check_combine_args(int min_agree, int store_per_slot) {
 
 // the kernels' constant tables, on the context's first call
 int ensure_combine_tables(ft8gpu_ctx *c) {
-    if (c->combine_tables) return 0;
-    HIP_TRY(combine_tables_init(c->stream));
-    HIP_TRY(hipStreamSynchronize(c->stream));                       // the upload reads a static host object
-    c->combine_tables = true;
-    return 0;
+    return tables_once(c, &c->combine_tables, combine_tables_init);
 }
 
 // one slot of n receivers: states (device memory) in-out, through the read-only copy in the context's buffer
 int update_slot(ft8gpu_ctx *c, const uint8_t *mag, const ft8gpu_candidate *cands, const int32_t *counts,
                 const ft8gpu_decode_status *status, const ft8gpu_combine_info *info, int n, ft8gpu_softmem_state *states,
                 int store_per_slot) {
-    HIP_TRY(hipMemcpyAsync(c->d_rx_sums, states, (size_t)n * kStateBytes, hipMemcpyDeviceToDevice, c->stream));
+    HIP_TRY(hipMemcpyAsync(c->d_scratch[0], states, (size_t)n * kStateBytes, hipMemcpyDeviceToDevice, c->stream));
     HIP_TRY(launch_softmem_update(mag, cands, counts, status, info, n, c->params.max_candidates,
-                                  (const ft8gpu_softmem_state *)c->d_rx_sums, states, store_per_slot, c->stream));
+                                  (const ft8gpu_softmem_state *)c->d_scratch[0], states, store_per_slot, c->stream));
     return 0;
 }
 
@@ -63,16 +59,16 @@ int ft8gpu_combine_candidates(ft8gpu_ctx *c, const uint8_t *mag, const ft8gpu_ca
     if (ensure_messages_buffers(c) || ensure_combine_tables(c)) return -1;
     const int mc = c->params.max_candidates;
     const size_t piece = (size_t)(nframes < c->max_frames ? nframes : c->max_frames);
-    if (ensure_rx_scratch(c, 0, dev ? 0 : piece * kStateBytes, dev ? 0 : piece * mc * sizeof(ft8gpu_decode_status),
+    if (ensure_scratch(c, 0, dev ? 0 : piece * kStateBytes, dev ? 0 : piece * mc * sizeof(ft8gpu_decode_status),
                           dev ? 0 : piece * mc * sizeof(ft8gpu_combine_info)))
         return -1;
     // records at and behind a frame's count keep the caller's bytes (both outputs are uploaded in the host form)
     const StageArg a[] = { { mag, c->d_mag, kMagArray, kIn }, { cands, c->d_cands, mc * sizeof(ft8gpu_candidate), kIn },
                            { counts, c->d_counts, sizeof(int32_t), kIn },
                            { status_in, c->d_status, mc * sizeof(ft8gpu_decode_status), kIn },
-                           { states, c->d_rx_p2, kStateBytes, kIn },
-                           { status_out, c->d_rx_iq, mc * sizeof(ft8gpu_decode_status), kInOut },
-                           { info, c->d_rx_raw, mc * sizeof(ft8gpu_combine_info), kInOut } };
+                           { states, c->d_scratch[1], kStateBytes, kIn },
+                           { status_out, c->d_scratch[2], mc * sizeof(ft8gpu_decode_status), kInOut },
+                           { info, c->d_scratch[3], mc * sizeof(ft8gpu_combine_info), kInOut } };
     return for_each_chunk(c, nframes, flags & FT8GPU_DEVICE_PTRS, a, [&](int n, void *const *p) {
         HIP_TRY(launch_combine((const uint8_t *)p[0], (const ft8gpu_candidate *)p[1], (const int32_t *)p[2],
                                (const ft8gpu_decode_status *)p[3], (ft8gpu_decode_status *)p[5], (ft8gpu_combine_info *)p[6], n, mc,
@@ -93,13 +89,13 @@ int ft8gpu_softmem_update(ft8gpu_ctx *c, const uint8_t *mag, const ft8gpu_candid
     if (dev && ((uintptr_t)states & 15) != 0) return ft8_fail("states must be 16-byte aligned");
     const int mc = c->params.max_candidates;
     const size_t piece = (size_t)(nframes < c->max_frames ? nframes : c->max_frames);
-    if (ensure_rx_scratch(c, piece * kStateBytes, dev ? 0 : piece * kStateBytes, 0, dev ? 0 : piece * mc * sizeof(ft8gpu_combine_info)))
+    if (ensure_scratch(c, piece * kStateBytes, dev ? 0 : piece * kStateBytes, 0, dev ? 0 : piece * mc * sizeof(ft8gpu_combine_info)))
         return -1;
     const StageArg a[] = { { mag, c->d_mag, kMagArray, kIn }, { cands, c->d_cands, mc * sizeof(ft8gpu_candidate), kIn },
                            { counts, c->d_counts, sizeof(int32_t), kIn },
                            { status, c->d_status, mc * sizeof(ft8gpu_decode_status), kIn },
-                           { info, c->d_rx_raw, mc * sizeof(ft8gpu_combine_info), kIn },
-                           { states, c->d_rx_p2, kStateBytes, kInOut } };
+                           { info, c->d_scratch[3], mc * sizeof(ft8gpu_combine_info), kIn },
+                           { states, c->d_scratch[1], kStateBytes, kInOut } };
     return for_each_chunk(c, nframes, flags & FT8GPU_DEVICE_PTRS, a, [&](int n, void *const *p) {
         return update_slot(c, (const uint8_t *)p[0], (const ft8gpu_candidate *)p[1], (const int32_t *)p[2],
                            (const ft8gpu_decode_status *)p[3], (const ft8gpu_combine_info *)p[4], n, (ft8gpu_softmem_state *)p[5],
@@ -123,7 +119,7 @@ int ft8gpu_decode_messages_combined(ft8gpu_ctx *c, const float *iq, int nstreams
     if (dev && (((uintptr_t)msgs | (uintptr_t)state | (uintptr_t)iq) & 15) != 0) return ft8_fail("iq, msgs and state must be 16-byte aligned");
     if (ensure_messages_buffers(c) || ensure_combine_tables(c)) return -1;
     const int mc = c->params.max_candidates, rg_max = Pieces(nstreams, nslots, c->max_frames).rg_max;
-    if (ensure_rx_scratch(c, (size_t)rg_max * kStateBytes, dev ? 0 : (size_t)rg_max * kStateBytes, 0,
+    if (ensure_scratch(c, (size_t)rg_max * kStateBytes, dev ? 0 : (size_t)rg_max * kStateBytes, 0,
                           (size_t)rg_max * mc * sizeof(ft8gpu_combine_info)))
         return -1;
     const int gate = params->min_agree, store = params->store_per_slot;
@@ -133,7 +129,7 @@ int ft8gpu_decode_messages_combined(ft8gpu_ctx *c, const float *iq, int nstreams
                                       [=](size_t o, int rg, void *st, ft8gpu_message *dm, int32_t *pn, int32_t *pb) {
         ft8gpu_softmem_state *states = (ft8gpu_softmem_state *)st;
         ft8gpu_decode_status *status = c->d_status + o * mc;
-        ft8gpu_combine_info *inf = (ft8gpu_combine_info *)c->d_rx_raw;
+        ft8gpu_combine_info *inf = (ft8gpu_combine_info *)c->d_scratch[3];
         HIP_TRY(launch_combine(c->d_mag + o * kMagArray, c->d_cands + o * mc, c->d_counts + o, status, status, inf, rg, mc, states,
                                max_age, gate, c->params.ldpc_iters, force_ieee(c), s));
         HIP_TRY(launch_append(c->d_mag + o * kMagArray, c->d_base + o * 2 * kNumBin, c->d_cands + o * mc, c->d_counts + o, status,

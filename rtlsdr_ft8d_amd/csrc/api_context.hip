@@ -8,7 +8,6 @@
 #include <new>
 #include <stdarg.h>
 #include <stdio.h>
-#include <stdlib.h>
 #include <string.h>
 #include <vector>
 
@@ -84,21 +83,7 @@ int build_tables(Ft8Tables *t) {
 // All or nothing: both new buffers exist before the old pair is released, so a failed allocation (ft8gpu_set_params growing
 // the cap under memory pressure) leaves the context exactly as it was -- old buffers, old cap_candidates -- and returns -1.
 int alloc_candidate_buffers(ft8gpu_ctx *c, int cap) {
-    ft8gpu_candidate *cands = nullptr;
-    ft8gpu_decode_status *status = nullptr;
-    if (hipMalloc(&cands, (size_t)c->max_frames * cap * sizeof(ft8gpu_candidate)) != hipSuccess ||
-        hipMalloc(&status, (size_t)c->max_frames * cap * sizeof(ft8gpu_decode_status)) != hipSuccess) {
-        (void)hipGetLastError();
-        if (cands) (void)hipFree(cands);
-        return ft8_fail("out of device memory for %d candidates x %d frames (the context keeps its %d-candidate buffers)", cap, c->max_frames,
-                        c->cap_candidates);
-    }
-    if (c->d_cands) (void)hipFree(c->d_cands);          // hipFree waits for work that still uses the old pair
-    if (c->d_status) (void)hipFree(c->d_status);
-    c->d_cands = cands;
-    c->d_status = status;
-    c->cap_candidates = cap;
-    return 0;
+    return c->mem.pair_kept(&c->d_cands, &c->d_status, &c->cap_candidates, cap, (size_t)c->max_frames, "the candidate buffers");
 }
 
 int check_params(const ft8gpu_params *p) {
@@ -169,7 +154,7 @@ hipError_t create_side_stream(hipStream_t *s) { return hipStreamCreateWithFlags(
 int probe_streams(ft8gpu_ctx *c) {
     c->overlap_ok = false;
     c->overlap_why[0] = 0;
-    if (!c->d_probe) HIP_TRY(hipMalloc(&c->d_probe, 2 * sizeof(int)));
+    if (c->mem.once(&c->d_probe, 2 * sizeof(int), "the stream probe's flags")) return -1;
     std::vector<hipStream_t> rejected;
     auto cleanup = [&] { for (hipStream_t r : rejected) (void)hipStreamDestroy(r); rejected.clear(); };
     int rc = 1;
@@ -220,23 +205,19 @@ static int create_body(ft8gpu_ctx *c) {
     // (the upload stream of the host-buffer path is created on first use: a context that only sees device pointers
     // keeps its three streams on three hardware queues of their own)
     for (auto &e : c->copied) HIP_TRY(hipEventCreateWithFlags(&e, hipEventDisableTiming));
-    Ft8Tables *h = (Ft8Tables *)malloc(sizeof(Ft8Tables));
-    if (!h) return ft8_fail("out of host memory");
-    if (build_tables(h)) { free(h); return -1; }
-    hipError_t e = hipMalloc(&c->d_tab, sizeof(Ft8Tables));
-    if (e == hipSuccess) e = hipMemcpy(c->d_tab, h, sizeof(Ft8Tables), hipMemcpyHostToDevice);
-    free(h);
-    if (e != hipSuccess) return ft8_fail("uploading the constant tables failed: %s", hipGetErrorString(e));
+    if (c->mem.table(&c->d_tab, "the constant tables", build_tables)) return -1;
     HIP_TRY(decode_tables_init(c->stream));
 
     const size_t F = (size_t)c->max_frames;
-    HIP_TRY(hipMalloc(&c->d_mag, F * kMagArray));
-    HIP_TRY(hipMalloc(&c->d_lists, F * kSublistsPerFrame * kSublistCap * sizeof(uint32_t)));
-    HIP_TRY(hipMalloc(&c->d_list_counts, F * kSublistsPerFrame * sizeof(int32_t)));
-    HIP_TRY(hipMalloc(&c->d_counts, F * sizeof(int32_t)));
-    HIP_TRY(hipMalloc(&c->d_decodes, F * kMaxMessages * sizeof(struct decoder_results)));
-    HIP_TRY(hipMalloc(&c->d_nres, F * sizeof(int32_t)));
-    if (alloc_candidate_buffers(c, c->params.max_candidates < 120 ? 120 : c->params.max_candidates)) return -1;
+    CtxMem &m = c->mem;
+    if (m.once(&c->d_mag, F * kMagArray, "the waterfall") ||
+        m.once(&c->d_lists, F * kSublistsPerFrame * kSublistCap * sizeof(uint32_t), "the sync sublists") ||
+        m.once(&c->d_list_counts, F * kSublistsPerFrame * sizeof(int32_t), "the sublist counts") ||
+        m.once(&c->d_counts, F * sizeof(int32_t), "the candidate counts") ||
+        m.once(&c->d_decodes, F * kMaxMessages * sizeof(struct decoder_results), "the spot records") ||
+        m.once(&c->d_nres, F * sizeof(int32_t), "the record counts") ||
+        alloc_candidate_buffers(c, c->params.max_candidates < 120 ? 120 : c->params.max_candidates))
+        return -1;
     HIP_TRY(hipStreamSynchronize(c->stream));
     if (probe_streams(c)) return -1;
     return 0;
@@ -278,17 +259,7 @@ void ft8gpu_destroy(ft8gpu_ctx *c) {
     struct Restore { int d; ~Restore() { if (d >= 0) (void)hipSetDevice(d); } } restore{ prev };
     (void)hipSetDevice(c->device);
     if (c->stream) (void)hipStreamSynchronize(c->stream);
-    void *bufs[] = { c->d_tab, c->d_iq, c->d_mag, c->d_lists, c->d_list_counts, c->d_cands, c->d_counts,
-                     c->d_status, c->d_decodes, c->d_nres, c->d_scores, c->d_sigs,
-                     c->d_rx_sums, c->d_rx_p2, c->d_rx_raw, c->d_rx_iq,
-                     c->d_rep, c->d_rep_len, c->d_rep_time, c->d_probe, c->d_base, c->d_msgtab, c->d_msgs };
-    for (void *b : bufs) if (b) (void)hipFree(b);
-    free_multipass_buffers(c);
-    free_osd_buffers(c);
-    free_ap_buffers(c);
-    free_subtract_buffers(c);
-    free_audio_buffers(c);
-    free_gfsk_buffers(c);
+    c->mem.release_all();                       // hipFree waits for work that still uses a block
     if (c->side) (void)hipStreamSynchronize(c->side);
     for (auto &slot : c->ev) for (auto &e : slot) if (e) (void)hipEventDestroy(e);
     for (auto &e : c->dep) if (e) (void)hipEventDestroy(e);

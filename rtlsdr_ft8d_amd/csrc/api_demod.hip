@@ -1,9 +1,9 @@
 // api_demod.hip -- host side of the demodulation from the I/Q samples: the stage entry ft8gpu_demod_candidates and the whole
 // path ft8gpu_decode_messages_demod (DESIGN.md "Demodulation from the I/Q samples"; the kernels are demod.hip).
 //
-// Both entries cut the frames with for_each_chunk.  Everything beyond the messages path lives in the context's RX buffers
-// (ensure_rx_scratch), which no other entry uses while this one holds the context's mutex: the info records (rx_raw), the host
-// form's staging of status_out (rx_iq), the whole path's counts before the append step (rx_sums).  w4 is the subtraction's table.
+// Both entries cut the frames with for_each_chunk.  Everything beyond the messages path lives in the context's scratch
+// blocks (ensure_scratch), which no other entry uses while this one holds the context's mutex: the info records (block 3), the
+// host form's staging of status_out (2), the whole path's counts before the append step (0).  w4 is the subtraction's table.
 #include "demod.h"
 #include "ft8gpu_ctx.h"
 
@@ -25,11 +25,7 @@ int check_demod_args(const ft8gpu_ctx *c, const ft8gpu_demod_params *p) {
 // the kernels' constant tables, on the context's first call
 int ensure_demod_tables(ft8gpu_ctx *c) {
     if (ensure_subtract_tables(c)) return -1;
-    if (c->demod_tables) return 0;
-    HIP_TRY(demod_tables_init(c->stream));
-    HIP_TRY(hipStreamSynchronize(c->stream));                       // the upload reads a static host object
-    c->demod_tables = true;
-    return 0;
+    return tables_once(c, &c->demod_tables, demod_tables_init);
 }
 
 }  // namespace
@@ -49,15 +45,15 @@ int ft8gpu_demod_candidates(ft8gpu_ctx *c, const float *iq, const ft8gpu_candida
     const int mc = c->params.max_candidates;
     const size_t piece = (size_t)(nframes < c->max_frames ? nframes : c->max_frames);
     if (!dev && ensure_host_staging(c)) return -1;
-    if (ensure_rx_scratch(c, 0, 0, dev ? 0 : piece * mc * sizeof(ft8gpu_decode_status), dev ? 0 : piece * mc * sizeof(ft8gpu_demod_info)))
+    if (ensure_scratch(c, 0, 0, dev ? 0 : piece * mc * sizeof(ft8gpu_decode_status), dev ? 0 : piece * mc * sizeof(ft8gpu_demod_info)))
         return -1;
     const ft8gpu_demod_params p = *params;
     // records at and behind a frame's count keep the caller's bytes (both outputs are uploaded in the host form)
     const StageArg a[] = { { iq, c->d_iq, kFrameBytes, kIn }, { cands, c->d_cands, mc * sizeof(ft8gpu_candidate), kIn },
                            { counts, c->d_counts, sizeof(int32_t), kIn },
                            { status_in, c->d_status, mc * sizeof(ft8gpu_decode_status), kIn },
-                           { status_out, c->d_rx_iq, mc * sizeof(ft8gpu_decode_status), kInOut },
-                           { info, c->d_rx_raw, mc * sizeof(ft8gpu_demod_info), kInOut } };
+                           { status_out, c->d_scratch[2], mc * sizeof(ft8gpu_decode_status), kInOut },
+                           { info, c->d_scratch[3], mc * sizeof(ft8gpu_demod_info), kInOut } };
     return for_each_chunk(c, nframes, flags & FT8GPU_DEVICE_PTRS, a, [&](int n, void *const *q) {
         HIP_TRY(launch_demod((const float *)q[0], (const ft8gpu_candidate *)q[1], (const int32_t *)q[2],
                              (const ft8gpu_decode_status *)q[3], (ft8gpu_decode_status *)q[4], (ft8gpu_demod_info *)q[5], n, mc,
@@ -78,7 +74,7 @@ int ft8gpu_decode_messages_demod(ft8gpu_ctx *c, const float *iq, int nframes, co
     if (!dev && (ensure_host_staging(c) || (n_by_stage && ensure_counts_staging(c)))) return -1;
     const int mc = c->params.max_candidates;
     const size_t piece = (size_t)(nframes < c->max_frames ? nframes : c->max_frames);
-    if (ensure_rx_scratch(c, piece * sizeof(int32_t), 0, 0, piece * mc * sizeof(ft8gpu_demod_info))) return -1;
+    if (ensure_scratch(c, piece * sizeof(int32_t), 0, 0, piece * mc * sizeof(ft8gpu_demod_info))) return -1;
     const ft8gpu_demod_params p = *params;
     // slots past a frame's count keep the caller's bytes (msgs is uploaded in the host form)
     const StageArg a[] = { { iq, c->d_iq, kFrameBytes, kIn }, { msgs, c->d_msgs, kMsgBytes, kInOut },
@@ -86,8 +82,8 @@ int ft8gpu_decode_messages_demod(ft8gpu_ctx *c, const float *iq, int nframes, co
     return for_each_chunk(c, nframes, flags & FT8GPU_DEVICE_PTRS, a, [&](int n, void *const *q) {
         const float *x = (const float *)q[0];
         ft8gpu_message *dm = (ft8gpu_message *)q[1];
-        int32_t *pn = (int32_t *)q[2], *pb = (int32_t *)q[3], *before = (int32_t *)c->d_rx_sums;
-        ft8gpu_demod_info *inf = (ft8gpu_demod_info *)c->d_rx_raw;
+        int32_t *pn = (int32_t *)q[2], *pb = (int32_t *)q[3], *before = (int32_t *)c->d_scratch[0];
+        ft8gpu_demod_info *inf = (ft8gpu_demod_info *)c->d_scratch[3];
         if (run_pipeline_messages(c, x, n, dm, pn)) return -1;
         if (pb) HIP_TRY(launch_pass_counts(pn, pb, n, 2, 0, c->stream));
         HIP_TRY(hipMemcpyAsync(before, pn, (size_t)n * sizeof(int32_t), hipMemcpyDeviceToDevice, c->stream));

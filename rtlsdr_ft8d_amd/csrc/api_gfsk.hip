@@ -9,44 +9,21 @@
 #include "ft8gpu_ctx.h"
 
 #include <math.h>
-#include <stdlib.h>
 #include <vector>
 
 namespace {
 
 constexpr size_t kClipFloats = FT8GPU_AUDIO_NSAMPLES;       // the longest output of a clip in floats (an I/Q frame takes 96000)
 
-// a failed allocation is reported and forgotten, so that the launches of a later call do not see it
-template <class T>
-int gfsk_alloc(T **p, size_t bytes) {
-    if (*p) return 0;
-    const hipError_t e = hipMalloc(p, bytes);
-    if (e == hipSuccess) return 0;
-    *p = nullptr;
-    (void)hipGetLastError();
-    return ft8_fail("GFSK synthesis: hipMalloc(%zu) failed: %s", bytes, hipGetErrorString(e));
-}
-
 int ensure_gfsk_tables(ft8gpu_ctx *c) {
-    if (c->d_gfsktab) return 0;
-    GfskTables *h = (GfskTables *)calloc(1, sizeof(GfskTables));
-    if (!h) return ft8_fail("out of memory");
-    ft8gpu_gfsk_pulse(FT8GPU_GFSK_SPS_IQ, h->q_iq);
-    ft8gpu_gfsk_pulse(FT8GPU_GFSK_SPS_AUDIO, h->q_audio);
-    ft8gpu_gfsk_twiddles(&h->gc[0].x, &h->gf[0].x);
-    ft8gpu_gfsk_ramp(FT8GPU_GFSK_SPS_IQ, h->ramp_iq);
-    ft8gpu_gfsk_ramp(FT8GPU_GFSK_SPS_AUDIO, h->ramp_audio);
-    GfskTables *d = nullptr;
-    hipError_t e = hipMalloc(&d, sizeof(GfskTables));
-    if (e == hipSuccess) e = hipMemcpy(d, h, sizeof(GfskTables), hipMemcpyHostToDevice);
-    free(h);
-    if (e != hipSuccess) {
-        if (d) (void)hipFree(d);
-        (void)hipGetLastError();
-        return ft8_fail("GFSK tables: %s", hipGetErrorString(e));
-    }
-    c->d_gfsktab = d;
-    return 0;
+    return c->mem.table(&c->d_gfsktab, "the GFSK tables", [](GfskTables *h) {
+        ft8gpu_gfsk_pulse(FT8GPU_GFSK_SPS_IQ, h->q_iq);
+        ft8gpu_gfsk_pulse(FT8GPU_GFSK_SPS_AUDIO, h->q_audio);
+        ft8gpu_gfsk_twiddles(&h->gc[0].x, &h->gf[0].x);
+        ft8gpu_gfsk_ramp(FT8GPU_GFSK_SPS_IQ, h->ramp_iq);
+        ft8gpu_gfsk_ramp(FT8GPU_GFSK_SPS_AUDIO, h->ramp_audio);
+        return 0;
+    });
 }
 
 // the refusals of both entries; on success hdr holds the nclips * nsig headers
@@ -102,12 +79,12 @@ int synth_gfsk(ft8gpu_ctx *c, int mode, const ft8gpu_synth_signal *signals, int 
     const int ntiles = gfsk_tiles(mode, nsamples);
     const size_t mf = (size_t)c->max_frames;
     if (ensure_gfsk_tables(c)) return -1;
-    if (!dev && gfsk_alloc(&c->d_gfsk_out, mf * kClipFloats * sizeof(float))) return -1;
-    if (peak > 0.0f && gfsk_alloc(&c->d_gfsk_max, mf * kGfskMaxTiles * sizeof(float))) return -1;
-    if (peak > 0.0f && format == FT8GPU_AUDIO_S16 && gfsk_alloc(&c->d_gfsk_x, mf * kClipFloats * sizeof(float))) return -1;
+    if (!dev && c->mem.once(&c->d_gfsk_out, mf * kClipFloats * sizeof(float), "staging of the GFSK output")) return -1;
+    if (peak > 0.0f && c->mem.once(&c->d_gfsk_max, mf * kGfskMaxTiles * sizeof(float), "the GFSK tiles' maxima")) return -1;
+    if (peak > 0.0f && format == FT8GPU_AUDIO_S16 && c->mem.once(&c->d_gfsk_x, mf * kClipFloats * sizeof(float), "the GFSK floats")) return -1;
     HIP_TRY(hipStreamSynchronize(c->stream));               // an earlier call's launches may still read the headers
     if (!hdr.empty()) {
-        if (grow_buffer((void **)&c->d_gfsk_hdr, &c->gfsk_hdr_cap, hdr.size() * sizeof(GfskHeader))) return -1;
+        if (c->mem.grow(&c->d_gfsk_hdr, &c->gfsk_hdr_cap, hdr.size() * sizeof(GfskHeader), "the GFSK signal headers")) return -1;
         HIP_TRY(hipMemcpyAsync(c->d_gfsk_hdr, hdr.data(), hdr.size() * sizeof(GfskHeader), hipMemcpyHostToDevice, c->stream));
         HIP_TRY(hipStreamSynchronize(c->stream));           // hdr is gone when this call returns
     }
@@ -129,11 +106,6 @@ int synth_gfsk(ft8gpu_ctx *c, int mode, const ft8gpu_synth_signal *signals, int 
 }
 
 }  // namespace
-
-void free_gfsk_buffers(ft8gpu_ctx *c) {
-    void *bufs[] = { c->d_gfsktab, c->d_gfsk_hdr, c->d_gfsk_x, c->d_gfsk_out, c->d_gfsk_max };
-    for (void *b : bufs) if (b) (void)hipFree(b);
-}
 
 extern "C" {
 

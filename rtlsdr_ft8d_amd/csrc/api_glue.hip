@@ -4,53 +4,27 @@
 
 #include <string.h>
 
-int grow_buffer(void **buf, size_t *cap, size_t need) {
-    if (need <= *cap) return 0;
-    if (*buf) (void)hipFree(*buf);
-    *buf = nullptr;
-    *cap = 0;
-    HIP_TRY(hipMalloc(buf, need));
-    *cap = need;
-    return 0;
-}
-
-int ensure_rx_scratch(ft8gpu_ctx *c, size_t sums, size_t p2, size_t iq, size_t raw) {
-    if (sums > c->rx_sums_cap || p2 > c->rx_p2_cap || iq > c->rx_iq_cap || raw > c->rx_raw_cap)
-        HIP_TRY(hipStreamSynchronize(c->stream));                   // the old buffers may still be in use
-    if (grow_buffer(&c->d_rx_sums, &c->rx_sums_cap, sums)) return -1;
-    if (grow_buffer(&c->d_rx_p2, &c->rx_p2_cap, p2)) return -1;
-    if (grow_buffer((void **)&c->d_rx_iq, &c->rx_iq_cap, iq)) return -1;
-    if (grow_buffer((void **)&c->d_rx_raw, &c->rx_raw_cap, raw)) return -1;
-    return 0;
-}
-
-int follow_cap(ft8gpu_ctx *c, int *cap, void **a, size_t a_bytes, void **b, size_t b_bytes) {
-    if (*cap >= c->cap_candidates) return 0;
-    HIP_TRY(hipStreamSynchronize(c->stream));                       // the old pair may still be in use
-    if (*a) (void)hipFree(*a);
-    if (*b) (void)hipFree(*b);
-    *a = *b = nullptr;
-    *cap = 0;
-    const size_t records = (size_t)c->max_frames * c->cap_candidates;
-    HIP_TRY(hipMalloc(a, records * a_bytes));
-    HIP_TRY(hipMalloc(b, records * b_bytes));
-    *cap = c->cap_candidates;
+int ensure_scratch(ft8gpu_ctx *c, size_t b0, size_t b1, size_t b2, size_t b3) {
+    const size_t need[4] = { b0, b1, b2, b3 };
+    bool grows = false;
+    for (int i = 0; i < 4; ++i) grows |= need[i] > c->scratch_cap[i];
+    if (grows) HIP_TRY(hipStreamSynchronize(c->stream));
+    for (int i = 0; i < 4; ++i)
+        if (c->mem.grow(&c->d_scratch[i], &c->scratch_cap[i], need[i], "scratch")) return -1;
     return 0;
 }
 
 int ensure_msgs_staging(ft8gpu_ctx *c) {
-    if (!c->d_msgs) HIP_TRY(hipMalloc(&c->d_msgs, (size_t)c->max_frames * kMaxMessages * sizeof(ft8gpu_message)));
-    return 0;
+    return c->mem.once(&c->d_msgs, (size_t)c->max_frames * kMaxMessages * sizeof(ft8gpu_message), "staging of the records");
 }
 
-int ensure_host_staging(ft8gpu_ctx *c) {
-    if (!c->d_iq) HIP_TRY(hipMalloc(&c->d_iq, (size_t)c->max_frames * 2 * kNSamples * sizeof(float)));
-    return ensure_msgs_staging(c);
+int ensure_host_staging(ft8gpu_ctx *c, bool msgs) {
+    if (c->mem.once(&c->d_iq, (size_t)c->max_frames * 2 * kNSamples * sizeof(float), "staging of the frames")) return -1;
+    return msgs ? ensure_msgs_staging(c) : 0;
 }
 
 int ensure_counts_staging(ft8gpu_ctx *c) {
-    if (!c->d_nbs) HIP_TRY(hipMalloc(&c->d_nbs, (size_t)c->max_frames * FT8GPU_MAX_PASSES * 3 * sizeof(int32_t)));
-    return 0;
+    return c->mem.once(&c->d_nbs, (size_t)c->max_frames * FT8GPU_MAX_PASSES * 3 * sizeof(int32_t), "staging of the counts by stage");
 }
 
 extern "C" {
@@ -66,19 +40,16 @@ int ft8gpu_rx_decimate(ft8gpu_ctx *c, const uint8_t *raw, int ncaptures, size_t 
     const size_t sums_bytes = (size_t)ncaptures * (nblocks + 1) * 16;
     const size_t p2_bytes = (size_t)ncaptures * ((nblocks + 15) / 16 + 1) * 32 + (size_t)ncaptures * 376 * 4;   // entry states + group totals + partial peaks
     const bool staged = !(flags & FT8GPU_DEVICE_PTRS);
-    if (sums_bytes > c->rx_sums_cap || p2_bytes > c->rx_p2_cap || (staged && (raw_bytes > c->rx_raw_cap || iq_bytes > c->rx_iq_cap)))
-        HIP_TRY(hipStreamSynchronize(c->stream));          // a buffer is regrown below: earlier launches may still use the old one
-    if (grow_buffer(&c->d_rx_sums, &c->rx_sums_cap, sums_bytes)) return -1;
-    if (grow_buffer(&c->d_rx_p2, &c->rx_p2_cap, p2_bytes)) return -1;
+    // scratch: 0 block sums, 1 entry states, 2 the host form's frames, 3 its raw bytes
+    if (ensure_scratch(c, sums_bytes, p2_bytes, staged ? iq_bytes : 0, staged ? raw_bytes : 0)) return -1;
+    void *const *sc = c->d_scratch;
     if (flags & FT8GPU_DEVICE_PTRS) {
         if (((uintptr_t)raw & 15) != 0) return ft8_fail("raw must be 16-byte aligned");
-        HIP_TRY(launch_rx(raw, ncaptures, npairs, c->d_rx_sums, c->d_rx_p2, iq, normalise, c->stream));
+        HIP_TRY(launch_rx(raw, ncaptures, npairs, sc[0], sc[1], iq, normalise, c->stream));
     } else {
-        if (grow_buffer((void **)&c->d_rx_raw, &c->rx_raw_cap, raw_bytes)) return -1;
-        if (grow_buffer((void **)&c->d_rx_iq, &c->rx_iq_cap, iq_bytes)) return -1;
-        HIP_TRY(hipMemcpyAsync(c->d_rx_raw, raw, raw_bytes, hipMemcpyHostToDevice, c->stream));
-        HIP_TRY(launch_rx(c->d_rx_raw, ncaptures, npairs, c->d_rx_sums, c->d_rx_p2, c->d_rx_iq, normalise, c->stream));
-        HIP_TRY(hipMemcpyAsync(iq, c->d_rx_iq, iq_bytes, hipMemcpyDeviceToHost, c->stream));
+        HIP_TRY(hipMemcpyAsync(sc[3], raw, raw_bytes, hipMemcpyHostToDevice, c->stream));
+        HIP_TRY(launch_rx((const uint8_t *)sc[3], ncaptures, npairs, sc[0], sc[1], (float *)sc[2], normalise, c->stream));
+        HIP_TRY(hipMemcpyAsync(iq, sc[2], iq_bytes, hipMemcpyDeviceToHost, c->stream));
         HIP_TRY(hipStreamSynchronize(c->stream));
     }
     return 0;
@@ -150,9 +121,9 @@ int ft8gpu_pskreporter_datagrams(ft8gpu_ctx *c, const struct decoder_results *de
     }
     const size_t F = (size_t)c->max_frames;
     HIP_TRY(hipStreamSynchronize(c->stream));              // staging may be regrown below
-    if (grow_buffer((void **)&c->d_rep, &c->rep_cap, F * FT8GPU_DATAGRAM_STRIDE)) return -1;
-    if (grow_buffer((void **)&c->d_rep_len, &c->rep_len_cap, F * sizeof(int32_t))) return -1;
-    if (unixtimes && grow_buffer((void **)&c->d_rep_time, &c->rep_time_cap, F * sizeof(uint32_t))) return -1;
+    if (c->mem.grow(&c->d_rep, &c->rep_cap, F * FT8GPU_DATAGRAM_STRIDE, "staging of the datagrams")) return -1;
+    if (c->mem.grow(&c->d_rep_len, &c->rep_len_cap, F * sizeof(int32_t), "staging of the datagram lengths")) return -1;
+    if (unixtimes && c->mem.grow(&c->d_rep_time, &c->rep_time_cap, F * sizeof(uint32_t), "staging of the unixtimes")) return -1;
     const StageArg a[] = { { decodes, c->d_decodes, kMaxMessages * sizeof(struct decoder_results), kIn },
                            { n_results, c->d_nres, sizeof(int32_t), kIn }, { unixtimes, c->d_rep_time, sizeof(uint32_t), kIn },
                            { datagrams, c->d_rep, FT8GPU_DATAGRAM_STRIDE, kOut }, { lengths, c->d_rep_len, sizeof(int32_t), kOut } };
@@ -175,7 +146,7 @@ int ft8gpu_synth_frames_at(ft8gpu_ctx *c, const ft8gpu_synth_signal *signals, in
     if (nsig < 0 || nsig > 64) return ft8_fail("nsig_per_frame %d out of range [0, 64]", nsig);
     if (!iq_dev || (nsig > 0 && !signals)) return ft8_fail("NULL array argument");
     const size_t bytes = (size_t)nframes * (nsig > 0 ? nsig : 1) * sizeof(ft8gpu_synth_signal);
-    if (grow_buffer((void **)&c->d_sigs, &c->sigs_cap, bytes)) return -1;
+    if (c->mem.grow(&c->d_sigs, &c->sigs_cap, bytes, "the synthesiser's signals")) return -1;
     if (nsig > 0) HIP_TRY(hipMemcpyAsync(c->d_sigs, signals, (size_t)nframes * nsig * sizeof(ft8gpu_synth_signal), hipMemcpyHostToDevice, c->stream));
     HIP_TRY(launch_synth(c->d_sigs, nframes, nsig, noise_sigma, seed, first_frame, iq_dev, c->stream));
     HIP_TRY(hipStreamSynchronize(c->stream));

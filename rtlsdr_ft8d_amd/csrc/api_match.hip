@@ -3,7 +3,7 @@
 // helpers of the table are plain C in ft8_pack.c).
 //
 // Buffers.  The codewords of the tables (24 bytes per entry plus the live masks), the info records and the host form's
-// staging of the states and of status_out live in the context's RX buffers (ensure_rx_scratch); they grow on the first call that
+// staging of the states and of status_out live in the context's scratch blocks (ensure_scratch: 0 codewords, 1 states, 2 status_out, 3 info); they grow on the first call that
 // needs them.  Everything else is the staging of the messages path.
 //
 // The slot-major whole path (decode_messages_slot_major; ft8gpu_decode_messages_combined of api_combine.hip runs on it too)
@@ -33,7 +33,7 @@ hipError_t copy_rows(void *dst, size_t dpitch, const void *src, size_t spitch, s
 }  // namespace
 
 // The caller has checked its arguments and sized its scratch for Pieces(nstreams, nslots, max_frames).rg_max receivers; the
-// host form stages the states (state_bytes each) in d_rx_p2.  `slot` issues one slot's launches behind the pipeline; column 0
+// host form stages the states (state_bytes each) in scratch block 1.  `slot` issues one slot's launches behind the pipeline; column 0
 // of n_by_stage is the count in front of them, column 1 the count behind.
 int decode_messages_slot_major(ft8gpu_ctx *c, const float *iq, int nstreams, int nslots, void *state, size_t state_bytes,
                                ft8gpu_message *msgs, int32_t *n_msgs, int32_t *n_by_stage, int flags, const SlotStages &slot) {
@@ -43,7 +43,7 @@ int decode_messages_slot_major(ft8gpu_ctx *c, const float *iq, int nstreams, int
     hipStream_t s = c->stream;
     return Pieces(nstreams, nslots, c->max_frames).each([&](int r0, int rg, int s0, int ns, size_t f0) {
         char *user_st = (char *)state + r0 * state_bytes;
-        void *st = dev ? user_st : c->d_rx_p2;
+        void *st = dev ? user_st : c->d_scratch[1];
         if (!dev && s0 == 0) HIP_TRY(hipMemcpyAsync(st, user_st, rg * state_bytes, hipMemcpyHostToDevice, s));
         const int nfr = rg * ns;                                         // receiver r's slot t is frame f0 + r * nslots + t
         // A piece whose frames are consecutive in the caller's arrays (one receiver, or one slot per receiver) is slot-major
@@ -95,21 +95,21 @@ int ft8gpu_match_candidates(ft8gpu_ctx *c, const uint8_t *mag, const ft8gpu_cand
     if (ensure_messages_buffers(c)) return -1;
     const int mc = c->params.max_candidates;
     const size_t piece = (size_t)(nframes < c->max_frames ? nframes : c->max_frames);
-    if (ensure_rx_scratch(c, piece * kExpectWorkBytes, dev ? 0 : piece * sizeof(ft8gpu_expect_state),
+    if (ensure_scratch(c, piece * kExpectWorkBytes, dev ? 0 : piece * sizeof(ft8gpu_expect_state),
                           dev ? 0 : piece * mc * sizeof(ft8gpu_decode_status), dev ? 0 : piece * mc * sizeof(ft8gpu_match_info)))
         return -1;
     // records at and behind a frame's count keep the caller's bytes (both outputs are uploaded in the host form)
     const StageArg a[] = { { mag, c->d_mag, kMagArray, kIn }, { cands, c->d_cands, mc * sizeof(ft8gpu_candidate), kIn },
                            { counts, c->d_counts, sizeof(int32_t), kIn },
                            { status_in, c->d_status, mc * sizeof(ft8gpu_decode_status), kIn },
-                           { states, c->d_rx_p2, sizeof(ft8gpu_expect_state), kIn },
-                           { status_out, c->d_rx_iq, mc * sizeof(ft8gpu_decode_status), kInOut },
-                           { info, c->d_rx_raw, mc * sizeof(ft8gpu_match_info), kInOut } };
+                           { states, c->d_scratch[1], sizeof(ft8gpu_expect_state), kIn },
+                           { status_out, c->d_scratch[2], mc * sizeof(ft8gpu_decode_status), kInOut },
+                           { info, c->d_scratch[3], mc * sizeof(ft8gpu_match_info), kInOut } };
     return for_each_chunk(c, nframes, flags & FT8GPU_DEVICE_PTRS, a, [&](int n, void *const *p) {
-        HIP_TRY(launch_expect_encode((const ft8gpu_expect_state *)p[4], n, max_age, c->d_msgtab, c->d_rx_sums, c->stream));
+        HIP_TRY(launch_expect_encode((const ft8gpu_expect_state *)p[4], n, max_age, c->d_msgtab, c->d_scratch[0], c->stream));
         HIP_TRY(launch_match((const uint8_t *)p[0], (const ft8gpu_candidate *)p[1], (const int32_t *)p[2],
                              (const ft8gpu_decode_status *)p[3], (ft8gpu_decode_status *)p[5], (ft8gpu_match_info *)p[6], n, mc,
-                             c->d_rx_sums, max_hard_errors, c->stream));
+                             c->d_scratch[0], max_hard_errors, c->stream));
         return 0;
     });
 }
@@ -126,11 +126,11 @@ int ft8gpu_expect_update(ft8gpu_ctx *c, const ft8gpu_message *msgs, const int32_
     if (dev && (((uintptr_t)msgs | (uintptr_t)state) & 15) != 0) return ft8_fail("msgs and state must be 16-byte aligned");
     if (dev && ((uintptr_t)n_msgs & 3) != 0) return ft8_fail("n_msgs must be 4-byte aligned");
     const Pieces cut(nstreams, nslots, dev ? kNoBound : c->max_frames);      // nothing bounds a piece in the device form
-    if (!dev && (ensure_rx_scratch(c, 0, (size_t)cut.rg_max * sizeof(ft8gpu_expect_state), 0, 0) || ensure_msgs_staging(c))) return -1;
+    if (!dev && (ensure_scratch(c, 0, (size_t)cut.rg_max * sizeof(ft8gpu_expect_state), 0, 0) || ensure_msgs_staging(c))) return -1;
     return cut.each([&](int r0, int rg, int, int ns, size_t f0) {
         const StageArg a[] = { { msgs + f0 * kMaxMessages, c->d_msgs, (size_t)ns * kMaxMessages * sizeof(ft8gpu_message), kIn },
                                { n_msgs + f0, c->d_nres, (size_t)ns * sizeof(int32_t), kIn },
-                               { state + r0, c->d_rx_p2, sizeof(ft8gpu_expect_state), kInOut } };
+                               { state + r0, c->d_scratch[1], sizeof(ft8gpu_expect_state), kInOut } };
         return for_each_chunk(c, rg, flags & FT8GPU_DEVICE_PTRS, a, [&](int n, void *const *p) {
             HIP_TRY(launch_expect_update((const ft8gpu_message *)p[0], (const int32_t *)p[1], n, ns, (ft8gpu_expect_state *)p[2],
                                          derive, c->stream));
@@ -155,7 +155,7 @@ int ft8gpu_decode_messages_expected(ft8gpu_ctx *c, const float *iq, int nstreams
     if (dev && (((uintptr_t)msgs | (uintptr_t)state | (uintptr_t)iq) & 15) != 0) return ft8_fail("iq, msgs and state must be 16-byte aligned");
     if (ensure_messages_buffers(c)) return -1;
     const int mc = c->params.max_candidates, rg_max = Pieces(nstreams, nslots, c->max_frames).rg_max;
-    if (ensure_rx_scratch(c, (size_t)rg_max * kExpectWorkBytes, dev ? 0 : (size_t)rg_max * sizeof(ft8gpu_expect_state), 0,
+    if (ensure_scratch(c, (size_t)rg_max * kExpectWorkBytes, dev ? 0 : (size_t)rg_max * sizeof(ft8gpu_expect_state), 0,
                           (size_t)rg_max * mc * sizeof(ft8gpu_match_info)))
         return -1;
     const int gate = params->max_hard_errors, derive = params->derive;
@@ -165,9 +165,9 @@ int ft8gpu_decode_messages_expected(ft8gpu_ctx *c, const float *iq, int nstreams
                                       [=](size_t o, int rg, void *st, ft8gpu_message *dm, int32_t *pn, int32_t *pb) {
         ft8gpu_expect_state *states = (ft8gpu_expect_state *)st;
         ft8gpu_decode_status *status = c->d_status + o * mc;
-        HIP_TRY(launch_expect_encode(states, rg, max_age, c->d_msgtab, c->d_rx_sums, s));
+        HIP_TRY(launch_expect_encode(states, rg, max_age, c->d_msgtab, c->d_scratch[0], s));
         HIP_TRY(launch_match(c->d_mag + o * kMagArray, c->d_cands + o * mc, c->d_counts + o, status, status,
-                             (ft8gpu_match_info *)c->d_rx_raw, rg, mc, c->d_rx_sums, gate, s));
+                             (ft8gpu_match_info *)c->d_scratch[3], rg, mc, c->d_scratch[0], gate, s));
         HIP_TRY(launch_append(c->d_mag + o * kMagArray, c->d_base + o * 2 * kNumBin, c->d_cands + o * mc, c->d_counts + o, status,
                               c->d_msgtab, nullptr, rg, mc, c->params.min_score, dm, pn, s));
         HIP_TRY(launch_match_tag(pb, 2, pn, rg, dm, s));

@@ -15,7 +15,7 @@ constexpr double kSnrCalibrationK = 25.16;
 // P[v] = 10^((v - 240) / 20): byte v = 2 dB + 240 back to power; T[d] = (1 + 10^((d - 0.5 + K) / 10)) / q with
 // q = -ln(0.75), the 25th percentile of exponential noise power in units of its mean.  libm's pow / log, as the numpy
 // restatement (tests/ft8_spec_messages.py, math.pow / math.log) evaluates them.
-void build_msg_tables(MsgTables *t) {
+int build_msg_tables(MsgTables *t) {
     for (int v = 0; v < 256; ++v) t->power[v] = pow(10.0, (double)(v - 240) / 20.0);
     const double q = -log(0.75);
     for (int d = kSnrMin; d <= kSnrMax; ++d) t->thr[d - kSnrMin] = (1.0 + pow(10.0, ((double)d - 0.5 + kSnrCalibrationK) / 10.0)) / q;
@@ -23,25 +23,15 @@ void build_msg_tables(MsgTables *t) {
         for (int w = 0; w < 3; ++w)
             t->gen[m][w] = (uint32_t)kFT8_generator[m][4 * w] << 24 | (uint32_t)kFT8_generator[m][4 * w + 1] << 16 |
                            (uint32_t)kFT8_generator[m][4 * w + 2] << 8 | (uint32_t)kFT8_generator[m][4 * w + 3];
+    return 0;
 }
 
 }  // namespace
 
 // the noise baseline buffer and the tables, on the first messages call (ft8gpu_create's footprint is unchanged)
 int ensure_messages_buffers(ft8gpu_ctx *c) {
-    if (!c->d_base) HIP_TRY(hipMalloc(&c->d_base, (size_t)c->max_frames * 2 * kNumBin));
-    if (!c->d_msgtab) {
-        MsgTables t;
-        build_msg_tables(&t);
-        MsgTables *d = nullptr;
-        HIP_TRY(hipMalloc(&d, sizeof t));
-        if (hipMemcpy(d, &t, sizeof t, hipMemcpyHostToDevice) != hipSuccess) {
-            (void)hipFree(d);
-            return ft8_fail("uploading the SNR tables failed");
-        }
-        c->d_msgtab = d;
-    }
-    return 0;
+    if (c->mem.once(&c->d_base, (size_t)c->max_frames * 2 * kNumBin, "the noise baseline")) return -1;
+    return c->mem.table(&c->d_msgtab, "the SNR tables", build_msg_tables);
 }
 
 extern "C" {
@@ -65,7 +55,7 @@ int ft8gpu_collect_messages(ft8gpu_ctx *c, const uint8_t *mag, const ft8gpu_cand
     if (!mag || !cands || !counts || !status || !msgs || !n_msgs) return ft8_fail("NULL array argument");
     if (ensure_messages_buffers(c)) return -1;
     const int mc = c->params.max_candidates;
-    if (!(flags & FT8GPU_DEVICE_PTRS) && !c->d_msgs) HIP_TRY(hipMalloc(&c->d_msgs, (size_t)c->max_frames * kMaxMessages * sizeof(ft8gpu_message)));
+    if (!(flags & FT8GPU_DEVICE_PTRS) && ensure_msgs_staging(c)) return -1;
     // slots past a frame's count keep the caller's bytes; c->d_base is scratch in both forms
     const StageArg a[] = { { mag, c->d_mag, kMagArray, kIn }, { cands, c->d_cands, mc * sizeof(ft8gpu_candidate), kIn },
                            { counts, c->d_counts, sizeof(int32_t), kIn }, { status, c->d_status, mc * sizeof(ft8gpu_decode_status), kIn },

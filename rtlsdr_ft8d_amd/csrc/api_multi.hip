@@ -170,7 +170,8 @@ extern "C" int ft8gpu_gather_spots(ft8gpu_ctx *const *ctxs, int ndev, const stru
     const size_t cnt_bytes = (size_t)frames_per_dev * sizeof(int32_t);
     // RCCL enqueues the grouped collectives on the contexts' streams at ncclGroupEnd(), not at the ncclAllGather calls: every
     // context stays locked from GroupStart to GroupEnd (in address order -- the one lock order any multi-context entry may use),
-    // so that a concurrent ft8gpu_set_stream / ft8gpu_destroy cannot replace or destroy a stream RCCL is launching on.
+    // so that a concurrent ft8gpu_set_stream cannot replace a stream RCCL is launching on.  (ft8gpu_destroy takes no lock:
+    // destroying a context while an entry runs on it is the caller's error, include/ft8gpu.h.)
     std::vector<ft8gpu_ctx *> order(ctxs, ctxs + ndev);
     std::sort(order.begin(), order.end(), std::less<ft8gpu_ctx *>());
     std::vector<std::unique_lock<std::mutex>> held;

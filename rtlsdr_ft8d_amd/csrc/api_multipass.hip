@@ -8,13 +8,12 @@
 int ensure_multipass_buffers(ft8gpu_ctx *c) {
     if (ensure_messages_buffers(c)) return -1;
     const size_t mf = (size_t)c->max_frames;
-    if (!c->d_mag2) HIP_TRY(hipMalloc(&c->d_mag2, mf * kMagArray));
-    if (!c->d_map) HIP_TRY(hipMalloc(&c->d_map, mf * sizeof(int32_t)));
-    if (!c->d_nprev) HIP_TRY(hipMalloc(&c->d_nprev, mf * sizeof(int32_t)));
-    if (!c->d_nactive) HIP_TRY(hipMalloc(&c->d_nactive, sizeof(int32_t)));
-    if (!c->h_nactive) HIP_TRY(hipHostMalloc(&c->h_nactive, sizeof(int32_t)));
-    if (!c->d_counts2) HIP_TRY(hipMalloc(&c->d_counts2, mf * sizeof(int32_t)));
-    return follow_cap(c, &c->cap2, (void **)&c->d_cands2, sizeof(ft8gpu_candidate), (void **)&c->d_status2, sizeof(ft8gpu_decode_status));
+    CtxMem &m = c->mem;
+    if (m.once(&c->d_mag2, mf * kMagArray, "a later pass's waterfall") || m.once(&c->d_map, mf * sizeof(int32_t), "the slot map") ||
+        m.once(&c->d_nprev, mf * sizeof(int32_t), "the counts before a pass") || m.once(&c->d_nactive, sizeof(int32_t), "the active count") ||
+        m.once_pinned(&c->h_nactive, sizeof(int32_t), "the active count") || m.once(&c->d_counts2, mf * sizeof(int32_t), "a later pass's counts"))
+        return -1;
+    return follow_cap(c, &c->d_cands2, &c->d_status2, &c->cap2, "a later pass's candidates");
 }
 
 namespace {
@@ -64,12 +63,6 @@ int decode_messages_masked(ft8gpu_ctx *c, const float *iq, int nframes, int pass
         if (run_pipeline_messages(c, (const float *)p[0], n, (ft8gpu_message *)p[1], (int32_t *)p[2])) return -1;
         return run_masking_passes(Chunk{ c, n, passes, cols, (ft8gpu_message *)p[1], (int32_t *)p[2], (int32_t *)p[3] }, rescue);
     });
-}
-
-void free_multipass_buffers(ft8gpu_ctx *c) {
-    void *bufs[] = { c->d_mag2, c->d_map, c->d_nprev, c->d_nactive, c->d_cands2, c->d_counts2, c->d_status2, c->d_nbs };
-    for (void *b : bufs) if (b) (void)hipFree(b);
-    if (c->h_nactive) (void)hipHostFree(c->h_nactive);
 }
 
 extern "C" {

@@ -12,13 +12,9 @@ constexpr int kOsdMaxOrder = 2, kOsdMaxHard = kLdpcM;
 // the constant tables, the info records and the host form's staging of status_out, on the first OSD call
 // (ft8gpu_create's footprint is unchanged)
 int ensure_osd_buffers(ft8gpu_ctx *c) {
-    if (!c->osd_tables) {
-        HIP_TRY(osd_tables_init(c->stream));
-        HIP_TRY(hipStreamSynchronize(c->stream));
-        c->osd_tables = true;
-    }
-    if (!c->d_nosd) HIP_TRY(hipMalloc(&c->d_nosd, (size_t)c->max_frames * sizeof(int32_t)));
-    return follow_cap(c, &c->osd_cap, (void **)&c->d_osd_info, sizeof(ft8gpu_osd_info), (void **)&c->d_osd_out, sizeof(ft8gpu_decode_status));
+    if (tables_once(c, &c->osd_tables, osd_tables_init)) return -1;
+    if (c->mem.once(&c->d_nosd, (size_t)c->max_frames * sizeof(int32_t), "the counts before OSD")) return -1;
+    return follow_cap(c, &c->d_osd_info, &c->d_osd_out, &c->osd_cap, "the OSD records");
 }
 
 int check_osd_args(int order, int max_hard_errors) {
@@ -38,11 +34,6 @@ int osd_step(const Chunk &k, const PassSet &f, int col, int order, int max_hard_
                           k.n_msgs, c->stream));
     HIP_TRY(launch_osd_tag(c->d_osd_info, f.map, c->d_nosd, k.n_msgs, f.nslots, mc, k.msgs, c->stream));
     return k.counts_to(col);
-}
-
-void free_osd_buffers(ft8gpu_ctx *c) {
-    void *bufs[] = { c->d_osd_info, c->d_osd_out, c->d_nosd };
-    for (void *b : bufs) if (b) (void)hipFree(b);
 }
 
 extern "C" {

@@ -176,7 +176,7 @@ int decode_frames(ft8gpu_ctx *c, const float *iq, int nframes, Rec *recs, int32_
             if (run(c, iq + f0 * frame_floats, n, recs + (size_t)f0 * kMaxMessages, counts + f0)) return -1;
         } else {
             const bool iq_dev = flags & kIqOnDevice;
-            if (!iq_dev && !c->d_iq) HIP_TRY(hipMalloc(&c->d_iq, (size_t)c->max_frames * frame_floats * sizeof(float)));
+            if (!iq_dev && ensure_host_staging(c, false)) return -1;
             // slots the path does not write must keep the caller's bytes (rtlsdr_ft8d.c:1509-1520)
             HIP_TRY(hipMemcpyAsync(d_stage, recs + (size_t)f0 * kMaxMessages,
                                    (size_t)n * kMaxMessages * sizeof(Rec), hipMemcpyHostToDevice, c->stream));
@@ -229,7 +229,6 @@ extern "C" int ft8gpu_decode_messages(ft8gpu_ctx *c, const float *iq, int nframe
     if (nframes == 0) return 0;
     if (!iq || !msgs || !n_msgs) return ft8_fail("NULL array argument");
     if (ensure_messages_buffers(c)) return -1;
-    if (!(flags & FT8GPU_DEVICE_PTRS) && !c->d_msgs)
-        HIP_TRY(hipMalloc(&c->d_msgs, (size_t)c->max_frames * kMaxMessages * sizeof(ft8gpu_message)));
+    if (!(flags & FT8GPU_DEVICE_PTRS) && ensure_msgs_staging(c)) return -1;
     return decode_frames(c, iq, nframes, msgs, n_msgs, flags & FT8GPU_DEVICE_PTRS, c->d_msgs, c->d_nres, run_pipeline_messages);
 }

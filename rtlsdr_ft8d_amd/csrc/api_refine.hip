@@ -3,8 +3,8 @@
 // are plain C in ft8_refine.c).
 //
 // Both entries cut the frames with for_each_chunk.  The host form stages the frames in the context's d_iq, the records in d_msgs,
-// the counts in d_nres and the refined records in the growable RX buffer d_rx_raw, which no other entry uses while this one holds
-// the context's mutex.  Records at and behind a frame's count keep the caller's bytes, so msgs and refined travel both ways.
+// the counts in d_nres and the refined records in the context's scratch block 3 (ensure_scratch), which no other entry uses while
+// this one holds the context's mutex.  Records at and behind a frame's count keep the caller's bytes, so msgs and refined travel both ways.
 #include "refine.h"
 #include "ft8gpu_ctx.h"
 
@@ -19,10 +19,7 @@ int ensure_refine_buffers(ft8gpu_ctx *c, int nframes, bool dev) {
     if (ensure_messages_buffers(c)) return -1;
     if (dev) return 0;
     const size_t piece = (size_t)(nframes < c->max_frames ? nframes : c->max_frames);
-    if (!c->d_iq) HIP_TRY(hipMalloc(&c->d_iq, (size_t)c->max_frames * kFrameBytes));
-    if (!c->d_msgs) HIP_TRY(hipMalloc(&c->d_msgs, (size_t)c->max_frames * kMsgBytes));
-    if (piece * kRefBytes > c->rx_raw_cap) HIP_TRY(hipStreamSynchronize(c->stream));   // the old buffer may still be in use
-    return grow_buffer((void **)&c->d_rx_raw, &c->rx_raw_cap, piece * kRefBytes);
+    return ensure_host_staging(c) || ensure_scratch(c, 0, 0, 0, piece * kRefBytes) ? -1 : 0;
 }
 
 }  // namespace
@@ -38,7 +35,7 @@ int ft8gpu_refine_messages(ft8gpu_ctx *c, const float *iq, const ft8gpu_message 
     if (dev && ((uintptr_t)iq & 15) != 0) return ft8_fail("iq must be 16-byte aligned");
     if (ensure_refine_buffers(c, nframes, dev)) return -1;
     const StageArg a[] = { { iq, c->d_iq, kFrameBytes, kIn }, { msgs, c->d_msgs, kMsgBytes, kIn },
-                           { n_msgs, c->d_nres, sizeof(int32_t), kIn }, { refined, c->d_rx_raw, kRefBytes, kInOut } };
+                           { n_msgs, c->d_nres, sizeof(int32_t), kIn }, { refined, c->d_scratch[3], kRefBytes, kInOut } };
     return for_each_chunk(c, nframes, flags & FT8GPU_DEVICE_PTRS, a, [&](int n, void *const *p) {
         HIP_TRY(launch_refine((const float *)p[0], (const ft8gpu_message *)p[1], (const int32_t *)p[2], n, c->d_tab, c->d_msgtab,
                               (ft8gpu_refined *)p[3], c->stream));
@@ -55,7 +52,7 @@ int ft8gpu_decode_messages_refined(ft8gpu_ctx *c, const float *iq, int nframes, 
     if (dev && ((uintptr_t)iq & 15) != 0) return ft8_fail("iq must be 16-byte aligned");
     if (ensure_refine_buffers(c, nframes, dev)) return -1;
     const StageArg a[] = { { iq, c->d_iq, kFrameBytes, kIn }, { msgs, c->d_msgs, kMsgBytes, kInOut },
-                           { n_msgs, c->d_nres, sizeof(int32_t), kOut }, { refined, c->d_rx_raw, kRefBytes, kInOut } };
+                           { n_msgs, c->d_nres, sizeof(int32_t), kOut }, { refined, c->d_scratch[3], kRefBytes, kInOut } };
     return for_each_chunk(c, nframes, flags & FT8GPU_DEVICE_PTRS, a, [&](int n, void *const *p) {
         if (run_pipeline_messages(c, (const float *)p[0], n, (ft8gpu_message *)p[1], (int32_t *)p[2])) return -1;
         HIP_TRY(launch_refine((const float *)p[0], (const ft8gpu_message *)p[1], (const int32_t *)p[2], n, c->d_tab, c->d_msgtab,

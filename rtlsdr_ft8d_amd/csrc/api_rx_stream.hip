@@ -1,6 +1,6 @@
 // api_rx_stream.hip -- host glue of ft8gpu_rx_stream: the RX front end with the filter state carried from one buffer
 // into the next (rx_stream.hip).  The host form stages the whole call at once: raw bytes, states, frames and counts go
-// through the context's RX buffers, so the result does not depend on how a caller cuts a stream into calls.
+// through the context's scratch blocks, so the result does not depend on how a caller cuts a stream into calls.
 #include "ft8gpu_ctx.h"
 
 #include <string.h>
@@ -45,22 +45,19 @@ int ft8gpu_rx_stream(ft8gpu_ctx *c, const uint8_t *raw, int nstreams, int nslots
     rx_stream_scratch(nstreams, nslots, npairs, &sums_bytes, &p2_bytes);
     const size_t stage_at = (p2_bytes + 15) & ~(size_t)15;   // host form: states and counts are staged behind the scratch
     if (!dev) p2_bytes = stage_at + ((state_bytes + 15) & ~(size_t)15) + nout_bytes;
-    if (sums_bytes > c->rx_sums_cap || p2_bytes > c->rx_p2_cap || (!dev && (raw_bytes > c->rx_raw_cap || iq_bytes > c->rx_iq_cap)))
-        HIP_TRY(hipStreamSynchronize(c->stream));          // a buffer is regrown below: earlier launches may still use the old one
-    if (grow_buffer(&c->d_rx_sums, &c->rx_sums_cap, sums_bytes)) return -1;
-    if (grow_buffer(&c->d_rx_p2, &c->rx_p2_cap, p2_bytes)) return -1;
+    // scratch: 0 block sums, 1 entry states (and the staging behind them), 2 the host form's frames, 3 its raw bytes
+    if (ensure_scratch(c, sums_bytes, p2_bytes, dev ? 0 : iq_bytes, dev ? 0 : raw_bytes)) return -1;
+    void *const *sc = c->d_scratch;
     if (dev) {
-        HIP_TRY(launch_rx_stream(raw, nstreams, nslots, npairs, state, c->d_rx_sums, c->d_rx_p2, iq, n_out, normalise, c->stream));
+        HIP_TRY(launch_rx_stream(raw, nstreams, nslots, npairs, state, sc[0], sc[1], iq, n_out, normalise, c->stream));
         return 0;
     }
-    if (grow_buffer((void **)&c->d_rx_raw, &c->rx_raw_cap, raw_bytes)) return -1;
-    if (grow_buffer((void **)&c->d_rx_iq, &c->rx_iq_cap, iq_bytes)) return -1;
-    ft8gpu_rx_state *d_state = (ft8gpu_rx_state *)((char *)c->d_rx_p2 + stage_at);
+    ft8gpu_rx_state *d_state = (ft8gpu_rx_state *)((char *)sc[1] + stage_at);
     uint32_t *d_nout = (uint32_t *)((char *)d_state + ((state_bytes + 15) & ~(size_t)15));
-    HIP_TRY(hipMemcpyAsync(c->d_rx_raw, raw, raw_bytes, hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(hipMemcpyAsync(sc[3], raw, raw_bytes, hipMemcpyHostToDevice, c->stream));
     HIP_TRY(hipMemcpyAsync(d_state, state, state_bytes, hipMemcpyHostToDevice, c->stream));
-    HIP_TRY(launch_rx_stream(c->d_rx_raw, nstreams, nslots, npairs, d_state, c->d_rx_sums, c->d_rx_p2, c->d_rx_iq, d_nout, normalise, c->stream));
-    HIP_TRY(hipMemcpyAsync(iq, c->d_rx_iq, iq_bytes, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(launch_rx_stream((const uint8_t *)sc[3], nstreams, nslots, npairs, d_state, sc[0], sc[1], (float *)sc[2], d_nout, normalise, c->stream));
+    HIP_TRY(hipMemcpyAsync(iq, sc[2], iq_bytes, hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(hipMemcpyAsync(state, d_state, state_bytes, hipMemcpyDeviceToHost, c->stream));
     if (n_out) HIP_TRY(hipMemcpyAsync(n_out, d_nout, nout_bytes, hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(hipStreamSynchronize(c->stream));

@@ -9,7 +9,7 @@ int ft8gpu_waterfall(ft8gpu_ctx *c, const float *iq, int nframes, uint8_t *mag, 
     if (nframes == 0) return 0;
     if (!iq || !mag) return ft8_fail("NULL array argument");
     const size_t frame_floats = 2 * (size_t)kNSamples;
-    if (!(flags & FT8GPU_DEVICE_PTRS) && !c->d_iq) HIP_TRY(hipMalloc(&c->d_iq, (size_t)c->max_frames * frame_floats * sizeof(float)));
+    if (!(flags & FT8GPU_DEVICE_PTRS) && ensure_host_staging(c, false)) return -1;
     const StageArg a[] = { { iq, c->d_iq, frame_floats * sizeof(float), kIn }, { mag, c->d_mag, kMagArray, kOut } };
     return for_each_chunk(c, nframes, flags, a, [&](int n, void *const *p) {
         HIP_TRY(launch_waterfall((const float *)p[0], (uint8_t *)p[1], c->d_tab, n, c->num_cus, c->debug_flags, c->stream));
@@ -35,7 +35,8 @@ int ft8gpu_score_map(ft8gpu_ctx *c, const uint8_t *mag, int nframes, int16_t *sc
     CHECK_COMMON(c, nframes);
     if (nframes == 0) return 0;
     if (!mag || !scores) return ft8_fail("NULL array argument");
-    if (!(flags & FT8GPU_DEVICE_PTRS) && !c->d_scores) HIP_TRY(hipMalloc(&c->d_scores, (size_t)c->max_frames * kScoresPerFrame * sizeof(int16_t)));
+    if (!(flags & FT8GPU_DEVICE_PTRS) &&
+        c->mem.once(&c->d_scores, (size_t)c->max_frames * kScoresPerFrame * sizeof(int16_t), "staging of the score map")) return -1;
     const StageArg a[] = { { mag, c->d_mag, kMagArray, kIn }, { scores, c->d_scores, kScoresPerFrame * sizeof(int16_t), kOut } };
     return for_each_chunk(c, nframes, flags, a, [&](int n, void *const *p) {
         HIP_TRY(launch_sync((const uint8_t *)p[0], c->d_lists, c->d_list_counts, (int16_t *)p[1], n, c->params.min_score, c->stream));

@@ -9,8 +9,6 @@
 #include "refine.h"
 #include "ft8gpu_ctx.h"
 
-#include <stdlib.h>
-
 extern "C" void ft8_subtract_inv_table(float *inv);
 
 namespace {
@@ -28,16 +26,15 @@ int ensure_subtract_buffers(ft8gpu_ctx *c, bool host, bool work, bool info) {
     if (ensure_messages_buffers(c)) return -1;
     const size_t mf = (size_t)c->max_frames;
     if (ensure_subtract_tables(c)) return -1;
-    if (!c->d_sub_scratch) {
-        const int sf = c->max_frames < kSubFrames ? c->max_frames : kSubFrames;
-        HIP_TRY(hipMalloc(&c->d_sub_scratch, (size_t)sf * kMaxMessages * kSubStride * sizeof(uint32_t)));
-        c->sub_frames = sf;
-    }
-    if ((host || work) && !c->d_sub_x) HIP_TRY(hipMalloc(&c->d_sub_x, mf * kFrameBytes));
-    if ((host || work) && !c->d_sub_ref) HIP_TRY(hipMalloc(&c->d_sub_ref, mf * kRefBytes));
-    if (work && !c->d_sub_nref) HIP_TRY(hipMalloc(&c->d_sub_nref, mf * sizeof(int32_t)));
+    CtxMem &m = c->mem;
+    c->sub_frames = c->max_frames < kSubFrames ? c->max_frames : kSubFrames;
+    if (m.once(&c->d_sub_scratch, (size_t)c->sub_frames * kMaxMessages * kSubStride * sizeof(uint32_t), "the subtraction's scratch")) return -1;
+    if ((host || work) && (m.once(&c->d_sub_x, mf * kFrameBytes, "the frames being subtracted from") ||
+                           m.once(&c->d_sub_ref, mf * kRefBytes, "the refined records")))
+        return -1;
+    if (work && m.once(&c->d_sub_nref, mf * sizeof(int32_t), "the counts a pass subtracts")) return -1;
     if (host && ensure_host_staging(c)) return -1;
-    if (host && info && !c->d_sub_info) HIP_TRY(hipMalloc(&c->d_sub_info, mf * kInfoBytes));
+    if (host && info && m.once(&c->d_sub_info, mf * kInfoBytes, "staging of the subtraction's info records")) return -1;
     return 0;
 }
 
@@ -95,26 +92,11 @@ int run_subtracted_passes(ft8gpu_ctx *c, const float *iq, int n, int passes, ft8
 
 // the constant tables (w4, inv), on the first call that needs them; api_demod.hip reads w4 too
 int ensure_subtract_tables(ft8gpu_ctx *c) {
-    if (c->d_subtab) return 0;
-    SubTables *h = (SubTables *)calloc(1, sizeof(SubTables));
-    if (!h) return ft8_fail("out of memory");
-    ft8gpu_subtract_twiddles(&h->w4[0].x);
-    ft8_subtract_inv_table(h->inv);
-    SubTables *d = nullptr;
-    hipError_t e = hipMalloc(&d, sizeof(SubTables));
-    if (e == hipSuccess) e = hipMemcpy(d, h, sizeof(SubTables), hipMemcpyHostToDevice);
-    free(h);
-    if (e != hipSuccess) {
-        if (d) (void)hipFree(d);
-        return ft8_fail("subtraction tables: %s", hipGetErrorString(e));
-    }
-    c->d_subtab = d;
-    return 0;
-}
-
-void free_subtract_buffers(ft8gpu_ctx *c) {
-    void *bufs[] = { c->d_subtab, c->d_sub_scratch, c->d_sub_x, c->d_sub_ref, c->d_sub_info, c->d_sub_nref };
-    for (void *b : bufs) if (b) (void)hipFree(b);
+    return c->mem.table(&c->d_subtab, "the subtraction tables", [](SubTables *h) {
+        ft8gpu_subtract_twiddles(&h->w4[0].x);
+        ft8_subtract_inv_table(h->inv);
+        return 0;
+    });
 }
 
 extern "C" {

@@ -1,7 +1,9 @@
 // ft8gpu_ctx.h -- the context object and the helpers every host-side translation unit of the C ABI shares: api_context.hip,
-// api_pipeline.hip, api_multi.hip, api_stages.hip, api_messages.hip, api_multipass.hip, api_osd.hip, api_ap.hip, api_glue.hip,
-// api_rx_stream.hip, api_callhash.hip, api_match.hip, api_combine.hip, api_refine.hip, api_subtract.hip, api_demod.hip, api_audio.hip, api_gfsk.hip.  Not installed.
+// api_mem.hip, api_pipeline.hip, api_multi.hip, api_stages.hip, api_messages.hip, api_multipass.hip, api_osd.hip, api_ap.hip,
+// api_glue.hip, api_rx_stream.hip, api_callhash.hip, api_match.hip, api_combine.hip, api_refine.hip, api_subtract.hip,
+// api_demod.hip, api_audio.hip, api_gfsk.hip.  Not installed.
 #pragma once
+#include "ctx_mem.h"
 #include "ft8gpu_internal.h"
 
 #include <functional>
@@ -9,8 +11,7 @@
 #include <mutex>
 #include <stddef.h>
 
-// ft8gpu_last_error(): thread-local text, written by ft8_fail() only (api_context.hip)
-int ft8_fail(const char *fmt, ...) __attribute__((format(printf, 1, 2)));
+// ft8gpu_last_error(): thread-local text, written by ft8_fail() only (api_context.hip; declared in ctx_mem.h)
 char *ft8_err_buffer();                       // the calling thread's buffer (kErrBytes), for hand-overs between threads
 constexpr size_t kErrBytes = 512;
 
@@ -20,7 +21,10 @@ constexpr size_t kErrBytes = 512;
         if (e_ != hipSuccess) return ft8_fail("%s failed: %s (%s:%d)", #expr, hipGetErrorString(e_), __FILE__, __LINE__); \
     } while (0)
 
+const MemBackend *hip_mem();                  // api_mem.hip
+
 struct ft8gpu_ctx {
+    CtxMem mem{ hip_mem() };                 // owns every d_* / h_* buffer below: allocated through it, freed by its release_all()
     int device = 0;
     int num_cus = 256;
     int max_frames = 0;
@@ -104,10 +108,8 @@ struct ft8gpu_ctx {
     float *d_gfsk_max = nullptr;           //   and the tiles' maxima [max_frames][22]
     ft8gpu_synth_signal *d_sigs = nullptr;
     size_t sigs_cap = 0;
-    void *d_rx_sums = nullptr, *d_rx_p2 = nullptr;     // RX front end scratch
-    uint8_t *d_rx_raw = nullptr;
-    float *d_rx_iq = nullptr;
-    size_t rx_sums_cap = 0, rx_p2_cap = 0, rx_raw_cap = 0, rx_iq_cap = 0;
+    void *d_scratch[4]{};                  // four growable scratch blocks (ensure_scratch) for whichever entry holds the mutex:
+    size_t scratch_cap[4]{};               //   the RX front end, call hash, match, combine, demod and refine say in place what they keep where
     uint8_t *d_rep = nullptr;              // host-pointer staging of the report stage
     int32_t *d_rep_len = nullptr;
     uint32_t *d_rep_time = nullptr;
@@ -235,44 +237,45 @@ int run_pipeline(ft8gpu_ctx *c, const float *d_iq, int n, struct decoder_results
 int run_pipeline_messages(ft8gpu_ctx *c, const float *d_iq, int n, ft8gpu_message *d_msgs, int32_t *d_nmsgs);
 // api_messages.hip: allocates d_base / d_msgtab on the first messages call
 int ensure_messages_buffers(ft8gpu_ctx *c);
-// api_multipass.hip: frees the multi-pass buffers and the n_by_stage staging (ft8gpu_destroy); allocates them on the first
-// multi-pass call; the masking whole path behind ft8gpu_decode_messages_passes / _deep / _ap (checked arguments, buffers of
-// the rescue stages in place): pass 1, then masking passes up to `passes`, `rescue` (may be empty) on every pass's failures
-void free_multipass_buffers(ft8gpu_ctx *c);
+// api_multipass.hip: allocates the multi-pass buffers on the first multi-pass call; the masking whole path behind
+// ft8gpu_decode_messages_passes / _deep / _ap (checked arguments, buffers of the rescue stages in place): pass 1, then masking
+// passes up to `passes`, `rescue` (may be empty) on every pass's failures
 int ensure_multipass_buffers(ft8gpu_ctx *c);
 int decode_messages_masked(ft8gpu_ctx *c, const float *iq, int nframes, int passes, int cols, ft8gpu_message *msgs, int32_t *n_msgs,
                            int32_t *n_by_stage, int flags, const Rescue &rescue);
-// api_osd.hip: frees the OSD buffers (ft8gpu_destroy); allocates them on the first OSD call; refuses arguments out of range;
-// the OSD rescue step, whose count goes to column col
-void free_osd_buffers(ft8gpu_ctx *c);
+// api_osd.hip: allocates the OSD buffers on the first OSD call; refuses arguments out of range; the OSD rescue step, whose
+// count goes to column col
 int ensure_osd_buffers(ft8gpu_ctx *c);
 int check_osd_args(int order, int max_hard_errors);
 int osd_step(const Chunk &k, const PassSet &f, int col, int order, int max_hard_errors);
 // api_match.hip: the slot-major whole path behind ft8gpu_decode_messages_expected / _combined
 int decode_messages_slot_major(ft8gpu_ctx *c, const float *iq, int nstreams, int nslots, void *state, size_t state_bytes,
                                ft8gpu_message *msgs, int32_t *n_msgs, int32_t *n_by_stage, int flags, const SlotStages &slot);
-// api_ap.hip: frees the AP buffers (ft8gpu_destroy)
-void free_ap_buffers(ft8gpu_ctx *c);
-// api_subtract.hip: frees the subtraction buffers (ft8gpu_destroy); uploads the subtraction's constant tables (d_subtab) on the
-// first call that needs them
-void free_subtract_buffers(ft8gpu_ctx *c);
+// api_subtract.hip: uploads the subtraction's constant tables (d_subtab) on the first call that needs them
 int ensure_subtract_tables(ft8gpu_ctx *c);
-// api_audio.hip: frees the audio front end's buffers (ft8gpu_destroy)
-void free_audio_buffers(ft8gpu_ctx *c);
-// api_gfsk.hip: frees the GFSK synthesiser's buffers (ft8gpu_destroy)
-void free_gfsk_buffers(ft8gpu_ctx *c);
 // ft8gpu_decode_batch with one more form: kIqOnDevice, frames resident on the context's GPU and records to host arrays
 // (used by the multi-GPU entries; not part of the ABI, whose entry passes on FT8GPU_DEVICE_PTRS only)
 constexpr int kIqOnDevice = 2;
 int decode_batch(ft8gpu_ctx *c, const float *iq, int nframes, struct decoder_results *decodes, int32_t *n_results, int flags);
-// api_glue.hip: (re)allocates *buf when `need` exceeds *cap (the caller has synchronised the stream)
-int grow_buffer(void **buf, size_t *cap, size_t need);
-// the context's RX buffers as scratch of at least these sizes (0: not needed); no other entry uses them while this one holds
-// the context's mutex
-int ensure_rx_scratch(ft8gpu_ctx *c, size_t sums, size_t p2, size_t iq, size_t raw);
-// a lazily allocated pair of [max_frames][*cap] records of a_bytes / b_bytes follows cap_candidates when ft8gpu_set_params grows it
-int follow_cap(ft8gpu_ctx *c, int *cap, void **a, size_t a_bytes, void **b, size_t b_bytes);
-// the host form's staging, on the first call that needs it: the records; the frames and the records; the n_by_stage rows
+// api_glue.hip: the context's scratch blocks at these sizes or more (0: not needed).  The stream is synchronised only if one of
+// them has to grow, since earlier launches may still use the old block.
+int ensure_scratch(ft8gpu_ctx *c, size_t b0, size_t b1, size_t b2, size_t b3);
+// the host form's staging, on the first call that needs it: the records; the frames and (msgs) the records; the n_by_stage rows
 int ensure_msgs_staging(ft8gpu_ctx *c);
-int ensure_host_staging(ft8gpu_ctx *c);
+int ensure_host_staging(ft8gpu_ctx *c, bool msgs = true);
 int ensure_counts_staging(ft8gpu_ctx *c);
+
+// a lazily allocated pair of [max_frames][*cap] records follows cap_candidates when ft8gpu_set_params grows it
+template <class A, class B>
+int follow_cap(ft8gpu_ctx *c, A **a, B **b, int *cap, const char *what) {
+    if (*cap >= c->cap_candidates) return 0;
+    HIP_TRY(hipStreamSynchronize(c->stream));                       // the old pair may still be in use
+    return c->mem.pair(a, b, cap, c->cap_candidates, (size_t)c->max_frames, what);
+}
+
+// a kernel file's constant tables, uploaded on the context's first call that needs them (the upload reads a static host object)
+inline int tables_once(ft8gpu_ctx *c, bool *done, hipError_t (*init)(hipStream_t)) {
+    if (!*done) { HIP_TRY(init(c->stream)); HIP_TRY(hipStreamSynchronize(c->stream)); }
+    *done = true;
+    return 0;
+}

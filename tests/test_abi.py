@@ -175,6 +175,32 @@ def test_product_never_touches_the_oracle():
     assert "ft8o_" not in sym
 
 
+def test_context_memory_is_allocated_and_freed_in_one_place():
+    """The host side allocates and frees device and pinned memory in two places only: the HIP binding of the context's memory
+    owner (csrc/api_mem.hip, behind csrc/ctx_mem.h) and the four helpers for the CALLER's memory, ft8gpu_dev_alloc / _dev_free /
+    _host_alloc / _host_free.  Any other hipMalloc / hipHostMalloc / hipFree / hipHostFree in csrc/api_*.hip or csrc/*.h is a
+    buffer the owner does not know: a leak at ft8gpu_destroy, and a failure path that leaves the runtime's error set."""
+    import glob
+    csrc = os.path.join(ROOT, "rtlsdr_ft8d_amd", "csrc")
+    helpers = {"ft8gpu_dev_alloc", "ft8gpu_dev_free", "ft8gpu_host_alloc", "ft8gpu_host_free"}
+    call = re.compile(r"\b(hipMalloc|hipHostMalloc|hipFree|hipHostFree)\s*\(")
+    head = re.compile(r"^[A-Za-z_][\w \*&:<>]*?\b(\w+)\s*\(")           # a function's head starts in column 0
+    files = sorted(glob.glob(os.path.join(csrc, "api_*.hip")) + glob.glob(os.path.join(csrc, "*.h")))
+    assert len(files) > 30 and os.path.join(csrc, "api_mem.hip") in files
+    seen = set()
+    for path in files:
+        fn, inside = os.path.basename(path), None
+        for ln, line in enumerate(open(path), 1):
+            m = head.match(line)
+            if m:
+                inside = m.group(1)
+            code = line.split("//")[0]
+            for m in call.finditer(code):
+                seen.add((fn, inside))
+                assert fn == "api_mem.hip" or inside in helpers, f"{fn}:{ln}: {m.group(1)} outside the owner's binding: {line.strip()}"
+    assert {("api_context.hip", h) for h in helpers} <= seen and any(f == "api_mem.hip" for f, _ in seen), seen
+
+
 def test_gather_entry_argument_errors_and_no_rccl_link_dependency(ft8):
     """ft8gpu_gather_spots checks its arguments before touching a GPU or RCCL, and libft8gpu.so itself must not
     depend on librccl (it is bound with dlopen at the first gather, so a plain C caller links without it)"""

@@ -589,6 +589,134 @@ def test_failed_buffer_growth_leaves_the_context_as_it_was():
         assert int(nres.sum().item()) > 8 * n
 
 
+def _call_every_lazy_entry(ft8, workload, dec, host, sig, raw):
+    """one call, host-pointer form, of every entry that allocates context memory on its first use; host: 4 frames
+    [4][2][48000], sig: their signal records [4][nsig], raw: 4 short captures [4][2 * npairs]"""
+    import torch
+    n = host.shape[0]
+    grid = host.reshape(2, 2, 2, ft8.NSAMPLES)                   # two receivers, two slots
+    dec.decode_messages(host)
+    dec.decode_messages_passes(host, passes=2)
+    dec.decode_messages_deep(host, passes=2, osd_order=1)
+    dec.decode_messages_ap(host, passes=2, osd_order=1)
+    dec.decode_messages_resolved(grid)
+    dec.decode_messages_expected(grid)
+    dec.decode_messages_combined(grid)
+    dec.decode_messages_demod(host)
+    msgs, cnt, refined = dec.decode_messages_refined(host)
+    dec.decode_messages_subtracted(host, passes=2, want_residual=True)
+    dec.subtract_messages(host, msgs, refined, np.zeros(n, np.int32), cnt, want_info=True)
+    pcm = dec.synth_gfsk_audio(sig, n, sig.shape[1], noise_sigma=0.01, seed=1, peak=0.5, fmt=ft8.AUDIO_S16)
+    dec.synth_gfsk_frames(sig, n, sig.shape[1], noise_sigma=0.01, seed=1, peak=0.5)
+    dec.audio_frames(pcm)
+    dec.decode_audio(pcm)
+    dec.score_map(dec.waterfall(host))
+    dec.rx_decimate(raw)
+    dec.rx_stream(raw.reshape(2, 2, -1))
+    d, k = dec.decode_batch(host)
+    dec.pskreporter_datagrams(d, k, ft8.ReportInfo(rcall=b"K1ABC", rloc=b"FN42", app_version=b"lifecycle", dial_freq=14074000, unixtime=1700000000,
+                                                   sequence=1, random_id=7), unixtimes=np.full(n, 1700000000, np.uint32))
+    iq = torch.empty((n, 2, ft8.NSAMPLES), dtype=torch.float32, device="cuda")
+    dec.synth_frames(sig, n, sig.shape[1], 1.0, workload.SEED_BASE, iq)
+    dec.synchronize()
+    return cnt
+
+
+def test_context_lifecycle_with_every_lazy_buffer_does_not_leak():
+    """ft8gpu_create / ft8gpu_destroy twenty times at max_frames = 256, each context calling once, in the host-pointer form on 4
+    frames or clips, every entry that allocates lazily: the whole paths (messages, passes, deep, ap, resolved, expected,
+    combined, demod, refined, subtracted with residual), the subtraction stage with info, both audio entries, both GFSK
+    entries (int16 audio with peak > 0), score map, both RX entries, the datagrams and the synthesiser.  The context's memory
+    has one owner (csrc/ctx_mem.h) and ft8gpu_destroy frees what that owner recorded, so the device's free memory returns to
+    where it was, within the 64 MB the older lifecycle test allows torch's allocator (taken here as 64 * 10^6 bytes, a little
+    under that test's 64 MiB).  The smallest of the large lazy buffers is 3.28 MB at this size (the bands' records, the merged
+    records' staging), so twenty cycles put a leak of any of them, 65.5 MB, above the allowance; the small ones (the records'
+    staging of 0.8 MB, per-frame counters, constant tables) stay below it, and the stand-alone program of
+    tests/test_sanitizers.py::test_ctx_mem_owner_under_asan_ubsan covers them exactly."""
+    import torch
+    import rtlsdr_ft8d_amd as ft8
+    from rtlsdr_ft8d_amd import workload
+    F, n, cycles, allowance = 256, 4, 20, 64 * 10**6
+    _, tones = workload.message_pool(traffic="cq")
+    sig, _ = workload.frame_signals(123000, n, 6, tones, snr_range=(-12.0, 0.0))
+    raw = np.random.default_rng(5).integers(0, 256, (n, 2 * 751 * 64), dtype=np.uint8)
+    with ft8.Decoder(device=0, max_frames=F) as dec:
+        iq = torch.empty((n, 2, ft8.NSAMPLES), dtype=torch.float32, device="cuda")
+        dec.synth_frames(sig, n, 6, 1.0, workload.SEED_BASE, iq, first_frame=123000)
+        dec.synchronize()
+        host = iq.cpu().numpy()
+        del iq
+        first = _call_every_lazy_entry(ft8, workload, dec, host, sig, raw)      # (every kernel's code is loaded before the measurement)
+    assert int(first.sum()) >= n                                  # the frames carry messages: the later passes have work
+    assert cycles * (F * 4 * 50 * 64) > allowance                 # cycles x smallest large buffer against the allowance
+    torch.cuda.synchronize()
+    torch.cuda.empty_cache()
+    free0, _ = torch.cuda.mem_get_info()
+    for _ in range(cycles):
+        with ft8.Decoder(device=0, max_frames=F) as dec:
+            cnt = _call_every_lazy_entry(ft8, workload, dec, host, sig, raw)
+            assert np.array_equal(cnt, first)
+    torch.cuda.synchronize()
+    torch.cuda.empty_cache()
+    free1, _ = torch.cuda.mem_get_info()
+    print(f"lifecycle with every lazy buffer: free memory {free0} -> {free1} over {cycles} cycles")
+    assert free0 - free1 < allowance, (free0, free1)
+
+
+def test_failed_lazy_allocation_does_not_poison_the_context():
+    """A lazily allocated buffer that cannot be had: with the GPU's memory filled until less than one frame buffer (max_frames x
+    384 000 bytes, 3.1 GB at max_frames 8192) is left, ft8gpu_decode_messages_subtracted in the host form raises.  The owner of
+    the context's memory clears the runtime's error with the refusal, so once the filler is gone the same call on the same
+    context succeeds -- before, the first launch of that call reported the stale out-of-memory error -- and gives, byte for byte,
+    the records of a fresh context, as does a plain ft8gpu_decode_batch on device pointers.  (An allocation refusal, never a
+    kernel fault: nothing is launched on a buffer that was not allocated.)"""
+    import torch
+    import rtlsdr_ft8d_amd as ft8
+    from rtlsdr_ft8d_amd import workload
+    F, n = 8192, 8
+    frame_buffer = F * 2 * ft8.NSAMPLES * 4
+
+    def spots_of(dec, iq):
+        spots = torch.zeros((n, 1400), dtype=torch.uint8, device="cuda")
+        nres = torch.zeros((n,), dtype=torch.int32, device="cuda")
+        torch.cuda.synchronize()
+        dec.decode_batch_dev(iq, n, spots, nres)
+        dec.synchronize()
+        return spots.cpu().numpy().tobytes(), nres.cpu().numpy().tobytes()
+
+    def records_of(dec, host):
+        return tuple(a.tobytes() for a in dec.decode_messages_subtracted(host, passes=2, want_residual=True))
+
+    with ft8.Decoder(device=0, max_frames=F) as fresh:
+        iq = _job(ft8, workload, fresh, 920000, n)
+        host = iq.cpu().numpy()
+        want, want_spots = records_of(fresh, host), spots_of(fresh, iq)
+    assert int(np.frombuffer(want[1], np.int32).sum()) > 8 * n
+    with ft8.Decoder(device=0, max_frames=F) as dec:
+        torch.cuda.empty_cache()
+        # as in test_failed_buffer_growth_leaves_the_context_as_it_was: fill in pieces, halving the piece whenever one is refused
+        filler, piece, target = [], 8 << 30, frame_buffer - (256 << 20)
+        while piece >= (32 << 20):
+            free_now, _ = torch.cuda.mem_get_info()
+            if free_now <= target:
+                break
+            sz = min(piece, free_now - target)
+            if sz < (32 << 20):
+                break
+            try:
+                filler.append(torch.empty(sz, dtype=torch.uint8, device="cuda"))
+            except torch.OutOfMemoryError:
+                piece //= 2
+        free_now, _ = torch.cuda.mem_get_info()
+        assert free_now < frame_buffer, (free_now, frame_buffer)
+        with pytest.raises(ft8.Ft8GpuError, match="out of device memory"):
+            dec.decode_messages_subtracted(host, passes=2, want_residual=True)
+        del filler
+        torch.cuda.empty_cache()
+        assert records_of(dec, host) == want
+        assert spots_of(dec, iq) == want_spots
+
+
 def test_device_outputs_stay_inside_their_buffers():
     """Every device-pointer entry writes into caller-owned HBM.  A write one element past a buffer would corrupt whatever the
     caller keeps next to it and no parity test would notice: here every output buffer is a slice of ONE allocation with 4 KB of

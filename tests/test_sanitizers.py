@@ -3,6 +3,7 @@ not available on the GPU pool), and ThreadSanitizer runs of its host concurrency
 only hints at ASan (Makefile:7).
   * the oracle (oracle/ft8_oracle.c, `make -C oracle asan`) under its own CPU test file;
   * csrc/ft8_compat.c + csrc/ft8_pack.c (pack77 / encode / file readers / formatter / drop-in shim) under tests/host_asan;
+  * csrc/ctx_mem.h (the owner of a context's device memory) on a counting fake backend under tests/host_asan;
   * csrc/shard_pool.h and the global-context / candidate-cache logic of csrc/ft8_compat.c under tests/host_tsan."""
 import os
 import subprocess
@@ -45,6 +46,21 @@ def test_compat_host_code_under_asan_ubsan(tmp_path):
                            "-lpthread", "-lm", "-o", exe])
     out = subprocess.run([exe, str(tmp_path)], env=dict(os.environ, **SAN_ENV), capture_output=True, text=True, timeout=300)
     assert out.returncode == 0 and "compat_asan ok" in out.stdout, (out.stdout + out.stderr)[-3000:]
+
+
+def test_ctx_mem_owner_under_asan_ubsan(tmp_path):
+    """csrc/ctx_mem.h, the one owner of a context's device and pinned memory, as a stand-alone program on a counting fake
+    backend: every allocation of a scripted context life (once, table, grow, the cap-following pairs, a pinned block) refused
+    in turn -- the failed step leaves null fields, cap 0, a cleared runtime error and nothing recorded, the same call then
+    succeeds, table() gives its device block back when the upload or the fill fails, and release_all() frees every live
+    block exactly once.  This is the exact leak and double-free check of the small buffers (counters, tables) that the GPU
+    lifecycle test of tests/test_gpu_multi.py cannot see."""
+    exe = str(tmp_path / "ctx_mem_asan")
+    subprocess.check_call(["g++", "-std=c++17", "-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=all",
+                           "-fno-omit-frame-pointer", "-Wall", "-Wextra", "-I" + os.path.join(ROOT, "rtlsdr_ft8d_amd", "csrc"),
+                           os.path.join(ROOT, "tests", "host_asan", "ctx_mem_asan_main.cpp"), "-o", exe])
+    out = subprocess.run([exe], env=dict(os.environ, **SAN_ENV), capture_output=True, text=True, timeout=300)
+    assert out.returncode == 0 and "ctx_mem_asan ok" in out.stdout, (out.stdout + out.stderr)[-3000:]
 
 
 # ---- ThreadSanitizer: the host concurrency of the library (CPU only) -----------------------------------------------------
