@@ -1036,6 +1036,35 @@ int ft8gpu_subtract_messages(ft8gpu_ctx *ctx, const float *iq, const ft8gpu_mess
 int ft8gpu_decode_messages_subtracted(ft8gpu_ctx *ctx, const float *iq, int nframes, int passes, ft8gpu_message *msgs,
                                       int32_t *n_msgs, int32_t *n_by_pass, float *residual, int flags);
 
+/* ---- GFSK reference: the subtraction rule with the waveform a station sends -------------------------------------------------------
+ * (DESIGN.md "Subtraction in the I/Q samples", "GFSK reference".)  The rule above rebuilds a record as CPFSK, tone steps
+ * abrupt.  A `shape` selects the reference: FT8GPU_SUBTRACT_CPFSK is the rule above, unchanged.  FT8GPU_SUBTRACT_GFSK is the same
+ * rule but for (b') and (e'); tests/ft8_spec_subtract_gfsk.py restates it and the device output equals that byte for byte.
+ * (b') Reference phase of a start sample S and a base index k4.  Q = Q_512[0 .. 1536], the pulse table of ft8gpu_gfsk_pulse(512, .)
+ *     (the device uses its host's table, as the synthesiser does);  e[0] = tone[0], e[j] = tone[j - 1] for j = 1 .. 79,
+ *     e[80] = tone[78].  For the local sample n' = j - S in [0, 40448), m = n' div 512, k = n' mod 512, in wrapping uint32:
+ *       phi = (k4 << 20) * n' + e[m] * Q[k + 1024] + e[m + 1] * Q[k + 512] + e[m + 2] * Q[k]
+ *       theta(j) = ((phi + 2^19) >> 20) & 4095
+ *     -- the synthesiser's phase ("GFSK synthesis") at step = k4 * 2^20, rounded to the w4 table.  z, seg and P, both fine
+ *     searches with their first-strict-maximum rule, G, A and inv, and the NaN clauses are those of (b), (c) and (d) with this
+ *     theta.
+ * (e') Subtraction.  r = the ramp of ft8gpu_gfsk_ramp(512, .), 64 entries.  env(n') = r[n'] for n' < 64, r[40447 - n'] for
+ *     n' >= 40384, 1 otherwise.  Where env(n') != 1 the amplitude in (e) is (Ar * env, Ai * env), two float32 products formed
+ *     before the products with w; elsewhere A is used as it is (no multiplication by 1.0f is part of the rule).  The ramp is
+ *     NOT applied in the estimate: A stays the plain mean of (d).
+ * r[0] = 0, so a record's first sample keeps its value -- unless A(0) is infinite there: inf * 0 is a NaN by IEEE, and so is
+ * the sample. */
+#define FT8GPU_SUBTRACT_CPFSK   0       /* shape: abrupt tone steps, the rule of "subtraction in the I/Q samples" */
+#define FT8GPU_SUBTRACT_GFSK    1       /* shape: (b') and (e') */
+/* ft8gpu_subtract_messages and ft8gpu_decode_messages_subtracted with the shape in front of the flags.  shape 0 gives the bytes
+ * of those entries; a shape outside {0, 1} fails before anything is enqueued.  The GFSK tables are uploaded on the first call
+ * with shape 1 and freed at ft8gpu_destroy.  The refine stage of the pass loop is the same for both shapes. */
+int ft8gpu_subtract_messages_shaped(ft8gpu_ctx *ctx, const float *iq, const ft8gpu_message *msgs, const ft8gpu_refined *refined,
+                                    const int32_t *first, const int32_t *n_msgs, int nframes, float *iq_out,
+                                    ft8gpu_subtract_info *info, int shape, int flags);
+int ft8gpu_decode_messages_subtracted_shaped(ft8gpu_ctx *ctx, const float *iq, int nframes, int passes, ft8gpu_message *msgs,
+                                             int32_t *n_msgs, int32_t *n_by_pass, float *residual, int shape, int flags);
+
 /* ---- demodulation from the I/Q samples: undecoded candidates demodulated again from the frame itself ----------------------------
  * (DESIGN.md "Demodulation from the I/Q samples"; not in the reference.)  OSD, AP, matching and combining all start from the
  * soft bits of ft8_extract_likelihood: one byte per waterfall cell in half-decibel steps, a 1024-sample Hann window over

@@ -81,6 +81,7 @@ assert REFINED_DTYPE.itemsize == 48
 SUBTRACT_INFO_DTYPE = np.dtype([("k4", "<i4"), ("s_best", "<i4"), ("d_best", "i1"), ("t_best", "i1"), ("valid", "u1"), ("pad0", "u1"),
                                 ("pf", "<f4", (5,)), ("pt", "<f4", (5,)), ("pad", "u1", (12,))])
 SUBTRACT_TABLE = 4096            # FT8GPU_SUBTRACT_TABLE
+SUBTRACT_CPFSK, SUBTRACT_GFSK = 0, 1   # FT8GPU_SUBTRACT_CPFSK / _GFSK: the shape of the reference a record is subtracted with
 assert SUBTRACT_INFO_DTYPE.itemsize == 64
 assert SOFTMEM_ENTRY_DTYPE.itemsize == 720 and SOFTMEM_STATE_DTYPE.itemsize == 92176 and COMBINE_INFO_DTYPE.itemsize == 8
 # demodulation from the I/Q samples (ft8gpu_demod_candidates): what the second demodulation found for a candidate
@@ -185,6 +186,7 @@ ABI_SYMBOLS = [
     "ft8gpu_combine_candidates", "ft8gpu_softmem_update", "ft8gpu_decode_messages_combined", "ft8gpu_softmem_reset",
     "ft8gpu_refine_messages", "ft8gpu_decode_messages_refined", "ft8gpu_refined_estimate", "ft8gpu_format_messages_refined",
     "ft8gpu_subtract_messages", "ft8gpu_decode_messages_subtracted", "ft8gpu_subtract_twiddles",
+    "ft8gpu_subtract_messages_shaped", "ft8gpu_decode_messages_subtracted_shaped",
     "ft8gpu_demod_candidates", "ft8gpu_decode_messages_demod",
     "ft8gpu_audio_taps", "ft8gpu_audio_mixer", "ft8gpu_audio_frames", "ft8gpu_decode_audio", "ft8gpu_read_wav",
     "ft8gpu_gfsk_pulse", "ft8gpu_gfsk_ramp", "ft8gpu_gfsk_twiddles", "ft8gpu_synth_gfsk_frames", "ft8gpu_synth_gfsk_audio",
@@ -363,6 +365,9 @@ def _declare(L):
         L.ft8gpu_decode_messages_subtracted.argtypes = [vp, vp, C.c_int, C.c_int, vp, vp, vp, vp, C.c_int]
         L.ft8gpu_subtract_twiddles.argtypes = [vp]
         L.ft8gpu_subtract_twiddles.restype = None
+    if hasattr(L, "ft8gpu_subtract_messages_shaped"):     # absent from older builds loaded by load_library_at
+        L.ft8gpu_subtract_messages_shaped.argtypes = [vp, vp, vp, vp, vp, vp, C.c_int, vp, vp, C.c_int, C.c_int]
+        L.ft8gpu_decode_messages_subtracted_shaped.argtypes = [vp, vp, C.c_int, C.c_int, vp, vp, vp, vp, C.c_int, C.c_int]
     if hasattr(L, "ft8gpu_audio_frames"):                 # absent from older builds loaded by load_library_at
         L.ft8gpu_audio_taps.argtypes = [vp]
         L.ft8gpu_audio_taps.restype = None
@@ -1181,10 +1186,16 @@ class Decoder:
         self._ck(self.lib.ft8gpu_decode_messages_refined(self.h, _ptr(iq_dev), int(nframes), _ptr(msgs_dev), _ptr(n_msgs_dev),
                                                        _ptr(refined_dev), DEVICE_PTRS))
 
-    def subtract_messages(self, iq, msgs, refined, first, n_msgs, info=None, want_info=True):
+    def _subtract_entry(self, name, shape):
+        """(the entry `name` or its shaped form, the arguments that go in front of the flags): shape None is the older entry,
+        SUBTRACT_CPFSK / SUBTRACT_GFSK the shaped one (ft8gpu_subtract_messages_shaped, ft8gpu_decode_messages_subtracted_shaped)"""
+        return (getattr(self.lib, name), ()) if shape is None else (getattr(self.lib, name + "_shaped"), (int(shape),))
+
+    def subtract_messages(self, iq, msgs, refined, first, n_msgs, info=None, want_info=True, shape=None):
         """the subtraction stage (ft8gpu_subtract_messages) -> (iq_out [B][2][48000], info [B][50] SUBTRACT_INFO_DTYPE): the frames
         with the records [first[f], n_msgs[f]) subtracted; info records outside that range keep what `info` held (zeros when None).
-        want_info = False passes NULL and returns (iq_out, None)."""
+        want_info = False passes NULL and returns (iq_out, None).  shape: None for that entry, or the reference's shape through
+        ft8gpu_subtract_messages_shaped: SUBTRACT_CPFSK (the same bytes) or SUBTRACT_GFSK, the waveform a station sends."""
         iq = np.ascontiguousarray(iq, np.float32)
         msgs = np.ascontiguousarray(msgs)
         refined = np.ascontiguousarray(refined)
@@ -1199,21 +1210,23 @@ class Decoder:
             info = np.zeros((B, MAX_MESSAGES), SUBTRACT_INFO_DTYPE)
         assert info is None or (info.dtype == SUBTRACT_INFO_DTYPE and info.shape == (B, MAX_MESSAGES) and info.flags["C_CONTIGUOUS"])
         out = np.zeros((B, 2, NSAMPLES), np.float32)
-        self._ck(self.lib.ft8gpu_subtract_messages(self.h, iq.ctypes.data, msgs.ctypes.data, refined.ctypes.data, first.ctypes.data,
-                                                 n_msgs.ctypes.data, B, out.ctypes.data, None if info is None else info.ctypes.data,
-                                                 HOST_PTRS))
+        entry, shaped = self._subtract_entry("ft8gpu_subtract_messages", shape)
+        self._ck(entry(self.h, iq.ctypes.data, msgs.ctypes.data, refined.ctypes.data, first.ctypes.data, n_msgs.ctypes.data, B,
+                       out.ctypes.data, None if info is None else info.ctypes.data, *shaped, HOST_PTRS))
         return out, info
 
-    def subtract_messages_dev(self, iq_dev, msgs_dev, refined_dev, first_dev, n_msgs_dev, nframes, iq_out_dev, info_dev=None):
+    def subtract_messages_dev(self, iq_dev, msgs_dev, refined_dev, first_dev, n_msgs_dev, nframes, iq_out_dev, info_dev=None, shape=None):
         """every array in HBM (iq_dev and iq_out_dev 16-byte aligned; iq_out_dev may be iq_dev); info_dev: [nframes][50] 64-byte
-        records or None"""
-        self._ck(self.lib.ft8gpu_subtract_messages(self.h, _ptr(iq_dev), _ptr(msgs_dev), _ptr(refined_dev), _ptr(first_dev),
-                                                 _ptr(n_msgs_dev), int(nframes), _ptr(iq_out_dev),
-                                                 None if info_dev is None else _ptr(info_dev), DEVICE_PTRS))
+        records or None; shape as in subtract_messages"""
+        entry, shaped = self._subtract_entry("ft8gpu_subtract_messages", shape)
+        self._ck(entry(self.h, _ptr(iq_dev), _ptr(msgs_dev), _ptr(refined_dev), _ptr(first_dev), _ptr(n_msgs_dev), int(nframes),
+                       _ptr(iq_out_dev), None if info_dev is None else _ptr(info_dev), *shaped, DEVICE_PTRS))
 
-    def decode_messages_subtracted(self, iq, passes=2, msgs=None, want_residual=True):
+    def decode_messages_subtracted(self, iq, passes=2, msgs=None, want_residual=True, shape=None):
         """multi-pass decoding with subtraction in the I/Q samples (ft8gpu_decode_messages_subtracted) -> (msgs [B][50], n_msgs [B],
-        n_by_pass [B][passes], residual [B][2][48000] or None): every frame's last x_p"""
+        n_by_pass [B][passes], residual [B][2][48000] or None): every frame's last x_p.  shape: None for that entry, or the
+        reference's shape through ft8gpu_decode_messages_subtracted_shaped: SUBTRACT_CPFSK (the same bytes) or SUBTRACT_GFSK, which
+        cancels signals from the air deeper (profiles/subtract_gfsk_accuracy.json)."""
         iq = np.ascontiguousarray(iq, np.float32)
         B = iq.shape[0]
         assert iq.shape[1:] == (2, NSAMPLES)
@@ -1223,15 +1236,19 @@ class Decoder:
         n = np.zeros(B, np.int32)
         nbp = np.zeros((B, max(int(passes), 1)), np.int32)
         res = np.zeros((B, 2, NSAMPLES), np.float32) if want_residual else None
-        self._ck(self.lib.ft8gpu_decode_messages_subtracted(self.h, iq.ctypes.data, B, int(passes), msgs.ctypes.data, n.ctypes.data,
-                                                          nbp.ctypes.data, None if res is None else res.ctypes.data, HOST_PTRS))
+        entry, shaped = self._subtract_entry("ft8gpu_decode_messages_subtracted", shape)
+        self._ck(entry(self.h, iq.ctypes.data, B, int(passes), msgs.ctypes.data, n.ctypes.data, nbp.ctypes.data,
+                       None if res is None else res.ctypes.data, *shaped, HOST_PTRS))
         return msgs, n, nbp, res
 
-    def decode_messages_subtracted_dev(self, iq_dev, nframes, passes, msgs_dev, n_msgs_dev, n_by_pass_dev=None, residual_dev=None):
-        """n_by_pass_dev: [nframes][passes] int32 or None; residual_dev: [nframes][2][48000] float32 (16-byte aligned) or None"""
-        self._ck(self.lib.ft8gpu_decode_messages_subtracted(self.h, _ptr(iq_dev), int(nframes), int(passes), _ptr(msgs_dev),
-                                                          _ptr(n_msgs_dev), None if n_by_pass_dev is None else _ptr(n_by_pass_dev),
-                                                          None if residual_dev is None else _ptr(residual_dev), DEVICE_PTRS))
+    def decode_messages_subtracted_dev(self, iq_dev, nframes, passes, msgs_dev, n_msgs_dev, n_by_pass_dev=None, residual_dev=None,
+                                       shape=None):
+        """n_by_pass_dev: [nframes][passes] int32 or None; residual_dev: [nframes][2][48000] float32 (16-byte aligned) or None;
+        shape as in decode_messages_subtracted"""
+        entry, shaped = self._subtract_entry("ft8gpu_decode_messages_subtracted", shape)
+        self._ck(entry(self.h, _ptr(iq_dev), int(nframes), int(passes), _ptr(msgs_dev), _ptr(n_msgs_dev),
+                       None if n_by_pass_dev is None else _ptr(n_by_pass_dev), None if residual_dev is None else _ptr(residual_dev),
+                       *shaped, DEVICE_PTRS))
 
     @staticmethod
     def _audio_clips(pcm):

@@ -94,6 +94,7 @@ struct ft8gpu_ctx {
     ft8gpu_refined *d_sub_ref = nullptr;   //   the refined records [max_frames][50], the info records of the host form,
     ft8gpu_subtract_info *d_sub_info = nullptr;
     int32_t *d_sub_nref = nullptr;         //   and the counts a pass refines and subtracts [max_frames]
+    struct SubGfskTables *d_subgfsktab = nullptr;  // the GFSK reference's pulse table and ramp, on the first call with that shape
     struct AudioTables *d_audiotab = nullptr;  // audio front end, lazily on its first call: the constant tables,
     void *d_audio_pcm = nullptr;           //   host-pointer staging of the clips [max_frames][180000] floats,
     float *d_audio_iq = nullptr;           //   the frame buffer of the whole path and of the host form [max_frames][2][48000],

@@ -22,6 +22,16 @@
 // o + (o >> 5)), the ring, 160 segment sums and the 80 tones.  No scratch memory.
 // Phases: Theta_m = (512 m k4) mod 4096 (the tones' share of the recurrence is whole turns) and every product is formed in
 // uint32, which is exact modulo 4096.
+//
+// Shapes (include/ft8gpu.h "GFSK reference").  Both kernels exist twice, the bodies templated on the shape; the CPFSK kernels
+// keep their names, arithmetic and geometry.  ft8_subtract_estimate_gfsk_kernel and ft8_subtract_apply_gfsk_kernel look every
+// sample's phase up: phi = (k4 << 20) n' + e[m] Q[k + 1024] + e[m + 1] Q[k + 512] + e[m + 2] Q[k] in wrapping uint32, rounded to
+// the w4 table.  Nothing assumes Q linear inside a symbol.  The estimate kernel holds Q in LDS at k + (k >> 5) (1585 dwords,
+// 78 788 bytes per workgroup with the rest, still two workgroups per CU): a lane's 32 samples are Q[32 seg + i] and its two
+// neighbours 512 apart, so the 16 segments of a dechirp step fall on 16 different banks and lanes of different hypotheses
+// read the same entry.  The apply kernel holds Q in table order and reads a thread's four samples as one 16-byte word per
+// pulse term (S* is a multiple of 8 and j of 4), and the 64-entry ramp beside it; only the first and last 64 samples of a
+// record take the ramp's two extra products.
 #include "subtract.h"
 #include "tone_dev.h"
 #include <stddef.h>
@@ -42,6 +52,12 @@ constexpr int kBlocksPerFrame = (kMaxMessages + kWaves - 1) / kWaves;
 constexpr int kSpan = FT8GPU_NN * 512;                         // samples of a record
 constexpr int kParts = 6;                                      // apply: workgroups per frame
 constexpr int kPartSamples = kNSamples / kParts;               // 8000
+constexpr int kPulse = 3 * FT8GPU_GFSK_SPS_IQ + 1;                // 1537 entries of Q
+constexpr int kPulseSlots = kPulse - 1 + ((kPulse - 1) >> 5) + 1;  // 1585: entry k at k + (k >> 5)
+constexpr int kRamp = FT8GPU_GFSK_SPS_IQ / 8;                      // 64 samples of ramp at either end of a record
+constexpr uint32_t kHalfStep = 1u << 19;                           // rounds a 2^-32 turn phase to the 4096 steps of w4
+static_assert(kPulse <= (int)(sizeof(SubGfskTables::q) / sizeof(uint32_t)) && kRamp == (int)(sizeof(SubGfskTables::ramp) / sizeof(float)), "GFSK tables");
+static_assert(kSpan % 4 == 0 && kRamp % 4 == 0, "a thread's four samples share a side of the ramp's ends");
 static_assert(kHyp == 5 && kSmooth == 8 && FT8GPU_SUBTRACT_TSTEP == 8 && kTab == 4096, "lane assignment");
 static_assert(kPartSamples * kParts == kNSamples && kPartSamples % 4 == 0, "apply parts");
 static_assert(sizeof(ft8gpu_message) == 64 && sizeof(ft8gpu_refined) == 48 && sizeof(ft8gpu_subtract_info) == 64, "record sizes");
@@ -95,6 +111,42 @@ __device__ __forceinline__ void seg_sum(const float *s_i, const float *s_q, cons
     im = ai;
 }
 
+// the GFSK phases: the tones around symbol m as e[m], e[m + 1], e[m + 2] (the first and the last tone once more at the ends)
+struct Pulse3 {
+    uint32_t e0, e1, e2;
+};
+
+__device__ __forceinline__ Pulse3 pulse_tones(const int *tone, int m) {
+    Pulse3 e;
+    e.e0 = (uint32_t)tone[m > 0 ? m - 1 : 0];
+    e.e1 = (uint32_t)tone[m];
+    e.e2 = (uint32_t)tone[m < FT8GPU_NN - 1 ? m + 1 : FT8GPU_NN - 1];
+    return e;
+}
+
+// seg_sum with the GFSK phase: the 32 samples are the local samples 512 m + 32 seg + i of a record, phi_lin = step * (512 m +
+// 32 seg) and s_pulse holds Q[k] at k + (k >> 5), so Q[32 seg + i] sits at 33 seg + i.  Every sample is looked up.
+__device__ __forceinline__ void seg_sum_gfsk(const float *s_i, const float *s_q, const float *s_wr, const float *s_wi,
+                                             const uint32_t *s_pulse, int o0, uint32_t phi_lin, uint32_t step, Pulse3 e, int seg,
+                                             float &re, float &im) {
+    const uint32_t *qc = s_pulse + 33 * seg, *qb = qc + 512 + 16, *qa = qc + 1024 + 32;
+    float ar = 0.0f, ai = 0.0f;
+#pragma unroll 8
+    for (int i = 0; i < kSeg; ++i) {
+        const int o = o0 + i;
+        const int a = o + (o >> 5);
+        const float xr = s_i[a], xi = s_q[a];
+        const uint32_t phi = phi_lin + e.e0 * qa[i] + e.e1 * qb[i] + e.e2 * qc[i];
+        const int p = tab_slot((phi + kHalfStep) >> 20);
+        const float wr = s_wr[p], wi = s_wi[p];
+        ar = ar + (xr * wr - xi * wi);
+        ai = ai + (xr * wi + xi * wr);
+        phi_lin += step;
+    }
+    re = ar;
+    im = ai;
+}
+
 struct WaveLds {
     float plane[2][kPlane];
     float ring[2][kRing];
@@ -106,13 +158,13 @@ struct WaveLds {
 // of a first round and h = 4 on the lanes 0 .. 15 of a second one.  Time: start S_0 + 8 (h - 2) for h = 0, 1, 3, 4 in one round
 // (h = 2 is the frequency search's best, the same sums over the same samples, and is not formed again).
 // lane h < 5 returns P of hypothesis h (+0 for h = 2 of the time search).
-template <bool kTime>
+template <bool kTime, int kShape>
 __device__ __forceinline__ float search(const float *__restrict__ pi, const float *__restrict__ pq, WaveLds &L, const float *s_wr,
-                                        const float *s_wi, int S0, int k4_base, int lane) {
+                                        const float *s_wi, const uint32_t *s_pulse, int S0, int k4_base, int lane) {
     const int grp = lane >> 4, seg = lane & 15;
     float P = 0.0f;
     for (int m = 0; m < FT8GPU_NN; ++m) {
-        const uint32_t tone8 = 8u * (uint32_t)L.tone[m];
+        [[maybe_unused]] const uint32_t tone8 = 8u * (uint32_t)L.tone[m];
         if (kTime) stage_span<24>(pi, pq, S0 - kSeg + 512 * m, L.plane[0], L.plane[1], lane);
         else stage_span<16>(pi, pq, S0 + 512 * m, L.plane[0], L.plane[1], lane);
         wave_lds_sync();
@@ -122,9 +174,15 @@ __device__ __forceinline__ float search(const float *__restrict__ pi, const floa
             if (round == 0 || lane < kSymSegs) {
                 const uint32_t k4 = (uint32_t)(kTime ? k4_base : k4_base + h - FT8GPU_SUBTRACT_RANGE);
                 const int o0 = kTime ? kSeg + FT8GPU_SUBTRACT_TSTEP * (h - FT8GPU_SUBTRACT_RANGE) + kSeg * seg : kSeg * seg;
-                const uint32_t K = k4 + tone8;
                 float re, im;
-                seg_sum(L.plane[0], L.plane[1], s_wr, s_wi, o0, 512u * (uint32_t)m * k4 + K * (uint32_t)(kSeg * seg), K, re, im);
+                if constexpr (kShape == FT8GPU_SUBTRACT_GFSK) {
+                    const uint32_t step = k4 << 20;
+                    seg_sum_gfsk(L.plane[0], L.plane[1], s_wr, s_wi, s_pulse, o0, step * (uint32_t)(512 * m + kSeg * seg), step,
+                                 pulse_tones(L.tone, m), seg, re, im);
+                } else {
+                    const uint32_t K = k4 + tone8;
+                    seg_sum(L.plane[0], L.plane[1], s_wr, s_wi, o0, 512u * (uint32_t)m * k4 + K * (uint32_t)(kSeg * seg), K, re, im);
+                }
                 L.sum[0][kSymSegs * h + seg] = re;
                 L.sum[1][kSymSegs * h + seg] = im;
             }
@@ -162,12 +220,16 @@ __device__ __forceinline__ int first_max(WaveLds &L, float P, int lane, float &b
     return __builtin_amdgcn_readfirstlane(at);
 }
 
-__global__ __launch_bounds__(256)
-void ft8_subtract_estimate_kernel(const float *__restrict__ iq, const ft8gpu_message *__restrict__ msgs,
-                                  const ft8gpu_refined *__restrict__ refined, const int32_t *__restrict__ first,
-                                  const int32_t *__restrict__ n_msgs, int nframes, const SubTables *__restrict__ tab,
-                                  const MsgTables *__restrict__ mtab, uint32_t *__restrict__ scratch, ft8gpu_subtract_info *info) {
+// the estimate kernel of either shape (its LDS belongs to the one kernel that calls the instantiation); s_pulse: Q of the GFSK
+// shape, neither read nor allocated for CPFSK
+template <int kShape>
+__device__ __forceinline__ void estimate_body(const float *__restrict__ iq, const ft8gpu_message *__restrict__ msgs,
+                                              const ft8gpu_refined *__restrict__ refined, const int32_t *__restrict__ first,
+                                              const int32_t *__restrict__ n_msgs, int nframes, const SubTables *__restrict__ tab,
+                                              const SubGfskTables *__restrict__ gtab, const MsgTables *__restrict__ mtab,
+                                              uint32_t *__restrict__ scratch, ft8gpu_subtract_info *info) {
     __shared__ float s_wr[kTab], s_wi[kTab];
+    __shared__ uint32_t s_pulse[kShape == FT8GPU_SUBTRACT_GFSK ? kPulseSlots : 1];
     __shared__ __attribute__((aligned(16))) WaveLds s_wave[kWaves];
 
     const int lane = threadIdx.x & 63;
@@ -186,6 +248,8 @@ void ft8_subtract_estimate_kernel(const float *__restrict__ iq, const ft8gpu_mes
         s_wr[p] = w.x;
         s_wi[p] = w.y;
     }
+    if constexpr (kShape == FT8GPU_SUBTRACT_GFSK)
+        for (int i = threadIdx.x; i < kPulse; i += 256) s_pulse[i + (i >> 5)] = gtab->q[i];
     __syncthreads();
     const int mi = blk + wave;
     if (mi < lo || mi >= hi) return;                                  // wave-uniform: records outside [first, n_msgs) are not touched
@@ -224,10 +288,10 @@ void ft8_subtract_estimate_kernel(const float *__restrict__ iq, const ft8gpu_mes
 
     // ---- (c) the fine search: frequency, then time -----------------------------------------------------------------------------
     float pf_best, pt_best;
-    const float Pf = search<false>(pi, pq, L, s_wr, s_wi, S0, k4_0, lane);
+    const float Pf = search<false, kShape>(pi, pq, L, s_wr, s_wi, s_pulse, S0, k4_0, lane);
     const int di = first_max(L, Pf, lane, pf_best);
     const int k4 = k4_0 + di - FT8GPU_SUBTRACT_RANGE;
-    const float Pt4 = search<true>(pi, pq, L, s_wr, s_wi, S0, k4, lane);
+    const float Pt4 = search<true, kShape>(pi, pq, L, s_wr, s_wi, s_pulse, S0, k4, lane);
     const float Pt = lane == FT8GPU_SUBTRACT_RANGE ? pf_best : Pt4;   // pt[2] = P(S_0, k4*) = pf[d* + 2]
     const int ti = first_max(L, Pt, lane, pt_best);
     const int S = S0 + FT8GPU_SUBTRACT_TSTEP * (ti - FT8GPU_SUBTRACT_RANGE);
@@ -239,9 +303,15 @@ void ft8_subtract_estimate_kernel(const float *__restrict__ iq, const ft8gpu_mes
         wave_lds_sync();
         const int m = 2 * c + (lane >> 4), seg = lane & 15;
         if (lane < 32 && m < FT8GPU_NN) {
-            const uint32_t K = (uint32_t)k4 + 8u * (uint32_t)L.tone[m];
             float re, im;
-            seg_sum(L.plane[0], L.plane[1], s_wr, s_wi, kSeg * lane, 512u * (uint32_t)m * (uint32_t)k4 + K * (uint32_t)(kSeg * seg), K, re, im);
+            if constexpr (kShape == FT8GPU_SUBTRACT_GFSK) {
+                const uint32_t step = (uint32_t)k4 << 20;
+                seg_sum_gfsk(L.plane[0], L.plane[1], s_wr, s_wi, s_pulse, kSeg * lane, step * (uint32_t)(512 * m + kSeg * seg), step,
+                             pulse_tones(L.tone, m), seg, re, im);
+            } else {
+                const uint32_t K = (uint32_t)k4 + 8u * (uint32_t)L.tone[m];
+                seg_sum(L.plane[0], L.plane[1], s_wr, s_wi, kSeg * lane, 512u * (uint32_t)m * (uint32_t)k4 + K * (uint32_t)(kSeg * seg), K, re, im);
+            }
             L.ring[0][(32 * c + lane) & (kRing - 1)] = re;
             L.ring[1][(32 * c + lane) & (kRing - 1)] = im;
         }
@@ -287,6 +357,23 @@ void ft8_subtract_estimate_kernel(const float *__restrict__ iq, const ft8gpu_mes
     }
 }
 
+__global__ __launch_bounds__(256)
+void ft8_subtract_estimate_kernel(const float *__restrict__ iq, const ft8gpu_message *__restrict__ msgs,
+                                  const ft8gpu_refined *__restrict__ refined, const int32_t *__restrict__ first,
+                                  const int32_t *__restrict__ n_msgs, int nframes, const SubTables *__restrict__ tab,
+                                  const MsgTables *__restrict__ mtab, uint32_t *__restrict__ scratch, ft8gpu_subtract_info *info) {
+    estimate_body<FT8GPU_SUBTRACT_CPFSK>(iq, msgs, refined, first, n_msgs, nframes, tab, nullptr, mtab, scratch, info);
+}
+
+__global__ __launch_bounds__(256)
+void ft8_subtract_estimate_gfsk_kernel(const float *__restrict__ iq, const ft8gpu_message *__restrict__ msgs,
+                                       const ft8gpu_refined *__restrict__ refined, const int32_t *__restrict__ first,
+                                       const int32_t *__restrict__ n_msgs, int nframes, const SubTables *__restrict__ tab,
+                                       const SubGfskTables *__restrict__ gtab, const MsgTables *__restrict__ mtab,
+                                       uint32_t *__restrict__ scratch, ft8gpu_subtract_info *info) {
+    estimate_body<FT8GPU_SUBTRACT_GFSK>(iq, msgs, refined, first, n_msgs, nframes, tab, gtab, mtab, scratch, info);
+}
+
 // ---- apply ------------------------------------------------------------------------------------------------------------------
 struct ApplyHdr {
     int S[kMaxMessages];
@@ -294,11 +381,17 @@ struct ApplyHdr {
     uint32_t tones[kMaxMessages][20];
 };
 
-__global__ __launch_bounds__(256)
-void ft8_subtract_apply_kernel(const float *iq, float *out, const int32_t *__restrict__ first, const int32_t *__restrict__ n_msgs,
-                               int nframes, const SubTables *__restrict__ tab, const uint32_t *__restrict__ scratch) {
+__device__ __forceinline__ uint32_t hdr_tone(const uint32_t *tones, int m) { return (tones[m >> 2] >> (8 * (m & 3))) & 0xFFu; }
+
+// the apply kernel of either shape; s_q (Q in table order) and s_ramp: the GFSK shape's, neither read nor allocated for CPFSK
+template <int kShape>
+__device__ __forceinline__ void apply_body(const float *iq, float *out, const int32_t *__restrict__ first, const int32_t *__restrict__ n_msgs,
+                                           int nframes, const SubTables *__restrict__ tab, const SubGfskTables *__restrict__ gtab,
+                                           const uint32_t *__restrict__ scratch) {
     __shared__ float2 s_w[kTab];                                      // 32 KB: one 8-byte read per sample and record
     __shared__ ApplyHdr s_hdr;
+    __shared__ __attribute__((aligned(16))) uint32_t s_q[kShape == FT8GPU_SUBTRACT_GFSK ? kPulse + 3 : 4];
+    __shared__ float s_ramp[kShape == FT8GPU_SUBTRACT_GFSK ? kRamp : 1];
 
     const int frame = (int)(blockIdx.x / (unsigned)kParts);
     const int part = (int)(blockIdx.x - (unsigned)frame * kParts);
@@ -322,6 +415,10 @@ void ft8_subtract_apply_kernel(const float *iq, float *out, const int32_t *__res
     for (int i = threadIdx.x; i < kTab; i += 256) {
         s_w[i] = tab->w4[i];
     }
+    if constexpr (kShape == FT8GPU_SUBTRACT_GFSK) {
+        for (int i = threadIdx.x; i < kPulse; i += 256) s_q[i] = gtab->q[i];
+        if (threadIdx.x < kRamp) s_ramp[threadIdx.x] = gtab->ramp[threadIdx.x];
+    }
     const uint32_t *fs = scratch + ((size_t)frame * kMaxMessages + lo) * kSubStride;
     for (int i = threadIdx.x; i < cnt * 22; i += 256) {
         const int r = i / 22, k = i - 22 * r;
@@ -340,6 +437,45 @@ void ft8_subtract_apply_kernel(const float *iq, float *out, const int32_t *__res
             if ((unsigned)rel >= (unsigned)kSpan) continue;           // S* is a multiple of 8: all four samples or none
             const int m = rel >> 9;
             const uint32_t k4 = s_hdr.k4[r];
+            if constexpr (kShape == FT8GPU_SUBTRACT_GFSK) {
+                // (b') the four phases from Q, one 16-byte word per pulse term; (e') the ramp over a record's first and last 64 samples
+                const int k = rel & 511;
+                const uint32_t *tones = s_hdr.tones[r];
+                const uint32_t e0 = hdr_tone(tones, m > 0 ? m - 1 : 0), e1 = hdr_tone(tones, m);
+                const uint32_t e2 = hdr_tone(tones, m < FT8GPU_NN - 1 ? m + 1 : FT8GPU_NN - 1);
+                const uint4 qa = *reinterpret_cast<const uint4 *>(s_q + k + 1024), qb = *reinterpret_cast<const uint4 *>(s_q + k + 512);
+                const uint4 qc = *reinterpret_cast<const uint4 *>(s_q + k);
+                const uint32_t step = k4 << 20, lin = step * (uint32_t)rel;
+                const uint32_t i0 = (lin + e0 * qa.x + e1 * qb.x + e2 * qc.x + kHalfStep) >> 20;
+                const uint32_t i1 = (lin + step + e0 * qa.y + e1 * qb.y + e2 * qc.y + kHalfStep) >> 20;
+                const uint32_t i2 = (lin + 2u * step + e0 * qa.z + e1 * qb.z + e2 * qc.z + kHalfStep) >> 20;
+                const uint32_t i3 = (lin + 3u * step + e0 * qa.w + e1 * qb.w + e2 * qc.w + kHalfStep) >> 20;
+                const float2 A = reinterpret_cast<const float2 *>(fs + (size_t)r * kSubStride)[rel >> 5];
+                float2 A0 = A, A1 = A, A2 = A, A3 = A;
+                if (rel < kRamp || rel >= kSpan - kRamp) {
+                    const bool head = rel < kRamp;
+                    const float v0 = s_ramp[head ? rel : kSpan - 1 - rel], v1 = s_ramp[head ? rel + 1 : kSpan - 2 - rel];
+                    const float v2 = s_ramp[head ? rel + 2 : kSpan - 3 - rel], v3 = s_ramp[head ? rel + 3 : kSpan - 4 - rel];
+                    A0 = make_float2(A.x * v0, A.y * v0);
+                    A1 = make_float2(A.x * v1, A.y * v1);
+                    A2 = make_float2(A.x * v2, A.y * v2);
+                    A3 = make_float2(A.x * v3, A.y * v3);
+                }
+                float2 w;
+                w = s_w[i0];
+                a.x = a.x - (A0.x * w.x + A0.y * w.y);
+                b.x = b.x - (A0.y * w.x - A0.x * w.y);
+                w = s_w[i1];
+                a.y = a.y - (A1.x * w.x + A1.y * w.y);
+                b.y = b.y - (A1.y * w.x - A1.x * w.y);
+                w = s_w[i2];
+                a.z = a.z - (A2.x * w.x + A2.y * w.y);
+                b.z = b.z - (A2.y * w.x - A2.x * w.y);
+                w = s_w[i3];
+                a.w = a.w - (A3.x * w.x + A3.y * w.y);
+                b.w = b.w - (A3.y * w.x - A3.x * w.y);
+                continue;
+            }
             const uint32_t tone = (s_hdr.tones[r][m >> 2] >> (8 * (m & 3))) & 0xFFu;
             const uint32_t K = k4 + 8u * tone;
             uint32_t idx = (512u * (uint32_t)m * k4 + K * (uint32_t)(rel & 511)) & kTabMask;
@@ -361,6 +497,19 @@ void ft8_subtract_apply_kernel(const float *iq, float *out, const int32_t *__res
         dst_i[v] = a;
         dst_q[v] = b;
     }
+}
+
+__global__ __launch_bounds__(256)
+void ft8_subtract_apply_kernel(const float *iq, float *out, const int32_t *__restrict__ first, const int32_t *__restrict__ n_msgs,
+                               int nframes, const SubTables *__restrict__ tab, const uint32_t *__restrict__ scratch) {
+    apply_body<FT8GPU_SUBTRACT_CPFSK>(iq, out, first, n_msgs, nframes, tab, nullptr, scratch);
+}
+
+__global__ __launch_bounds__(256)
+void ft8_subtract_apply_gfsk_kernel(const float *iq, float *out, const int32_t *__restrict__ first, const int32_t *__restrict__ n_msgs,
+                                    int nframes, const SubTables *__restrict__ tab, const SubGfskTables *__restrict__ gtab,
+                                    const uint32_t *__restrict__ scratch) {
+    apply_body<FT8GPU_SUBTRACT_GFSK>(iq, out, first, n_msgs, nframes, tab, gtab, scratch);
 }
 
 // ---- the pass loop's bookkeeping ------------------------------------------------------------------------------------------
@@ -391,18 +540,27 @@ void ft8_subtract_gate_kernel(const int32_t *__restrict__ n_ref, int nframes, in
 }  // namespace
 
 hipError_t launch_subtract_estimate(const float *iq, const ft8gpu_message *msgs, const ft8gpu_refined *refined, const int32_t *first,
-                                    const int32_t *n_msgs, int nframes, const SubTables *tab, const MsgTables *mtab,
-                                    uint32_t *scratch, ft8gpu_subtract_info *info, hipStream_t s) {
+                                    const int32_t *n_msgs, int nframes, int shape, const SubTables *tab, const SubGfskTables *gtab,
+                                    const MsgTables *mtab, uint32_t *scratch, ft8gpu_subtract_info *info, hipStream_t s) {
+    if (shape != FT8GPU_SUBTRACT_CPFSK && (shape != FT8GPU_SUBTRACT_GFSK || !gtab)) return hipErrorInvalidValue;
     if (nframes <= 0) return hipSuccess;
-    ft8_subtract_estimate_kernel<<<dim3((unsigned)nframes * kBlocksPerFrame), dim3(256), 0, s>>>(iq, msgs, refined, first, n_msgs, nframes,
-                                                                                              tab, mtab, scratch, info);
+    const dim3 grid((unsigned)nframes * kBlocksPerFrame);
+    if (shape == FT8GPU_SUBTRACT_GFSK)
+        ft8_subtract_estimate_gfsk_kernel<<<grid, dim3(256), 0, s>>>(iq, msgs, refined, first, n_msgs, nframes, tab, gtab, mtab, scratch, info);
+    else
+        ft8_subtract_estimate_kernel<<<grid, dim3(256), 0, s>>>(iq, msgs, refined, first, n_msgs, nframes, tab, mtab, scratch, info);
     return hipGetLastError();
 }
 
-hipError_t launch_subtract_apply(const float *iq, float *out, const int32_t *first, const int32_t *n_msgs, int nframes,
-                                 const SubTables *tab, const uint32_t *scratch, hipStream_t s) {
+hipError_t launch_subtract_apply(const float *iq, float *out, const int32_t *first, const int32_t *n_msgs, int nframes, int shape,
+                                 const SubTables *tab, const SubGfskTables *gtab, const uint32_t *scratch, hipStream_t s) {
+    if (shape != FT8GPU_SUBTRACT_CPFSK && (shape != FT8GPU_SUBTRACT_GFSK || !gtab)) return hipErrorInvalidValue;
     if (nframes <= 0) return hipSuccess;
-    ft8_subtract_apply_kernel<<<dim3((unsigned)nframes * kParts), dim3(256), 0, s>>>(iq, out, first, n_msgs, nframes, tab, scratch);
+    const dim3 grid((unsigned)nframes * kParts);
+    if (shape == FT8GPU_SUBTRACT_GFSK)
+        ft8_subtract_apply_gfsk_kernel<<<grid, dim3(256), 0, s>>>(iq, out, first, n_msgs, nframes, tab, gtab, scratch);
+    else
+        ft8_subtract_apply_kernel<<<grid, dim3(256), 0, s>>>(iq, out, first, n_msgs, nframes, tab, scratch);
     return hipGetLastError();
 }
 

@@ -3,7 +3,8 @@
 percent, so only arms that share a box and a session are comparable.  Every arm decodes the same batch; arms are
 interleaved round by round; the records of all arms must be byte-identical.
   python tools/ab_libs.py --libs tools/ab/libft8gpu_prev.so rtlsdr_ft8d_amd/libft8gpu.so [--config 2|4] [--rounds 3] [--entry batch|messages]
---entry messages times ft8gpu_decode_messages (64-byte records of every message) instead of ft8gpu_decode_batch."""
+--entry messages times ft8gpu_decode_messages (64-byte records of every message) instead of ft8gpu_decode_batch; --entry
+subtracted times ft8gpu_decode_messages_subtracted at three passes (records, counts and the counts by pass in the digest)."""
 import argparse
 import hashlib
 import json
@@ -22,7 +23,7 @@ def main():
     ap.add_argument("--config", type=int, default=2, choices=(2, 4))
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--rounds", type=int, default=3)
-    ap.add_argument("--entry", choices=("batch", "messages"), default="batch")
+    ap.add_argument("--entry", choices=("batch", "messages", "subtracted"), default="batch")
     ap.add_argument("--torch-stream", action="store_true", help="run every arm on a torch.cuda.Stream (as bench.py does) instead of the context's own stream")
     args = ap.parse_args()
     import torch
@@ -45,7 +46,9 @@ def main():
     nres = torch.zeros((B,), dtype=torch.int32, device="cuda")
     torch.cuda.synchronize()
     res = [{"lib": p, "ms": [], "stages": None, "digest": None} for p in args.libs]
-    run = (lambda d: d.decode_batch_dev(iq, B, spots, nres)) if args.entry == "batch" else (lambda d: d.decode_messages_dev(iq, B, spots, nres))
+    nbp = torch.zeros((B, 3), dtype=torch.int32, device="cuda")
+    run = {"batch": lambda d: d.decode_batch_dev(iq, B, spots, nres), "messages": lambda d: d.decode_messages_dev(iq, B, spots, nres),
+           "subtracted": lambda d: d.decode_messages_subtracted_dev(iq, B, 3, spots, nres, nbp)}[args.entry]
     for _ in range(args.rounds):
         for dec, r in zip(decs, res):
             for _ in range(3):
@@ -61,7 +64,8 @@ def main():
             st = dec.timings()
             dec.enable_timing(False)
             r["stages"] = {k: round(v, 4) for k, v in st.items() if k.endswith("_ms")}
-            r["digest"] = hashlib.sha256(spots.cpu().numpy().tobytes() + nres.cpu().numpy().tobytes()).hexdigest()[:16]
+            r["digest"] = hashlib.sha256(spots.cpu().numpy().tobytes() + nres.cpu().numpy().tobytes() +
+                                         (nbp.cpu().numpy().tobytes() if args.entry == "subtracted" else b"")).hexdigest()[:16]
     for r in res:
         r["best_ms"] = min(r["ms"])
     out = {"frames": B, "config": args.config, "entry": args.entry, "steps": args.steps, "arms": res,

@@ -4,6 +4,7 @@ in one session, device pointers, on 4096 frames of the bench workload (20 signal
 
   python tools/bench_subtract.py [--json profiles/subtract_bench.json] [--steps 5] [--rounds 3] [--kernel-stats CSV]
   python tools/bench_subtract.py --stage-only 3          (three stage calls and nothing else: the program of a kernel trace)
+  python tools/bench_subtract.py --shapes 0 1 [--json profiles/subtract_gfsk_bench.json]    (the shaped entries, see below)
 
 Arms, interleaved round by round: the subtraction stage (estimate and apply kernels, in place on a copy of the frames) on the
 batch's own first-pass records, the refine stage those records need first, ft8gpu_decode_messages, ft8gpu_decode_messages_passes
@@ -12,7 +13,11 @@ Time = events on the context's stream around `steps` calls, after two warm-up ca
 kept.  --kernel-stats takes the trace_kernel_stats.csv of `rocprofv3 --kernel-trace --stats -- python tools/bench_subtract.py
 --stage-only N` and adds the two kernels' own times per stage call; the apply kernel's is set against the time its floor of one
 read and one write of every frame (768 KB) takes at 8 TB/s.  A machine without a GPU fails at ft8gpu_create; nothing is
-estimated."""
+estimated.
+--shapes 0 1 goes through the shaped entries (ft8gpu_subtract_messages_shaped, ft8gpu_decode_messages_subtracted_shaped): the
+stage and the whole path at two and three passes once per shape, the arms of shape 1 ("..._gfsk") right behind those of shape 0
+in every round, and each GFSK arm's ratio to its CPFSK arm.  With --stage-only, N stage calls per shape; --kernel-stats then
+finds the GFSK kernels beside the CPFSK ones and gives their ratios."""
 import argparse
 import csv
 import json
@@ -30,7 +35,8 @@ def kernel_times(path, calls):
     out = {}
     with open(path) as f:
         for row in csv.DictReader(f):
-            for key in ("ft8_subtract_estimate_kernel", "ft8_subtract_apply_kernel"):
+            for key in ("ft8_subtract_estimate_kernel", "ft8_subtract_apply_kernel", "ft8_subtract_estimate_gfsk_kernel",
+                        "ft8_subtract_apply_gfsk_kernel"):
                 if key in row["Name"]:
                     out[key] = {"launches": int(row["Calls"]), "ms_per_stage_call": round(float(row["TotalDurationNs"]) / 1e6 / calls, 4)}
     return out
@@ -43,6 +49,7 @@ def main():
     ap.add_argument("--rounds", type=int, default=3)
     ap.add_argument("--frames", type=int, default=FRAMES)
     ap.add_argument("--stage-only", type=int, default=0)
+    ap.add_argument("--shapes", type=int, nargs="+", choices=(0, 1), help="use the shaped entries, one set of arms per shape")
     ap.add_argument("--kernel-stats")
     ap.add_argument("--kernel-stats-calls", type=int, default=3)
     args = ap.parse_args()
@@ -70,20 +77,30 @@ def main():
         dec.refine_messages_dev(iq, msgs, n_msgs, B, refined)
         dec.synchronize()
         out["messages"] = int(n_msgs.sum().item())
-        stage = lambda: dec.subtract_messages_dev(x, msgs, refined, zero, n_msgs, B, x)     # in place: the figures do not depend on the samples
+        # in place: the figures do not depend on the samples.  shape None: the entries without a shape
+        stage_of = lambda shape: lambda: dec.subtract_messages_dev(x, msgs, refined, zero, n_msgs, B, x, shape=shape)
+        whole_of = lambda shape, passes, nbp: lambda: dec.decode_messages_subtracted_dev(iq, B, passes, msgs2, n_msgs2, nbp, shape=shape)
+        shapes = args.shapes or [None]
+        tag = lambda shape: "_gfsk" if shape == ft8.SUBTRACT_GFSK else ""
         if args.stage_only:
-            for _ in range(args.stage_only):
-                stage()
+            for shape in shapes:
+                for _ in range(args.stage_only):
+                    stage_of(shape)()
             dec.synchronize()
             return 0
-        arms = {"subtract_stage": stage,
-                "refine_stage": lambda: dec.refine_messages_dev(iq, msgs, n_msgs, B, refined),
-                "decode_messages": lambda: dec.decode_messages_dev(iq, B, msgs2, n_msgs2),
-                "decode_messages_passes_2": lambda: dec.decode_messages_passes_dev(iq, B, 2, msgs2, n_msgs2, nbp2),
-                "decode_messages_passes_3": lambda: dec.decode_messages_passes_dev(iq, B, 3, msgs2, n_msgs2, nbp3),
-                "decode_messages_subtracted_2": lambda: dec.decode_messages_subtracted_dev(iq, B, 2, msgs2, n_msgs2, nbp2),
-                "decode_messages_subtracted_3": lambda: dec.decode_messages_subtracted_dev(iq, B, 3, msgs2, n_msgs2, nbp3),
-                "ldpc_launch": lambda: dec.decode_candidates_dev(mag, cands, counts, B, status)}
+        arms = {}
+        for shape in shapes:
+            arms["subtract_stage" + tag(shape)] = stage_of(shape)
+        arms.update({"refine_stage": lambda: dec.refine_messages_dev(iq, msgs, n_msgs, B, refined),
+                     "decode_messages": lambda: dec.decode_messages_dev(iq, B, msgs2, n_msgs2),
+                     "decode_messages_passes_2": lambda: dec.decode_messages_passes_dev(iq, B, 2, msgs2, n_msgs2, nbp2),
+                     "decode_messages_passes_3": lambda: dec.decode_messages_passes_dev(iq, B, 3, msgs2, n_msgs2, nbp3)})
+        for passes, nbp in ((2, nbp2), (3, nbp3)):
+            for shape in shapes:
+                arms["decode_messages_subtracted_%d" % passes + tag(shape)] = whole_of(shape, passes, nbp)
+        arms["ldpc_launch"] = lambda: dec.decode_candidates_dev(mag, cands, counts, B, status)
+        if args.shapes:
+            out["shapes"] = args.shapes
         ms = {name: [] for name in arms}
 
         def timed(run):
@@ -107,6 +124,8 @@ def main():
         for name in arms:
             out["arms"][name]["ratio_to_ldpc_launch"] = round(out["arms"][name]["best_ms"] / ldpc, 4)
             out["arms"][name]["ratio_to_decode_messages"] = round(out["arms"][name]["best_ms"] / plain, 4)
+            if name.endswith("_gfsk") and name[:-5] in arms:
+                out["arms"][name]["ratio_to_cpfsk_arm"] = round(out["arms"][name]["best_ms"] / out["arms"][name[:-5]]["best_ms"], 4)
         # what the paths decode on this batch, counted once more outside the timed loops
         arms["decode_messages_passes_3"]()
         dec.synchronize()
@@ -114,6 +133,10 @@ def main():
         arms["decode_messages_subtracted_3"]()
         dec.synchronize()
         out["records_subtracted_by_pass"] = nbp3.view(B, 3).sum(dim=0).tolist()
+        if "decode_messages_subtracted_3_gfsk" in arms:                 # CPFSK frames: the bench workload's synthesiser makes no GFSK
+            arms["decode_messages_subtracted_3_gfsk"]()
+            dec.synchronize()
+            out["records_subtracted_gfsk_by_pass"] = nbp3.view(B, 3).sum(dim=0).tolist()
     floor_ms = B * 2 * 2 * ft8.NSAMPLES * 4 / HBM_BYTES_PER_S * 1e3
     out["apply_floor"] = {"bytes_per_frame": 2 * 2 * ft8.NSAMPLES * 4, "hbm_bytes_per_s": HBM_BYTES_PER_S, "floor_ms": round(floor_ms, 4)}
     if args.kernel_stats:
@@ -121,6 +144,10 @@ def main():
         k = out["kernels"].get("ft8_subtract_apply_kernel")
         if k:
             k["floor_over_measured"] = round(floor_ms / k["ms_per_stage_call"], 4)
+        for name in ("estimate", "apply"):
+            c, g = out["kernels"].get("ft8_subtract_%s_kernel" % name), out["kernels"].get("ft8_subtract_%s_gfsk_kernel" % name)
+            if c and g:
+                g["ratio_to_cpfsk_kernel"] = round(g["ms_per_stage_call"] / c["ms_per_stage_call"], 4)
     print(json.dumps(out))
     if args.json:
         with open(args.json, "w") as f:

@@ -14,6 +14,9 @@ ones again.
   depth    tools/subtract_accuracy.py: 10 log10(|x' - (x - s)|^2 / |s|^2), s the noiseless waveform as synthesised (the GFSK one in
            the GFSK run), 64 frames per set
   passes   tools/subtract_gain.py, rows cq 20 and cq 45: planted messages after 1, 2 and 3 passes, 96 frames each
+On the GFSK run, depth and passes are measured once more with the GFSK reference of the subtraction (shape 1 of
+tests/ft8_spec_subtract_gfsk.py; "cancellation_depth_gfsk_reference", "passes_gfsk_reference"): the same frames, the other
+reference.  profiles/subtract_gfsk_accuracy.json and profiles/subtract_gfsk_gain.json hold those figures from the tools themselves.
 No threshold is set on any of these figures."""
 import argparse
 import contextlib
@@ -80,10 +83,9 @@ def demod_frame(job):
 
 
 def passes_chunk(job):
-    name, inner = job
+    name, inner, shape = job
     import subtract_gain
-    with waveform(name):
-        return subtract_gain.decode_chunk(inner)
+    return subtract_gain.decode_chunk(inner + (name, shape))
 
 
 def part_decodes(pool, name, chosen):
@@ -111,21 +113,23 @@ def part_refine(name, threads):
     return out
 
 
-def part_depth(name, threads):
+def part_depth(name, threads, shape=0):
     import numpy as np
     import oracle_lib
+    import ft8_spec_subtract_gfsk as sg
     import subtract_craft as sc
     out = []
     with waveform(name):
         for label, snr, seed in (("noiseless", None, 1), ("0dB", 0.0, 2), ("-18dB", -18.0, 3)):
             iq, s, _f0, _start = sc.suppression_frames(oracle_lib, 64, snr, seed)
-            db = sc.suppression_db(oracle_lib, iq, s, nthreads=threads)
+            with sg.rule(shape):
+                db = sc.suppression_db(oracle_lib, iq, s, nthreads=threads)
             out.append({"set": label, "snr_db": snr, "decoded": int(len(db)), "median_db": round(float(np.median(db)), 2),
                         "p90_db": round(float(np.percentile(db, 90)), 2), "worst_db": round(float(db.max()), 2)})
     return out
 
 
-def part_passes(pool, name, procs):
+def part_passes(pool, name, procs, shape=0):
     import numpy as np
     from multipass_gain import PASSES, ROWS
     frames, seed0 = 96, 1000
@@ -134,7 +138,7 @@ def part_passes(pool, name, procs):
     rows = []
     for traffic, nsig, snr in (ROWS[0], ROWS[2]):
         assert (traffic, nsig) in (("cq", 20), ("cq", 45))
-        parts = pool.map(passes_chunk, [(name, (traffic, nsig, snr, seeds[i:i + per], (8, 2, 8))) for i in range(0, frames, per)], chunksize=1)
+        parts = pool.map(passes_chunk, [(name, (traffic, nsig, snr, seeds[i:i + per], (8, 2, 8)), shape) for i in range(0, frames, per)], chunksize=1)
         planted = [p for part in parts for p in part[0]]
         msgs = np.concatenate([part[1] for part in parts])
         nbp = np.concatenate([part[3] for part in parts])
@@ -182,8 +186,12 @@ def main():
                 res["refine"] = part_refine(name, a.procs)
             if "depth" in parts:
                 res["cancellation_depth"] = part_depth(name, a.procs)
+                if name == "gfsk":
+                    res["cancellation_depth_gfsk_reference"] = part_depth(name, a.procs, shape=1)
             if "passes" in parts:
                 res["passes"] = part_passes(pool, name, a.procs)
+                if name == "gfsk":
+                    res["passes_gfsk_reference"] = part_passes(pool, name, a.procs, shape=1)
             res["seconds"] = round(time.time() - t0, 1)
             doc[name] = res
             print(name, json.dumps(res), flush=True)

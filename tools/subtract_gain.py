@@ -2,9 +2,12 @@
 stages (tests/ft8_spec_subtract.py): planted messages decoded after 1, 2 and 3 passes, and decodes outside the planted set, over
 the rows, seeds and frame counts of tools/multipass_gain.py, with the masking path's figures from profiles/multipass_gain.json
 beside each.  Writes one JSON document.
+--waveform gfsk synthesises the same signals pulse-shaped (tools/gfsk_effect.waveform); --shape selects the reference the records
+are subtracted with (tests/ft8_spec_subtract_gfsk.py).  Several of either give every row once per waveform and shape.
 
   python tools/subtract_gain.py [--frames 96] [--seed 1000] [--out profiles/subtract_gain.json]
-                                [--smooth 8] [--range 2] [--tstep 8]      (other constants of the rule, for comparison only)"""
+                                [--smooth 8] [--range 2] [--tstep 8]      (other constants of the rule, for comparison only)
+  python tools/subtract_gain.py --rows 0 2 --waveform gfsk cpfsk --shape 0 1 --out profiles/subtract_gfsk_gain.json"""
 import argparse
 import concurrent.futures as cf
 import json
@@ -15,6 +18,7 @@ import time
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, "tests"))
+sys.path.insert(0, os.path.join(ROOT, "tools"))
 
 from multipass_gain import PASSES, ROWS  # noqa: E402  (tools/ is the script's directory)
 
@@ -28,22 +32,25 @@ def set_constants(smooth, rng, tstep):
 
 def decode_chunk(job):
     """a few frames of one row through the restated path (a worker process: the numpy restatement is single-threaded)"""
-    traffic, nsig, snr, seeds, consts = job
+    traffic, nsig, snr, seeds, consts = job[:5]
+    name, shape = job[5:] if len(job) > 5 else ("cpfsk", 0)
     import numpy as np
     import oracle_lib
     import synth_util as S
-    import ft8_spec_subtract as ss
+    import ft8_spec_subtract_gfsk as sg
+    from gfsk_effect import waveform
     from rtlsdr_ft8d_amd import workload
     oracle_lib.build()
     set_constants(*consts)
-    if traffic == "cq":
-        enc = S.oracle_encode_fn(oracle_lib)
-        fr = [S.make_frame(s, nsig, enc, snr_range=snr) for s in seeds]
-    else:
-        texts, tones = workload.mixed_message_pool(1024, seed=7)
-        fr = [S.make_mixed_frame(s, nsig, snr, texts, tones) for s in seeds]
+    with waveform(name):
+        if traffic == "cq":
+            enc = S.oracle_encode_fn(oracle_lib)
+            fr = [S.make_frame(s, nsig, enc, snr_range=snr) for s in seeds]
+        else:
+            texts, tones = workload.mixed_message_pool(1024, seed=7)
+            fr = [S.make_mixed_frame(s, nsig, snr, texts, tones) for s in seeds]
     iq = np.stack([f[0] for f in fr])
-    msgs, n, nbp, _res = ss.decode_passes_subtracted(oracle_lib, iq, PASSES, nthreads=1)
+    msgs, n, nbp, _res = sg.decode_passes_subtracted(oracle_lib, iq, PASSES, shape, nthreads=1)
     return [f[1] for f in fr], msgs, n, nbp
 
 
@@ -56,6 +63,8 @@ def main():
     ap.add_argument("--smooth", type=int, default=8)
     ap.add_argument("--range", type=int, default=2)
     ap.add_argument("--tstep", type=int, default=8)
+    ap.add_argument("--waveform", choices=("cpfsk", "gfsk"), nargs="+", default=["cpfsk"])
+    ap.add_argument("--shape", type=int, choices=(0, 1), nargs="+", default=[0])
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "subtract_gain.json"))
     a = ap.parse_args()
     import numpy as np
@@ -67,12 +76,14 @@ def main():
     seeds = list(range(a.seed, a.seed + a.frames))
     per = max(1, (a.frames + 2 * a.threads - 1) // (2 * a.threads))
     rows = []
+    plain = a.waveform == ["cpfsk"] and a.shape == [0]                  # the document this tool has always written
+    cases = [(k, row, name, shape) for k, row in enumerate(ROWS) for name in a.waveform for shape in a.shape]
     with cf.ProcessPoolExecutor(max_workers=a.threads) as ex:
-        for k, (traffic, nsig, snr) in enumerate(ROWS):
+        for k, (traffic, nsig, snr), name, shape in cases:
             if a.rows and k not in a.rows:
                 continue
             t0 = time.time()
-            parts = list(ex.map(decode_chunk, [(traffic, nsig, snr, seeds[i:i + per], consts) for i in range(0, a.frames, per)]))
+            parts = list(ex.map(decode_chunk, [(traffic, nsig, snr, seeds[i:i + per], consts, name, shape) for i in range(0, a.frames, per)]))
             planted = [p for part in parts for p in part[0]]
             msgs = np.concatenate([part[1] for part in parts])
             nbp = np.concatenate([part[3] for part in parts])
@@ -100,11 +111,15 @@ def main():
                        masking_outside_planted_by_pass=m["outside_planted_by_pass"] if same else None,
                        masking_gain_pct_by_pass=m["gain_pct_by_pass"] if same else None,
                        seconds=round(time.time() - t0, 1))
+            if not plain:
+                row = dict(waveform=name, shape=shape, reference=("cpfsk", "gfsk")[shape], **row)
             rows.append(row)
             print(json.dumps(row), flush=True)
     doc = dict(what="planted messages decoded after each pass with subtraction in the I/Q samples (CPU: the oracle's stages through "
                     "tests/ft8_spec_subtract.py), beside the masking path's figures of profiles/multipass_gain.json",
-               command="python tools/subtract_gain.py --frames %d --seed %d" % (a.frames, a.seed),
+               command="python tools/subtract_gain.py --frames %d --seed %d" % (a.frames, a.seed) +
+                       ("" if plain else " --rows %s --waveform %s --shape %s" % (" ".join(str(k) for k in a.rows or range(len(ROWS))),
+                                                                                  " ".join(a.waveform), " ".join(str(v) for v in a.shape))),
                seeds=[a.seed, a.seed + a.frames - 1], max_candidates=120, min_score=10, ldpc_iters=20,
                constants=dict(smooth=a.smooth, range=a.range, tstep=a.tstep),
                mixed_pool="workload.mixed_message_pool(1024, seed=7); a mixed frame carries nsig + 1 signals (one message twice)",
