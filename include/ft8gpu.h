@@ -1250,6 +1250,70 @@ int ft8gpu_decode_audio(ft8gpu_ctx *ctx, const void *pcm, int format, int nclips
  * refused with a line on stderr that names what was found: 0 = ok, -1 = refused (*nsamples = 0). */
 int ft8gpu_read_wav(const char *path, int16_t *out, int32_t cap, int32_t *nsamples);
 
+/* ---- wideband RX: many channels from one 2.4 Msps capture ----------------------------------------------------------------------
+ * (DESIGN.md "Wideband RX"; not in the reference, whose rtlsdr_callback keeps one 1.6 kHz band of a capture -- that one is
+ * ft8gpu_rx_decimate.)  A 2.4 Msps capture holds 2.4 MHz of spectrum; every channel the caller names becomes one frame of the
+ * decoder, and the capture's bytes are read once for all of them.  The rule is exact: stage A is integer arithmetic, stage B
+ * float32 with one IEEE operation per step, nothing fused, every sum sequential from +0 in the stated order.
+ *
+ * Input.  raw: unsigned bytes, I and Q interleaved, at FT8GPU_WIDE_RATE.  x[n] = (raw[2n] - 128) + i (raw[2n+1] - 128) as
+ *   integers (raw ^ 0x80 read as int8), 0 <= n < npairs, zero outside.  npairs is a positive multiple of 8, at most
+ *   FT8GPU_WIDE_MAX_PAIRS; every capture is 16-byte aligned.
+ * Channel.  freq_bin in units of 6.25 Hz from the capture's centre, |freq_bin| <= FT8GPU_WIDE_MAX_BIN (+-1.1 MHz).  The frame's
+ *   0 Hz is the centre + 6.25 freq_bin, and the decoder's bins 0 .. 511 are the 1600 Hz above it (a USB dial frequency).
+ *   F = freq_bin + 128 is the band's centre; c = floor((F + 32) / 64); q = F - 64 c, in [-32, 31].
+ * Stage A, integers.  w1[i] = (lrint(32767 cos(2 pi i / 6000)), -lrint(32767 sin(2 pi i / 6000))) as int16, computed in double
+ *   (ft8gpu_wide_mixer1).  u[n] = x[n] * w1[(n c) mod 6000] (the mathematical mod), a complex integer product: it mixes down by
+ *   400 c Hz, and each component is below 2^23.  g[0 .. 496] is the four-fold convolution of a 125-sample boxcar (symmetric about
+ *   j = 248, sum 125^4).  v[m] = sum over j of g[j] * u[125 m + 248 - j] in int64: a fourth-order CIC decimating by 125 to
+ *   19 200 sps, centred on sample 125 m.  |v| < 2^52: nothing wraps, and the value is the same however it is summed.
+ * Stage B, float32.  vf[m] = ((float)Re v[m] * c0, (float)Im v[m] * c0), the conversion rounding to nearest even,
+ *   c0 = (float)(1 / (32767 * 125^4 * 128)).  w2[i] = (cos, -sin)(2 pi i / 3072), each the float of the double value
+ *   (ft8gpu_wide_mixer2).  z[m] = vf[m] * w2[(m q) mod 3072]: zr = vr * wr - vi * wi, zi = vr * wi + vi * wr, four products, one
+ *   subtraction, one addition.
+ *   Taps (ft8gpu_wide_taps), in double: t[k] = (sinc((3200 * d) / 19200) * I0(9 * sqrt(1 - (d / 46)^2))) / I0(9) for k = 0 .. 92,
+ *   d = k - 46, and 0 outside (sinc and I0 as in the audio stage above); hh[i] = ((1 + 2 a) * t[i-1] - a * t[i]) - a * t[i-2],
+ *   i = 0 .. 94, a = 0.1685 (the CIC's droop compensation); s = the sum of hh, i ascending from 0; h[i] = (float)(hh[i] / s);
+ *   h[95] = 0.  95 taps centred on 47.
+ *   y[p] = sum over k = 0 .. 94, ascending, of h[k] * z[6 p + 47 - k], real and imaginary parts separately, each term a product
+ *   and then an add, for 0 <= p < 48000.  Output p is centred on input sample 750 p: a record's dt_s is on the capture's time axis.
+ *   out[p] = y[p] * j^p as swaps and negations: p mod 4 = 0: (yr, yi); 1: (-yi, yr); 2: (-yr, -yi); 3: (yi, -yr), where -a is
+ *   0 - a, so that a zero stays +0.  All 48000 outputs follow the rule; where the window holds no sample they are +0.
+ *   The frame is planar, [2][48000].  normalise != 0 then scales the frame by (float)(0.5 / (double)max(1e-24f, peak)), peak the
+ *   largest |value| of both planes: the peak normalisation of ft8gpu_rx_decimate.
+ * Whole chain, float taps times the exact response of g, over every q: at most -84 dB at or beyond 2400 Hz from the band's centre
+ * (the only offsets that alias into the bins the decoder reads), within +-0.057 dB up to 800 Hz (the CIC's tilt at the 200 Hz
+ * residual of |q| = 32; +-0.0003 dB at q = 0).  Every capture starts from zero state. */
+#define FT8GPU_WIDE_RATE         2400000
+#define FT8GPU_WIDE_MAX_PAIRS    36000000   /* 15 s */
+#define FT8GPU_WIDE_MIX1         6000
+#define FT8GPU_WIDE_MIX2         3072
+#define FT8GPU_WIDE_TAPS         96
+#define FT8GPU_WIDE_MAX_CHANNELS 16
+#define FT8GPU_WIDE_MAX_BIN      176000
+/* the tables of the rule (host, plain C): w1 as 6000 int16 pairs, w2 as 3072 float pairs, h[0 .. 95] */
+void ft8gpu_wide_mixer1(int16_t out[2 * FT8GPU_WIDE_MIX1]);
+void ft8gpu_wide_mixer2(float out[2 * FT8GPU_WIDE_MIX2]);
+void ft8gpu_wide_taps(float out[FT8GPU_WIDE_TAPS]);
+/* stage entry: raw [ncaptures][2 * npairs], freq_bin [nchannels] (host memory in both pointer forms) -> iq
+ * [ncaptures][nchannels][2][48000].  Host or device pointers by `flags` (device form: raw and iq 16-byte aligned), captures in
+ * chunks of max_frames.  Refused before anything is enqueued, the outputs untouched: a NULL context or array, nchannels outside
+ * [1, 16], a freq_bin beyond +-176000, npairs zero, not a multiple of 8 or above 36 000 000, a misaligned raw (device form).
+ * The 19 200 sps planes between the stages are allocated on the first call (a failed allocation is reported and leaves the
+ * context usable) and freed at ft8gpu_destroy. */
+int ft8gpu_wide_frames(ft8gpu_ctx *ctx, const uint8_t *raw, int ncaptures, size_t npairs, const int32_t *freq_bin,
+                       int nchannels, float *iq, int normalise, int flags);
+/* The whole path: the frames capture * nchannels + channel, normalised, go through the ft8gpu_decode_messages path, at most
+ * max_frames at a time.  Then the channels of a capture are merged: walking the channels in the caller's order and a channel's
+ * records in their order, a record is dropped if its 12 a91 bytes equal those of a record already kept for the capture whose
+ * channel lies less than 256 bins away (the bands overlap); a kept record is the channel's record with freq_hz =
+ * (cand.freq_offset + freq_bin + (float)cand.freq_sub / 2) * 6.25f (the integer add first; exact, on the capture's axis relative
+ * to its centre, possibly negative) and pad[0] = the channel's index; the walk stops at 50 * nchannels records.
+ * msgs [ncaptures][50 * nchannels], n_msgs [ncaptures]; records at and behind n_msgs[c] are left untouched.  Arguments are
+ * refused as by ft8gpu_wide_frames. */
+int ft8gpu_decode_wide(ft8gpu_ctx *ctx, const uint8_t *raw, int ncaptures, size_t npairs, const int32_t *freq_bin,
+                       int nchannels, ft8gpu_message *msgs, int32_t *n_msgs, int flags);
+
 /* ---- tooling: encoder + synthetic frames (pack77 / ft8_encode / CPFSK synth of
  *      decoderSelfTest, rtlsdr_ft8d.c:924-955) --------------------------------------------- */
 /* Message text -> 77 bits in 10 bytes (pack77, :927); 0 = ok, -1 = the text fits no message type.  Tokens are separated

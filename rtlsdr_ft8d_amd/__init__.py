@@ -97,6 +97,12 @@ AUDIO_MAX_BANDS = 4              # FT8GPU_AUDIO_MAX_BANDS
 AUDIO_MAX_BASE = 704             # FT8GPU_AUDIO_MAX_BASE
 AUDIO_S16, AUDIO_F32 = 0, 1      # FT8GPU_AUDIO_S16 / _F32
 GFSK_IQ, GFSK_AUDIO = 0, 1       # FT8GPU_GFSK_IQ / _AUDIO
+WIDE_RATE = 2400000              # FT8GPU_WIDE_RATE
+WIDE_MAX_PAIRS = 36000000        # FT8GPU_WIDE_MAX_PAIRS
+WIDE_MIX1, WIDE_MIX2 = 6000, 3072    # FT8GPU_WIDE_MIX1 / _MIX2
+WIDE_TAPS = 96                   # FT8GPU_WIDE_TAPS
+WIDE_MAX_CHANNELS = 16           # FT8GPU_WIDE_MAX_CHANNELS
+WIDE_MAX_BIN = 176000            # FT8GPU_WIDE_MAX_BIN
 GFSK_SPS_IQ, GFSK_SPS_AUDIO = 512, 1920   # FT8GPU_GFSK_SPS_IQ / _AUDIO
 GFSK_TWIDDLES = 4096             # FT8GPU_GFSK_TWIDDLES
 GFSK_MAX_SIGNALS = 64            # FT8GPU_GFSK_MAX_SIGNALS
@@ -191,6 +197,7 @@ ABI_SYMBOLS = [
     "ft8gpu_audio_taps", "ft8gpu_audio_mixer", "ft8gpu_audio_frames", "ft8gpu_decode_audio", "ft8gpu_read_wav",
     "ft8gpu_gfsk_pulse", "ft8gpu_gfsk_ramp", "ft8gpu_gfsk_twiddles", "ft8gpu_synth_gfsk_frames", "ft8gpu_synth_gfsk_audio",
     "ft8gpu_write_wav",
+    "ft8gpu_wide_mixer1", "ft8gpu_wide_mixer2", "ft8gpu_wide_taps", "ft8gpu_wide_frames", "ft8gpu_decode_wide",
     "ft8_find_sync", "ft8_decode", "ft8_encode", "pack77",            # ft8_lib level (include/ft8_lib/ft8/*.h)
     "initFFTW", "freeFFTW", "ft8_subsystem", "ft8gpu_read_raw_iq", "ft8gpu_read_c2", "ft8gpu_write_raw_iq",
 ]
@@ -385,6 +392,12 @@ def _declare(L):
         L.ft8gpu_synth_gfsk_audio.argtypes = [vp, vp, C.c_int, C.c_int, C.c_int, C.c_float, C.c_uint64, C.c_uint64, C.c_float, C.c_int,
                                               vp, C.c_int]
         L.ft8gpu_write_wav.argtypes = [C.c_char_p, vp, C.c_int32]
+    if hasattr(L, "ft8gpu_wide_frames"):                  # absent from older builds loaded by load_library_at
+        for f in (L.ft8gpu_wide_mixer1, L.ft8gpu_wide_mixer2, L.ft8gpu_wide_taps):
+            f.argtypes = [vp]
+            f.restype = None
+        L.ft8gpu_wide_frames.argtypes = [vp, vp, C.c_int, C.c_size_t, vp, C.c_int, vp, C.c_int, C.c_int]
+        L.ft8gpu_decode_wide.argtypes = [vp, vp, C.c_int, C.c_size_t, vp, C.c_int, vp, vp, C.c_int]
     L.ft8gpu_rx_decimate.argtypes = [vp, vp, C.c_int, C.c_size_t, vp, C.c_int, C.c_int]
     if hasattr(L, "ft8gpu_rx_stream"):                    # absent from older builds loaded by load_library_at
         L.ft8gpu_rx_stream.argtypes = [vp, vp, C.c_int, C.c_int, C.c_size_t, vp, vp, vp, C.c_int, C.c_int]
@@ -1294,6 +1307,46 @@ class Decoder:
         self._ck(self.lib.ft8gpu_decode_audio(self.h, _ptr(pcm_dev), int(fmt), int(nclips), int(nsamples), bases.ctypes.data, len(bases),
                                             _ptr(msgs_dev), _ptr(n_msgs_dev), DEVICE_PTRS))
 
+    def wide_frames(self, raw, freq_bins, normalise=False):
+        """the wideband RX front end (ft8gpu_wide_frames): 2.4 Msps captures, uint8 [ncaptures][2 * npairs] -> iq
+        [ncaptures][nchannels][2][48000], the 1600 Hz above the capture's centre + 6.25 * freq_bin Hz as a frame of the decoder"""
+        raw = np.ascontiguousarray(raw, np.uint8)
+        assert raw.ndim == 2
+        bins = np.ascontiguousarray(freq_bins, np.int32).reshape(-1)
+        out = np.zeros((raw.shape[0], len(bins), 2, NSAMPLES), np.float32)
+        self._ck(self.lib.ft8gpu_wide_frames(self.h, raw.ctypes.data, raw.shape[0], raw.shape[1] // 2, bins.ctypes.data, len(bins),
+                                           out.ctypes.data, int(normalise), HOST_PTRS))
+        return out
+
+    def wide_frames_dev(self, raw_dev, ncaptures, npairs, freq_bins, iq_dev, normalise=False):
+        """raw_dev [ncaptures][2 * npairs] and iq_dev [ncaptures][nchannels][2][48000] (both 16-byte aligned) in HBM; freq_bins
+        stay on the host"""
+        bins = np.ascontiguousarray(freq_bins, np.int32).reshape(-1)
+        self._ck(self.lib.ft8gpu_wide_frames(self.h, _ptr(raw_dev), int(ncaptures), int(npairs), bins.ctypes.data, len(bins),
+                                           _ptr(iq_dev), int(normalise), DEVICE_PTRS))
+
+    def decode_wide(self, raw, freq_bins, msgs=None):
+        """the whole path from 2.4 Msps captures (ft8gpu_decode_wide) -> (msgs [ncaptures][50 * nchannels], n_msgs [ncaptures]):
+        every channel's messages, a message heard in two overlapping channels once, freq_hz relative to the capture's centre,
+        pad[0] the channel it was taken from"""
+        raw = np.ascontiguousarray(raw, np.uint8)
+        assert raw.ndim == 2
+        bins = np.ascontiguousarray(freq_bins, np.int32).reshape(-1)
+        shape = (raw.shape[0], MAX_MESSAGES * max(len(bins), 1))
+        if msgs is None:
+            msgs = np.zeros(shape, MESSAGE_DTYPE)
+        assert msgs.dtype == MESSAGE_DTYPE and msgs.shape == shape and msgs.flags["C_CONTIGUOUS"]
+        n = np.zeros(raw.shape[0], np.int32)
+        self._ck(self.lib.ft8gpu_decode_wide(self.h, raw.ctypes.data, raw.shape[0], raw.shape[1] // 2, bins.ctypes.data, len(bins),
+                                           msgs.ctypes.data, n.ctypes.data, HOST_PTRS))
+        return msgs, n
+
+    def decode_wide_dev(self, raw_dev, ncaptures, npairs, freq_bins, msgs_dev, n_msgs_dev):
+        """raw_dev, msgs_dev [ncaptures][50 * nchannels] and n_msgs_dev [ncaptures] in HBM; freq_bins stay on the host"""
+        bins = np.ascontiguousarray(freq_bins, np.int32).reshape(-1)
+        self._ck(self.lib.ft8gpu_decode_wide(self.h, _ptr(raw_dev), int(ncaptures), int(npairs), bins.ctypes.data, len(bins),
+                                           _ptr(msgs_dev), _ptr(n_msgs_dev), DEVICE_PTRS))
+
     def ap_candidates_dev(self, mag_dev, cands_dev, counts_dev, status_in_dev, nframes, hyps, max_hard_errors, status_out_dev, info_dev):
         """status_out_dev may be status_in_dev; info_dev: [nframes][max_candidates] 8-byte records; hyps stay on the host"""
         hyps = _ap_hyps(hyps)
@@ -1624,6 +1677,27 @@ def audio_mixer():
     """ft8gpu_audio_mixer: wm[i] = (cos, -sin)(2 pi i / 1920) as float32 [1920][2]"""
     out = np.zeros((AUDIO_MIX, 2), np.float32)
     load_library().ft8gpu_audio_mixer(out.ctypes.data)
+    return out
+
+
+def wide_mixer1():
+    """ft8gpu_wide_mixer1: w1[i] = (lrint(32767 cos), -lrint(32767 sin))(2 pi i / 6000) as int16 [6000][2]"""
+    out = np.zeros((WIDE_MIX1, 2), np.int16)
+    load_library().ft8gpu_wide_mixer1(out.ctypes.data)
+    return out
+
+
+def wide_mixer2():
+    """ft8gpu_wide_mixer2: w2[i] = (cos, -sin)(2 pi i / 3072) as float32 [3072][2]"""
+    out = np.zeros((WIDE_MIX2, 2), np.float32)
+    load_library().ft8gpu_wide_mixer2(out.ctypes.data)
+    return out
+
+
+def wide_taps():
+    """ft8gpu_wide_taps: the second stage's low-pass of the wideband RX front end as float32 [96]"""
+    out = np.zeros(WIDE_TAPS, np.float32)
+    load_library().ft8gpu_wide_taps(out.ctypes.data)
     return out
 
 

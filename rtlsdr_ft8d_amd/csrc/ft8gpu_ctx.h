@@ -1,7 +1,7 @@
 // ft8gpu_ctx.h -- the context object and the helpers every host-side translation unit of the C ABI shares: api_context.hip,
 // api_mem.hip, api_pipeline.hip, api_multi.hip, api_stages.hip, api_messages.hip, api_multipass.hip, api_osd.hip, api_ap.hip,
 // api_glue.hip, api_rx_stream.hip, api_callhash.hip, api_match.hip, api_combine.hip, api_refine.hip, api_subtract.hip,
-// api_demod.hip, api_audio.hip, api_gfsk.hip.  Not installed.
+// api_demod.hip, api_audio.hip, api_gfsk.hip, api_wide.hip.  Not installed.
 #pragma once
 #include "ctx_mem.h"
 #include "ft8gpu_internal.h"
@@ -101,6 +101,14 @@ struct ft8gpu_ctx {
     ft8gpu_message *d_audio_bmsgs = nullptr;   // the bands' records [max_frames][4][50] and counts [max_frames][4],
     int32_t *d_audio_bn = nullptr;
     ft8gpu_message *d_audio_msgs = nullptr;    // and host-pointer staging of the merged records [max_frames][200]
+    struct WideTables *d_widetab = nullptr;    // wideband RX, lazily on its first call: the constant tables,
+    void *d_wide_planes = nullptr;         //   the 19 200 sps planes between its stages (a run of captures times the channels),
+    void *d_wide_raw = nullptr;            //   host-pointer staging of a chunk's captures,
+    float *d_wide_iq = nullptr;            //   the frame buffer of the whole path and of the host form [max_frames][2][48000],
+    ft8gpu_message *d_wide_cmsgs = nullptr;    // the channels' records [captures][channels][50] and counts of a chunk,
+    int32_t *d_wide_cn = nullptr;
+    ft8gpu_message *d_wide_msgs = nullptr;     // and host-pointer staging of the merged records
+    size_t wide_planes_cap = 0, wide_raw_cap = 0, wide_cmsgs_cap = 0, wide_cn_cap = 0, wide_msgs_cap = 0;
     struct GfskTables *d_gfsktab = nullptr;    // GFSK synthesiser, lazily on its first call: the constant tables,
     struct GfskHeader *d_gfsk_hdr = nullptr;   //   the signal headers of a call (grown as needed),
     size_t gfsk_hdr_cap = 0;
