@@ -15,6 +15,7 @@
 // with two waves per SIMD, 2.8 ms with three).  The mixing, the tap products and the sums are plain C++; -ffp-contract=off keeps
 // every product and add a single IEEE operation.
 #include "audio.h"
+#include "merge_dev.h"
 
 namespace {
 
@@ -180,36 +181,13 @@ void ft8_audio_frames_kernel(const void *__restrict__ pcm_, int nsamples, AudioB
     }
 }
 
-// One thread per clip: a record is 16 dwords (float members give 4-byte alignment); a91 = dwords 12 .. 14, freq_hz = dword 7,
-// cand.freq_offset / freq_sub = the low half / the top byte of dword 11, pad[0] = the low byte of dword 15.
+// One thread per clip: merge_dev.h's merge over the clip's bands; the bands of a clip overlap, so equal a91 is a duplicate
 __global__ __launch_bounds__(64)
 void ft8_audio_merge_kernel(const ft8gpu_message *__restrict__ band_msgs, const int32_t *__restrict__ band_n, int nclips,
                             AudioBands bands, ft8gpu_message *msgs, int32_t *__restrict__ n_msgs) {
     const int c = blockIdx.x * 64 + threadIdx.x;
     if (c >= nclips) return;
-    const int cap = kMaxMessages * bands.n;
-    uint32_t *dst = (uint32_t *)(msgs + (size_t)c * cap);
-    int kept = 0;
-    for (int b = 0; b < bands.n; ++b) {
-        int n = band_n[c * bands.n + b];
-        n = n < 0 ? 0 : n > kMaxMessages ? kMaxMessages : n;
-        const uint32_t *src = (const uint32_t *)(band_msgs + ((size_t)c * bands.n + b) * kMaxMessages);
-        for (int k = 0; k < n && kept < cap; ++k) {
-            const uint32_t *r = src + 16 * k;
-            bool dup = false;
-            for (int i = 0; i < kept && !dup; ++i)
-                dup = dst[16 * i + 12] == r[12] && dst[16 * i + 13] == r[13] && dst[16 * i + 14] == r[14];
-            if (dup) continue;
-            uint32_t *d = dst + 16 * kept;
-            for (int i = 0; i < 16; ++i) d[i] = r[i];
-            const int fo = (int16_t)(r[11] & 0xffffu);
-            const int fs = (int)(r[11] >> 24);
-            d[7] = __float_as_uint(((float)(fo + bands.base[b]) + (float)fs / 2) * 6.25f);
-            d[15] = (r[15] & 0xffffff00u) | (uint32_t)b;
-            ++kept;
-        }
-    }
-    n_msgs[c] = kept;
+    merge_parts<false>(band_msgs, band_n, c, bands.n, bands.base, msgs, n_msgs);
 }
 
 }  // namespace

@@ -11,6 +11,7 @@
 #include "unpack_dev.h"
 #include "bp_math.h"
 #include "ldpc_lds_layout.h"
+#include "wave_dev.h"
 #include <stddef.h>
 #include <stdlib.h>
 #include <type_traits>
@@ -77,12 +78,6 @@ __device__ __forceinline__ float add_f32(float a, float b) {
 // (What the guard of iteration k > 0 sees depends on the sums of messages and has no such bound.)
 __device__ __forceinline__ uint32_t guard_key(float v) { return (__float_as_uint(v) << 1) - 1u; }
 constexpr uint32_t kGuardMin = ((127u - 59u) << 24) - 1u;       // guard_key(0x1p-59f)
-
-__device__ __forceinline__ void wave_lds_sync() {
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-}
 
 // sum over the 64 lanes with DPP adds (no LDS crossbar round trips); the total comes back uniform
 __device__ __forceinline__ int wave_sum(int v) {

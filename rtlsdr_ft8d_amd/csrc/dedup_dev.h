@@ -1,16 +1,12 @@
-// dedup_dev.h -- the dedup of rtlsdr_ft8d.c:1487-1507 as the wave-per-frame kernels run it (spots.hip, messages.hip):
-// staged texts in canonical form, strcmp == 0 as dword equality, and the leader loop that numbers the new messages of a
-// chunk of 64 candidates in list order.  Shared so that both output paths keep exactly the same messages in the same order.
+// dedup_dev.h -- the dedup of rtlsdr_ft8d.c:1487-1507 as the wave-per-frame kernels run it (spots.hip, and record_dev.h for
+// messages.hip and multipass.hip): staged texts in canonical form, strcmp == 0 as dword equality, and the leader loop that
+// numbers the new messages of a chunk of 64 candidates in list order.  Shared so that both output paths keep exactly the
+// same messages in the same order.  (wave_lds_sync comes from wave_dev.h.)
 #pragma once
 #include "ft8gpu_internal.h"
+#include "wave_dev.h"
 
 namespace {
-
-__device__ __forceinline__ void wave_lds_sync() {
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-}
 
 constexpr int kTextDw = 7;                    // message_t.text[25] in 7 aligned dwords (bytes 25..27 are 0)
 

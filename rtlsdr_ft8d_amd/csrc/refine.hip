@@ -19,7 +19,9 @@
 //   segment sums, per wave: two planes of 80 floats.
 // No scratch.  Indices: (k * j) mod 1024 is formed in uint32, which is exact for every int32 k and j.
 #include "refine.h"
+#include "span_dev.h"
 #include "tone_dev.h"
+#include "wave_dev.h"
 #include <stddef.h>
 
 namespace {
@@ -29,39 +31,13 @@ constexpr int kSymSegs = 512 / kSeg;                           // 16 segments pe
 constexpr int kRange = FT8GPU_REFINE_RANGE;
 constexpr int kOffsets = 2 * kRange + 1;                       // 33
 constexpr int kSpanSegs = kSymSegs + 2 * kRange;               // 48 segments cover every offset of a symbol
-constexpr int kSegPitch = kSeg + 1;
+constexpr int kSegPitch = kStagePitch;                         // stage_span's layout (span_dev.h)
 constexpr int kPlane = kSpanSegs * kSegPitch;                  // 1584 floats
 constexpr int kSums = 80;                                      // 4 neighbours x 16 segments + 16 of the empty tone
 constexpr int kWaves = 4;
 constexpr int kBlocksPerFrame = (kMaxMessages + kWaves - 1) / kWaves;
-static_assert(kSeg == 32 && kSpanSegs <= 64 && kOffsets <= 64 && kSpanSegs <= kSums, "lane assignment");
+static_assert(kSeg == kStageSeg && kSpanSegs <= 64 && kOffsets <= 64 && kSpanSegs <= kSums, "lane assignment");
 static_assert(sizeof(ft8gpu_message) == 64 && sizeof(ft8gpu_refined) == 48, "record sizes");
-
-__device__ __forceinline__ void wave_lds_sync() {
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-}
-
-// NSEG segments from sample j0 (a multiple of 4) into the wave's planes; samples outside the frame are zero, not read
-template <int NSEG>
-__device__ __forceinline__ void stage_span(const float *__restrict__ pi, const float *__restrict__ pq, int j0, float *s_i, float *s_q,
-                                           int lane) {
-    static_assert(NSEG * kSeg / 4 % 64 == 0, "whole rounds of 64 float4");
-#pragma unroll
-    for (int r = 0; r < NSEG * kSeg / 4 / 64; ++r) {
-        const int v = lane + 64 * r;
-        const int j = j0 + 4 * v;
-        float4 a = make_float4(0.0f, 0.0f, 0.0f, 0.0f), b = a;
-        if (j >= 0 && j < kNSamples) {                                       // 48000 is a multiple of 4: all four or none
-            a = *reinterpret_cast<const float4 *>(pi + j);
-            b = *reinterpret_cast<const float4 *>(pq + j);
-        }
-        const int p = 4 * v + (v >> 3);
-        s_i[p] = a.x; s_i[p + 1] = a.y; s_i[p + 2] = a.z; s_i[p + 3] = a.w;
-        s_q[p] = b.x; s_q[p + 1] = b.y; s_q[p + 2] = b.z; s_q[p + 3] = b.w;
-    }
-}
 
 // g(k, q) of the segment staged at `seg`, whose first sample is j: sequential in j from +0
 __device__ __forceinline__ void seg_sum(const float *s_i, const float *s_q, const float *s_twr, const float *s_twi, int seg, int k, int j,

@@ -33,7 +33,9 @@
 // pulse term (S* is a multiple of 8 and j of 4), and the 64-entry ramp beside it; only the first and last 64 samples of a
 // record take the ramp's two extra products.
 #include "subtract.h"
+#include "span_dev.h"
 #include "tone_dev.h"
+#include "wave_dev.h"
 #include <stddef.h>
 
 namespace {
@@ -45,7 +47,9 @@ constexpr int kSymSegs = 16;
 constexpr int kSmooth = FT8GPU_SUBTRACT_SMOOTH;
 constexpr int kHyp = 2 * FT8GPU_SUBTRACT_RANGE + 1;            // 5 hypotheses per search
 constexpr int kPlaneSegs = 32;
-constexpr int kPlane = kPlaneSegs * (kSeg + 1);                // 1056 floats
+constexpr int kPlane = kPlaneSegs * kStagePitch;               // 1056 floats, stage_span's layout (span_dev.h)
+constexpr int kTimeSpanSegs = 24, kFreqSpanSegs = 16, kAmpSpanSegs = 32;   // what the two searches and the amplitude step stage at a time
+static_assert(kSeg == kStageSeg && kTimeSpanSegs <= kPlaneSegs && kFreqSpanSegs <= kPlaneSegs && kAmpSpanSegs <= kPlaneSegs, "a staged span fits a plane");
 constexpr int kRing = 64;
 constexpr int kWaves = 4;
 constexpr int kBlocksPerFrame = (kMaxMessages + kWaves - 1) / kWaves;
@@ -62,33 +66,7 @@ static_assert(kHyp == 5 && kSmooth == 8 && FT8GPU_SUBTRACT_TSTEP == 8 && kTab ==
 static_assert(kPartSamples * kParts == kNSamples && kPartSamples % 4 == 0, "apply parts");
 static_assert(sizeof(ft8gpu_message) == 64 && sizeof(ft8gpu_refined) == 48 && sizeof(ft8gpu_subtract_info) == 64, "record sizes");
 
-__device__ __forceinline__ void wave_lds_sync() {
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-}
-
 __device__ __forceinline__ int tab_slot(uint32_t idx) { return (int)((idx & 31u) << 7 | idx >> 5); }
-
-// NSEG segments from sample j0 (a multiple of 4) into the wave's planes; samples outside the frame are zero, not read
-template <int NSEG>
-__device__ __forceinline__ void stage_span(const float *__restrict__ pi, const float *__restrict__ pq, int j0, float *s_i, float *s_q,
-                                           int lane) {
-    static_assert(NSEG * kSeg / 4 % 64 == 0 && NSEG <= kPlaneSegs, "whole rounds of 64 float4");
-#pragma unroll
-    for (int r = 0; r < NSEG * kSeg / 4 / 64; ++r) {
-        const int v = lane + 64 * r;
-        const int j = j0 + 4 * v;
-        float4 a = make_float4(0.0f, 0.0f, 0.0f, 0.0f), b = a;
-        if (j >= 0 && j < kNSamples) {                                       // 48000 is a multiple of 4: all four or none
-            a = *reinterpret_cast<const float4 *>(pi + j);
-            b = *reinterpret_cast<const float4 *>(pq + j);
-        }
-        const int p = 4 * v + (v >> 3);
-        s_i[p] = a.x; s_i[p + 1] = a.y; s_i[p + 2] = a.z; s_i[p + 3] = a.w;
-        s_q[p] = b.x; s_q[p + 1] = b.y; s_q[p + 2] = b.z; s_q[p + 3] = b.w;
-    }
-}
 
 // the sum of z over the 32 staged samples from offset o0 (sample o sits at o + (o >> 5)), whose first phase index is theta and
 // whose step is K: sequential from +0
@@ -165,8 +143,8 @@ __device__ __forceinline__ float search(const float *__restrict__ pi, const floa
     float P = 0.0f;
     for (int m = 0; m < FT8GPU_NN; ++m) {
         [[maybe_unused]] const uint32_t tone8 = 8u * (uint32_t)L.tone[m];
-        if (kTime) stage_span<24>(pi, pq, S0 - kSeg + 512 * m, L.plane[0], L.plane[1], lane);
-        else stage_span<16>(pi, pq, S0 + 512 * m, L.plane[0], L.plane[1], lane);
+        if (kTime) stage_span<kTimeSpanSegs>(pi, pq, S0 - kSeg + 512 * m, L.plane[0], L.plane[1], lane);
+        else stage_span<kFreqSpanSegs>(pi, pq, S0 + 512 * m, L.plane[0], L.plane[1], lane);
         wave_lds_sync();
 #pragma unroll
         for (int round = 0; round < (kTime ? 1 : 2); ++round) {
@@ -299,7 +277,7 @@ __device__ __forceinline__ void estimate_body(const float *__restrict__ iq, cons
     // ---- (d) the amplitude: G(q) two symbols at a time, A(q) behind it by eight segments ---------------------------------------
     float2 *A = reinterpret_cast<float2 *>(out);
     for (int c = 0; c < (kSubSegs + 31) / 32; ++c) {
-        stage_span<32>(pi, pq, S + 1024 * c, L.plane[0], L.plane[1], lane);
+        stage_span<kAmpSpanSegs>(pi, pq, S + 1024 * c, L.plane[0], L.plane[1], lane);
         wave_lds_sync();
         const int m = 2 * c + (lane >> 4), seg = lane & 15;
         if (lane < 32 && m < FT8GPU_NN) {

@@ -16,6 +16,7 @@
 //                    wave per frame with the heap in LDS, so that candidate order is bit-identical
 //                    to ft8_find_sync().
 #include "ft8gpu_internal.h"
+#include "wave_dev.h"
 #include <stdlib.h>
 
 namespace {
@@ -277,11 +278,6 @@ void ft8_sync_kernel(const uint8_t *__restrict__ mag, uint32_t *__restrict__ lis
 // by lane 0 through the reference's insertion / eviction / heapify rules.  The final heap sort is
 // replayed the same way, so ties come out in exactly the reference's order.
 __device__ __forceinline__ int sc(uint64_t e) { return (int)(int16_t)(e & 0xFFFFu); }
-__device__ __forceinline__ void wave_lds_sync_heap() {
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-}
 
 __device__ __forceinline__ void heapify_down(uint64_t *heap, int heap_size) {
     int current = 0;
@@ -438,7 +434,7 @@ __device__ __forceinline__ void heap_select_regs(const uint32_t *__restrict__ fr
         hk_sift_down(h, len_unsorted, tmp);
     }
     if (lane == 0) *count_out = heap_size;
-    wave_lds_sync_heap();
+    wave_lds_sync();
     // node j sits in lane j >> 1: lane l stores nodes 2l and 2l + 1 (8-byte stores, pairs adjacent)
     if (2 * lane < max_candidates) out[2 * lane] = 2 * lane < heap_size ? ent[h.kE & 0xFFFFu] : 0ull;            // deterministic tail
     if (2 * lane + 1 < max_candidates) out[2 * lane + 1] = 2 * lane + 1 < heap_size ? ent[h.kO & 0xFFFFu] : 0ull;

@@ -1,6 +1,7 @@
 // tone_dev.h -- the tones of a decoded message, re-encoded from its a91 (ft8_encode of ft8_lib encode.c: encode174, the Gray map,
 // the Costas arrays), for the kernels that rebuild a record's signal: the mask of multipass.hip, refine.hip, subtract.hip.
-// (ft8_messages_kernel and the append kernel's copy of it encode a whole codeword at once, in their own form.)
+// The record loop of record_dev.h (ft8_messages_kernel, ft8_append_kernel) encodes a whole codeword at once, in its own form,
+// with the Gray and Costas constants defined here.
 #pragma once
 #include "ft8gpu_internal.h"
 

@@ -23,6 +23,7 @@
 //     -ffp-contract=off so every float operation is a single IEEE operation.
 #include "ft8gpu_internal.h"
 #include "quant_math.h"
+#include "wave_dev.h"
 #include <stdlib.h>
 
 namespace {
@@ -67,12 +68,6 @@ __device__ __forceinline__ void bfly4(c32 &a0, c32 &a1, c32 &a2, c32 &a3) {
     a2 = t0 - t2;
     a1 = add_mul_mi(t1, t3);
     a3 = add_mul_pi(t1, t3);
-}
-
-__device__ __forceinline__ void wave_lds_sync() {
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
 }
 
 // rtlsdr_ft8d.c:1415-1427 for two bins (y0 and y1 of a stage-4 butterfly): |a|^2, |b|^2, then quant_math.h's pair

@@ -20,6 +20,7 @@
 // float planes, a thread runs its 95 taps in ascending order (the taps are uniform: scalar loads), rotates by j^p and stores.
 // -ffp-contract=off keeps every product and add a single IEEE operation.
 #include "wide.h"
+#include "merge_dev.h"
 
 namespace {
 
@@ -180,39 +181,14 @@ void ft8_wide_normalise_kernel(float *__restrict__ iq) {
     }
 }
 
-// One thread per capture: a record is 16 dwords; a91 = dwords 12 .. 14, freq_hz = dword 7, cand.freq_offset / freq_sub = the low
-// half / the top byte of dword 11, pad[0] = the low byte of dword 15 (as in audio.hip).  A record already kept names its channel
-// in pad[0].
+// One thread per capture: merge_dev.h's merge over the capture's channels; channels may lie anywhere in the capture, so equal
+// a91 is a duplicate only between channels near enough to overlap
 __global__ __launch_bounds__(64)
 void ft8_wide_merge_kernel(const ft8gpu_message *__restrict__ chan_msgs, const int32_t *__restrict__ chan_n, int ncaptures,
                            WideChannels ch, ft8gpu_message *msgs, int32_t *__restrict__ n_msgs) {
     const int c = blockIdx.x * 64 + threadIdx.x;
     if (c >= ncaptures) return;
-    const int cap = kMaxMessages * ch.n;
-    uint32_t *dst = (uint32_t *)(msgs + (size_t)c * cap);
-    int kept = 0;
-    for (int b = 0; b < ch.n; ++b) {
-        int n = chan_n[c * ch.n + b];
-        n = n < 0 ? 0 : n > kMaxMessages ? kMaxMessages : n;
-        const uint32_t *src = (const uint32_t *)(chan_msgs + ((size_t)c * ch.n + b) * kMaxMessages);
-        for (int k = 0; k < n && kept < cap; ++k) {
-            const uint32_t *r = src + 16 * k;
-            bool dup = false;
-            for (int i = 0; i < kept && !dup; ++i) {
-                const int apart = ch.bin[b] - ch.bin[dst[16 * i + 15] & 0xffu];
-                dup = dst[16 * i + 12] == r[12] && dst[16 * i + 13] == r[13] && dst[16 * i + 14] == r[14] && apart > -256 && apart < 256;
-            }
-            if (dup) continue;
-            uint32_t *d = dst + 16 * kept;
-            for (int i = 0; i < 16; ++i) d[i] = r[i];
-            const int fo = (int16_t)(r[11] & 0xffffu);
-            const int fs = (int)(r[11] >> 24);
-            d[7] = __float_as_uint(((float)(fo + ch.bin[b]) + (float)fs / 2) * 6.25f);
-            d[15] = (r[15] & 0xffffff00u) | (uint32_t)b;
-            ++kept;
-        }
-    }
-    n_msgs[c] = kept;
+    merge_parts<true>(chan_msgs, chan_n, c, ch.n, ch.bin, msgs, n_msgs);
 }
 
 int last_m(size_t npairs) { return (int)((npairs - 1 + 248) / kR1); }

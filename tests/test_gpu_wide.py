@@ -194,11 +194,12 @@ def test_full_length_capture(dec4):
 CHANNELS = (48000, 48240, -66000, -65760)
 # text, dial (freq_bin), Hz above the dial, start (s), the channel that reports it
 PLANTED = (("CQ K1ABC FN42", 48000, 500.0, 0.5, 0), ("CQ DL1XYZ JO62", 48000, 2400.0, 0.8, 1),
-           ("CQ JA1AAA PM95", -66000, 1531.25, 0.3, 2), ("CQ VK2BBB QF56", -66000, 700.0, 1.0, 2))
+           ("CQ JA1AAA PM95", -66000, 1531.25, 0.3, 2), ("CQ VK2BBB QF56", -66000, 700.0, 1.0, 2),
+           ("CQ K1ABC FN42", -66000, 1100.0, 0.6, 2))                      # channel 0's text again, 114 000 bins from it
 
 
 def device_capture(oracle):
-    """one full-length capture built on the device in float64 from the tone sequences: four CPFSK signals at amplitude 20 over
+    """one full-length capture built on the device in float64 from the tone sequences: five CPFSK signals at amplitude 20 over
     noise of sigma 30, rounded to bytes -> uint8 tensor [2 * 36 000 000]"""
     import torch
     n = sw.MAX_PAIRS
@@ -238,10 +239,13 @@ def test_whole_path_is_decode_messages_and_the_merge(ft8, dec4, oracle):
     recs = got_m[0, :int(got_n[0])]
     texts = [wc.text_of(r) for r in recs]
     print(texts, [float(r["freq_hz"]) for r in recs], [int(r["pad"][0]) for r in recs], bn.tolist())
-    assert sorted(texts) == sorted(t for t, _, _, _, _ in PLANTED)         # each exactly once: JA1AAA lies in channels 2 and 3
+    # each planted signal exactly once: JA1AAA lies in channels 2 and 3 and is dropped from 3; K1ABC was sent in channels 0 and 2,
+    # which are more than 256 bins apart, and is kept from both, each record with its own frequency and channel
+    assert sorted(texts) == sorted(t for t, _, _, _, _ in PLANTED)
     for text, dial, f0, _, chan in PLANTED:
-        r = recs[texts.index(text)]
-        assert abs(float(r["freq_hz"]) - (6.25 * dial + f0)) <= 3.125 and r["pad"][0] == chan
+        mine = [r for r, t in zip(recs, texts) if t == text and r["pad"][0] == chan]
+        assert len(mine) == 1, (text, chan)
+        assert abs(float(mine[0]["freq_hz"]) - (6.25 * dial + f0)) <= 3.125
     assert bn[0, 3] >= 1 and any(wc.text_of(r) == "CQ JA1AAA PM95" for r in bm[0, 3, :bn[0, 3]])   # heard there too, and dropped
     assert got_n[1] == 0
 

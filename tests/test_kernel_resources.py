@@ -32,6 +32,27 @@ def test_no_kernel_uses_scratch_and_no_dpp_follows_a_cmpx(tmp_path):
     assert ks["ft8_waterfall_kernel<0>"]["vgprs"] <= 120 and ks["ft8_waterfall_kernel<0>"]["waves_per_simd_by_vgprs"] == 4
 
 
+def test_the_two_record_kernels_keep_their_lds_and_their_waves():
+    """ft8_messages_kernel and ft8_append_kernel are two instances of one loop (csrc/record_dev.h).  Before the loop was
+    shared, each copy compiled to 144 VGPRs, 106 SGPRs, 13 680 bytes of LDS and no scratch: three waves per SIMD by this
+    tool's count.  As instances they take 161 VGPRs; what must hold is no scratch, the same LDS (four waves' dedup tables)
+    and no fewer than those three waves."""
+    sys.path.insert(0, os.path.join(ROOT, "tools"))
+    import kernel_resources as K
+    seen = {}
+    for src in ("messages.hip", "multipass.hip"):
+        ks = K.kernels_of(K.assemble(os.path.join(K.CSRC, src)))
+        for k, nice in zip(ks, K.demangle([k["symbol"] for k in ks])):
+            seen[nice] = k
+    for name in ("ft8_messages_kernel", "ft8_append_kernel"):
+        assert name in seen, (name, sorted(seen))
+        k = seen[name]
+        print(name, k)
+        assert k["scratch_bytes_per_lane"] == 0
+        assert k["lds_bytes"] == 13680
+        assert K.waves_per_simd(k) >= 3
+
+
 def test_committed_counter_evidence_describes_these_kernel_sources():
     """profiles/pmc_traffic.json carries the hash of csrc/ it was collected on; bench.py reports the counter-derived roofline
     figures (traffic, valu_*) only while that hash matches the tree.  A mismatch is not an error of the code -- it means
