@@ -40,7 +40,7 @@ namespace {
 // that are tested on the scalar unit against the ballot words; only a word that passes all of them
 // (every codeword does; a non-codeword with e failed rows does so with probability ~2^-(groups-1)
 // when e is even and never when e is odd) goes through the exact per-row check on the vector unit.
-// The number of masks is a template parameter of the kernel: 3 keeps the kernel at 78 SGPRs, and 256-thread
+// The number of masks is a template parameter of the kernel: 3 keeps the kernel at 80 SGPRs, and 256-thread
 // workgroups are admitted 8 per CU only up to 80 (MI355X_MICROARCH.md, residency); 4 masks (84 SGPRs, 7
 // workgroups per CU) screen twice as well but hold one wave per SIMD less.  Measured in one session: 5.000 ms
 // against 5.002 ms per 4096-frame batch -- the kernel is bound by VALU issue either way; 3 is kept.
@@ -221,12 +221,151 @@ void ft8_decode_kernel(const uint8_t *__restrict__ mag, const ft8gpu_candidate *
     uint64_t B0 = 0, B1 = 0, B2 = 0;
     int iter = 0;
     bool fast_ok = !force_ieee_div;     // every state value is 0 or >= 2^-59 (true for the initial zeros)
-    // the nine row products of the previous iteration, in the pairing of the states they turn into
-    f2 PA[3] = { { 0.0f, 0.0f }, { 0.0f, 0.0f }, { 0.0f, 0.0f } }, PB = { 0.0f, 0.0f };
-    float pc = 0.0f;
+    // the nine row products of the previous iteration, in the pairing of the states they turn into (first written by
+    // iteration 0 below)
+    f2 PA[3], PB;
+    float pc;
+
+    // What every iteration does with its hard decision B0..B2 (all scalar but the exact check): the all-zero exit,
+    // ldpc_check, the exit at the iteration cap.  Returns true when decoding ends here.
+    auto word_checks = [&]() -> bool {
+        if ((B0 | B1 | B2) == 0ull) return true;        // all-zero word is prohibited
+
+        // ldpc_check
+        bool full_check = true;
+        if (!COUNT_ERRORS) {
+            uint32_t odd = 0;
+#pragma unroll
+            for (int g = 0; g < kCheckGroups; ++g)
+                odd |= (uint32_t)__popcll((B0 & gmask[g][0]) ^ (B1 & gmask[g][1]) ^ (B2 & gmask[g][2]));
+            full_check = (odd & 1u) == 0;               // wave-uniform (ballot words and masks are scalars)
+        }
+        if (full_check) {
+            int errors = 0;
+#pragma unroll
+            for (int rr = 0; rr < 2; ++rr) {
+                const uint64_t m0 = COUNT_ERRORS ? rmask[rr][0] : d_tab.rowmask[rr][lane][0];
+                const uint64_t m1 = COUNT_ERRORS ? rmask[rr][1] : d_tab.rowmask[rr][lane][1];
+                const uint64_t m2 = COUNT_ERRORS ? rmask[rr][2] : d_tab.rowmask[rr][lane][2];
+                const int par = (__popcll(B0 & m0) + __popcll(B1 & m1) + __popcll(B2 & m2)) & 1;
+                errors += __popcll(__ballot(rvalid[rr] && par));
+            }
+            if (COUNT_ERRORS) {
+                if (errors < min_errors) {
+                    min_errors = errors;
+                    if (errors == 0) return true;
+                }
+            } else if (errors == 0) {
+                min_errors = 0;
+                return true;
+            }
+        }
+        // The reference's last iteration still updates both message arrays, which nothing reads afterwards:
+        // the last hard decision has been taken and checked at this point.
+        if (iter + 1 >= max_iters) { iter = max_iters; return true; }
+        return false;
+    };
+
+    // The check-row half of an iteration: every row's ordered products, then the lane's nine come back into PA / PB / pc.
+    auto check_rows = [&]() {
+        wave_lds_sync();
+
+        // ---- check rows: ordered products that skip one member, for all members ---------------
+        // o_k = product of the row's other members in row order: the prefixes p_k = v0 * ... * v(k-1) are shared, every
+        // o_k then continues its own chain (a shared suffix would change the association, i.e. the roundings).  Chains of
+        // equal length run as packed pairs: (o0, o1), (o2, o3) from (p2 * v3, p3), (o4, o5).
+        if (has6) {                                                           // 59 lanes (EXEC mask)
+            const float4 lo = planeLO[row6], hi = planeHI[row6];
+            const float v0 = lo.x, v1 = lo.y, v2 = lo.z, v3 = lo.w, v4 = hi.x, v5 = hi.y;
+            const f2 o01 = (mul_bcast_hi(f2{ v1, v0 } * v2, f2{ lo.z, lo.w }) * v4) * v5;   // skip 0 | skip 1: ((. * v2) * v3) ...
+            const float p2 = v0 * v1;
+            const float p3 = p2 * v2;
+            const float p4 = p3 * v3;
+            const f2 o23 = (f2{ p2 * v3, p3 } * v4) * v5;                     // skip 2 | skip 3
+            const float o4 = p4 * v5, o5 = p4 * v4;
+            planeLO[row6] = make_float4(o01.x, o01.y, o23.x, o23.y);
+            *reinterpret_cast<float2 *>(planeHI + row6) = make_float2(o4, o5);
+        }
+        if (has7) {                                                           // 24 lanes
+            const float4 lo = planeLO[row7], hi = planeHI[row7];
+            const float v0 = lo.x, v1 = lo.y, v2 = lo.z, v3 = lo.w, v4 = hi.x, v5 = hi.y, v6 = hi.z;
+            const f2 h23 = { hi.z, hi.w };                                    // (v6, 1.0f)
+            const f2 o01 = mul_bcast_lo((mul_bcast_hi(f2{ v1, v0 } * v2, f2{ lo.z, lo.w }) * v4) * v5, h23);
+            const float p2 = v0 * v1;
+            const float p3 = p2 * v2;
+            const float p4 = p3 * v3;
+            const f2 p45 = f2{ v5, v4 } * p4;                                 // (p4 * v5, p5)
+            const float p5 = p45.y;
+            const f2 o23 = mul_bcast_lo((f2{ p2 * v3, p3 } * v4) * v5, h23);
+            const f2 o45 = mul_bcast_lo(p45, h23);                           // skip 4 | skip 5
+            const float o6 = p5 * v5;
+            planeLO[row7] = make_float4(o01.x, o01.y, o23.x, o23.y);
+            planeHI[row7] = make_float4(o45.x, o45.y, o6, 1.0f);
+        }
+        wave_lds_sync();
+
+        // ---- the lane's nine products come back; they become messages at the top of the next iteration -------
+        // (lanes without a third variable read the spare row's 1.0f: see its initialisation)
+#pragma unroll
+        for (int r = 0; r < 2; ++r) PA[r] = f2{ toc[slot[3 * r + 2]], toc[slot[3 * r + 1]] };
+        PB = f2{ toc[slot[0]], toc[slot[3]] };
+        PA[2] = f2{ toc[slot[8]], toc[slot[7]] };
+        pc = toc[slot[6]];
+    };
+
+    // ---- iteration 0, on its own in front of the loop -----------------------------------------------------------------
+    // No check has sent a message yet: the states A, B, c2 of the loop are all +0 (tov = -2 * 0 = -0), so the three
+    // edges of a variable carry ONE value, and fast_tanh is evaluated on three values per lane where an iteration of
+    // the loop evaluates nine.  Every operation below is one the loop's form performs on these operands:
+    //   * half domain: x = (cwh + 0) + 0 on every edge.  The second sum changes nothing any more, but the first one is
+    //     not dropped: an LLR of +0 gives cwh = -0, and -0 + 0 is +0.  The hard decision (x + 0) < 0 is x < 0;
+    //   * the reference's own domain: u = cw + -0 = cw, bit = ((cw + -0) + -0) > 0 = cw > 0, and every edge carries
+    //     ((cw + -0) + -0) * -0.5 = cw * -0.5 = cwh, the sign of a zero included.
+    // It ends like an iteration of the loop, guard excepted: its products satisfy the guard by construction (proof at
+    // guard_key), so fast_ok stays what it is.
+    bool done;
+    {
+        float x0[3];
+        if (fast_ok) {                                   // wave-uniform
+#pragma unroll
+            for (int r = 0; r < 3; ++r) x0[r] = cwh[r] + 0.0f;
+            B0 = __ballot(x0[0] < 0.0f);
+            B1 = __ballot(x0[1] < 0.0f);
+            B2 = __ballot(x0[2] < 0.0f) & has2_mask;
+        } else {
+#pragma unroll
+            for (int r = 0; r < 3; ++r) x0[r] = cwh[r];
+            B0 = __ballot(has[0] && cw[0] > 0.0f);
+            B1 = __ballot(has[1] && cw[1] > 0.0f);
+            B2 = __ballot(has[2] && cw[2] > 0.0f);
+        }
+        done = word_checks();
+        if (!done) {                                     // wave-uniform
+            f2 t01;
+            float t2 = any_f32();
+            if (fast_ok) {
+                t01 = tanh_pair<true>(f2{ x0[0], x0[1] });
+                if (has[2]) t2 = tanh_one<true>(x0[2]);
+            } else {
+                t01 = tanh_pair<false>(f2{ x0[0], x0[1] });
+                if (has[2]) t2 = tanh_one<false>(x0[2]);
+            }
+#pragma unroll
+            for (int e = 0; e < 3; ++e) {
+                toc[slot[e]] = t01.x;
+                toc[slot[3 + e]] = t01.y;
+            }
+            if (has[2]) {
+#pragma unroll
+                for (int e = 0; e < 3; ++e) toc[slot[6 + e]] = t2;
+            }
+            check_rows();
+            iter = 1;
+        }
+    }
     const float m735 = bpm::vgpr_m735();      // fast_atanh's -735.0f, in a vector register for the whole loop (bp_math.h)
 
-    // One iteration up to the stores of toc, in the arithmetic form FAST selects (packed rcp/fma division and
+    // One iteration of the loop (iterations 1 ...) up to the stores of toc, in the arithmetic form FAST selects (packed rcp/fma division and
     // half-domain sums, or IEEE division and the reference's own domain).  The two forms are complete,
     // separate instruction streams behind ONE wave-uniform branch per iteration: when they were chosen phase by
     // phase, the values live across the three branch points cost 14 VGPRs and a wave of occupancy.
@@ -234,11 +373,11 @@ void ft8_decode_kernel(const uint8_t *__restrict__ mag, const ft8gpu_candidate *
     auto first_half = [&](auto fast_tag) -> bool {
         constexpr bool FAST = decltype(fast_tag)::value;
         // ---- checks -> bits: tov[n][m_idx] = -2 * fast_atanh(product of the other toc of the row); the state
-        // kept is fast_atanh(...) itself, i.e. tov = -2 * state exactly (half domain).  No messages before
-        // the first iteration.
+        // kept is fast_atanh(...) itself, i.e. tov = -2 * state exactly (half domain).  (Iteration 0, which has no
+        // messages to turn into states, is the block above.)
         f2 A[3], B;
         float c2;
-        if (iter > 0) {                                  // wave-uniform
+        {
 #pragma unroll
             for (int r = 0; r < 2; ++r) A[r] = atanh_pair<FAST>(PA[r], m735);
             B = atanh_pair<FAST>(PB, m735);
@@ -255,11 +394,6 @@ void ft8_decode_kernel(const uint8_t *__restrict__ mag, const ft8gpu_candidate *
                 A[2] = atanh_pair<FAST>(PA[2], m735);
                 c2 = atanh_one<FAST>(pc);
             }
-        } else {
-#pragma unroll
-            for (int r = 0; r < 3; ++r) A[r] = f2{ 0.0f, 0.0f };
-            B = f2{ 0.0f, 0.0f };
-            c2 = 0.0f;
         }
         // ---- hard decision and Tnm / x for the lane's nine edges
         // (lanes without a third variable compute on unspecified register content; nothing of it is stored)
@@ -298,40 +432,7 @@ void ft8_decode_kernel(const uint8_t *__restrict__ mag, const ft8gpu_candidate *
             B1 = __ballot(bit[1]);
             B2 = __ballot(bit[2]);
         }
-        if ((B0 | B1 | B2) == 0ull) return true;        // all-zero word is prohibited
-
-        // ldpc_check
-        bool full_check = true;
-        if (!COUNT_ERRORS) {
-            uint32_t odd = 0;
-#pragma unroll
-            for (int g = 0; g < kCheckGroups; ++g)
-                odd |= (uint32_t)__popcll((B0 & gmask[g][0]) ^ (B1 & gmask[g][1]) ^ (B2 & gmask[g][2]));
-            full_check = (odd & 1u) == 0;               // wave-uniform (ballot words and masks are scalars)
-        }
-        if (full_check) {
-            int errors = 0;
-#pragma unroll
-            for (int rr = 0; rr < 2; ++rr) {
-                const uint64_t m0 = COUNT_ERRORS ? rmask[rr][0] : d_tab.rowmask[rr][lane][0];
-                const uint64_t m1 = COUNT_ERRORS ? rmask[rr][1] : d_tab.rowmask[rr][lane][1];
-                const uint64_t m2 = COUNT_ERRORS ? rmask[rr][2] : d_tab.rowmask[rr][lane][2];
-                const int par = (__popcll(B0 & m0) + __popcll(B1 & m1) + __popcll(B2 & m2)) & 1;
-                errors += __popcll(__ballot(rvalid[rr] && par));
-            }
-            if (COUNT_ERRORS) {
-                if (errors < min_errors) {
-                    min_errors = errors;
-                    if (errors == 0) return true;
-                }
-            } else if (errors == 0) {
-                min_errors = 0;
-                return true;
-            }
-        }
-        // The reference's last iteration still updates both message arrays, which nothing reads afterwards:
-        // the last hard decision has been taken and checked at this point.
-        if (iter + 1 >= max_iters) { iter = max_iters; return true; }
+        if (word_checks()) return true;
 
         // ---- bits -> checks: toc[m][n_idx] = fast_tanh(-Tnm / 2)
         f2 t[4];
@@ -355,72 +456,28 @@ void ft8_decode_kernel(const uint8_t *__restrict__ mag, const ft8gpu_candidate *
         return false;
     };
 
-    for (;; ++iter) {
-        if (iter >= max_iters) break;                    // (max_iters >= 1 is checked by the API; the loop leaves through first_half)
+    if (!done) for (;; ++iter) {                         // iterations 1 ...
+        if (iter >= max_iters) break;                    // (never taken: word_checks ends the last iteration; kept for the loop's shape)
         const bool stop = fast_ok ? first_half(std::true_type{}) : first_half(std::false_type{});
         if (stop) break;
-        wave_lds_sync();
-
-        // ---- check rows: ordered products that skip one member, for all members ---------------
-        // o_k = product of the row's other members in row order: the prefixes p_k = v0 * ... * v(k-1) are shared, every
-        // o_k then continues its own chain (a shared suffix would change the association, i.e. the roundings).  Chains of
-        // equal length run as packed pairs: (o0, o1), (o2, o3) from (p2 * v3, p3), (o4, o5).
-        if (has6) {                                                           // 59 lanes (EXEC mask)
-            const float4 lo = planeLO[row6], hi = planeHI[row6];
-            const float v0 = lo.x, v1 = lo.y, v2 = lo.z, v3 = lo.w, v4 = hi.x, v5 = hi.y;
-            const f2 o01 = (mul_bcast_hi(f2{ v1, v0 } * v2, f2{ lo.z, lo.w }) * v4) * v5;   // skip 0 | skip 1: ((. * v2) * v3) ...
-            const float p2 = v0 * v1;
-            const float p3 = p2 * v2;
-            const float p4 = p3 * v3;
-            const f2 o23 = (f2{ p2 * v3, p3 } * v4) * v5;                     // skip 2 | skip 3
-            const float o4 = p4 * v5, o5 = p4 * v4;
-            planeLO[row6] = make_float4(o01.x, o01.y, o23.x, o23.y);
-            *reinterpret_cast<float2 *>(planeHI + row6) = make_float2(o4, o5);
-        }
-        if (has7) {                                                           // 24 lanes
-            const float4 lo = planeLO[row7], hi = planeHI[row7];
-            const float v0 = lo.x, v1 = lo.y, v2 = lo.z, v3 = lo.w, v4 = hi.x, v5 = hi.y, v6 = hi.z;
-            const f2 h23 = { hi.z, hi.w };                                    // (v6, 1.0f)
-            const f2 o01 = mul_bcast_lo((mul_bcast_hi(f2{ v1, v0 } * v2, f2{ lo.z, lo.w }) * v4) * v5, h23);
-            const float p2 = v0 * v1;
-            const float p3 = p2 * v2;
-            const float p4 = p3 * v3;
-            const f2 p45 = f2{ v5, v4 } * p4;                                 // (p4 * v5, p5)
-            const float p5 = p45.y;
-            const f2 o23 = mul_bcast_lo((f2{ p2 * v3, p3 } * v4) * v5, h23);
-            const f2 o45 = mul_bcast_lo(p45, h23);                           // skip 4 | skip 5
-            const float o6 = p5 * v5;
-            planeLO[row7] = make_float4(o01.x, o01.y, o23.x, o23.y);
-            planeHI[row7] = make_float4(o45.x, o45.y, o6, 1.0f);
-        }
-        wave_lds_sync();
-
-        // ---- the lane's nine products come back; they become messages at the top of the next iteration -------
-#pragma unroll
-        for (int r = 0; r < 2; ++r) PA[r] = f2{ toc[slot[3 * r + 2]], toc[slot[3 * r + 1]] };
-        PB = f2{ toc[slot[0]], toc[slot[3]] };
-        PA[2] = f2{ toc[slot[8]], toc[slot[7]] };
-        pc = toc[slot[6]];
-        // Lanes without a third variable read the spare row's 1.0f here (see its initialisation), which cannot lower
-        // the minimum, so the guard needs no select for them.  Iteration 0 is not tested at all (proof at guard_key).
+        check_rows();
+        // Lanes without a third variable hold the spare row's 1.0f in PA[2] and pc (see its initialisation), which cannot
+        // lower the minimum, so the guard needs no select for them.
         // Quick form of the guard: the smallest magnitude of the nine products (four v_min3_f32 with |.|
         // modifiers; a NaN operand is skipped).  If it is at least 2^-59 there is neither a tiny value nor a
         // zero and the guard holds; otherwise (exact zeros are common in the first two iterations, rare
         // afterwards) the exact key test below decides.
-        bool guard_ok = true;                                         // iteration 0: by construction (see guard_key)
-        if (iter > 0) {                                               // wave-uniform
-            float mabs = min3_abs(pc, PA[2].x, PA[2].y);
-            mabs = min3_abs(mabs, PB.x, PB.y);
-            mabs = min3_abs(mabs, PA[0].x, PA[0].y);
-            mabs = min3_abs(mabs, PA[1].x, PA[1].y);
-            guard_ok = __all(mabs >= 0x1p-59f);
-            if (!guard_ok) {                                          // wave-uniform
-                uint32_t gmin = min(guard_key(pc), min(guard_key(PA[2].x), guard_key(PA[2].y)));
-                gmin = min(gmin, min(guard_key(PB.x), guard_key(PB.y)));
+        float mabs = min3_abs(pc, PA[2].x, PA[2].y);
+        mabs = min3_abs(mabs, PB.x, PB.y);
+        mabs = min3_abs(mabs, PA[0].x, PA[0].y);
+        mabs = min3_abs(mabs, PA[1].x, PA[1].y);
+        bool guard_ok = __all(mabs >= 0x1p-59f);
+        if (!guard_ok) {                                              // wave-uniform
+            uint32_t gmin = min(guard_key(pc), min(guard_key(PA[2].x), guard_key(PA[2].y)));
+            gmin = min(gmin, min(guard_key(PB.x), guard_key(PB.y)));
 #pragma unroll
-                for (int r = 0; r < 2; ++r) gmin = min(gmin, min(guard_key(PA[r].x), guard_key(PA[r].y)));
-                guard_ok = __all(gmin >= kGuardMin);
-            }
+            for (int r = 0; r < 2; ++r) gmin = min(gmin, min(guard_key(PA[r].x), guard_key(PA[r].y)));
+            guard_ok = __all(gmin >= kGuardMin);
         }
         fast_ok = guard_ok && !force_ieee_div;                        // wave-uniform; governs the whole next iteration
         // (the next iteration's toc stores hit only this lane's own slots; LDS is in order per wave)

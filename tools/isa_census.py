@@ -18,6 +18,8 @@ v_div_scale/v_div_fmas/v_div_fixup).  Blocks are attributed by that marker; bloc
 both (hard decision, parity screen, row products, guard).  The census of an iteration on the fast path is the sum of
 the shared blocks and the fast blocks that every iteration executes; rarely executed blocks (exact parity check,
 exact guard key, exits) are listed but left out of the per-iteration sum (flag `rare`, decided by name below).
+Iteration 0 stands in front of the loop (no messages yet: fast_tanh on three values per lane instead of nine); the key
+`iteration0_fast_tanh` lists the VALU instructions of its fast form's tanh blocks.
 The cycle model at the end turns the census into a predicted time per launch, to be compared with the measured one."""
 import argparse
 import json
@@ -194,6 +196,28 @@ def main():
                 opcodes[op] = opcodes.get(op, 0) + k
     costs = {"valu": 1.0, "valu_pk": args.pk_cost, "trans": args.trans_cost}
     slots = sum(per_iter[k] * c for k, c in costs.items())
+    # Iteration 0 stands in front of the loop (decode.hip: no messages yet, so fast_tanh runs on three values per lane, not
+    # nine).  It lies between the normalisation (the kernel's only v_sqrt_f32) and the loop header.  Its fast divisions are the
+    # blocks with v_rcp_f32 and no v_div_*; the compiler evaluates the pair's two polynomials once for both division forms in a
+    # block of their own, recognised by fast_tanh's constant 15.0f (0x41700000) in a scalar move.
+    after_norm = max((i for i, b in enumerate(blocks[:first_loop]) if any(op.startswith("v_sqrt_f32") for op in b[2])), default=-1) + 1
+    peel = {"fast_division_blocks": [], "polynomial_blocks": [], "valu": 0, "valu_pk": 0, "trans": 0, "valu_opcodes": {}}
+    is_ieee = lambda ops: any(op.startswith(("v_div_scale", "v_div_fmas", "v_div_fixup")) for op in ops)
+    has_rcp = lambda ops: any(op.startswith("v_rcp_f32") for op in ops)
+    last_fast = max((i for i in range(after_norm, first_loop) if has_rcp(blocks[i][2]) and not is_ieee(blocks[i][2])), default=after_norm - 1)
+    for lab, _, ops, text in blocks[after_norm:last_fast + 1]:      # (the loop's own preheader, behind the stores, uses the constant too)
+        ieee = is_ieee(ops)
+        rcp = has_rcp(ops)
+        poly = not ieee and not rcp and any(t.startswith("s_mov_b32") and t.endswith("0x41700000") for t in text)
+        if ieee or not (rcp or poly):
+            continue
+        peel["fast_division_blocks" if rcp else "polynomial_blocks"].append(lab)
+        for op in ops:
+            k = classify(op)
+            if k in costs:
+                peel[k] += 1
+                peel["valu_opcodes"][op] = peel["valu_opcodes"].get(op, 0) + 1
+    peel["valu_issue_slots"] = round(sum(peel[k] * c for k, c in costs.items()), 1)
     out = {"kernel": args.kernel, "loop_header": loop, "blocks": rows,
            "fast_stream": fast, "ieee_stream": total(("ieee", "ieee*")), "common_blocks": common, "rarely_executed_on_the_fast_path": rare,
            "per_iteration_fast_path": per_iter,
@@ -202,6 +226,7 @@ def main():
            "epilogue_all_paths_static": epilogue_all,
            "prologue_valu_issue_slots": round(prologue.get("valu", 0) + args.pk_cost * prologue.get("valu_pk", 0) + args.trans_cost * prologue.get("trans", 0), 1),
            "valu_issue_slots_per_iteration": round(slots, 1),
+           "iteration0_fast_tanh": peel,
            "slot_costs": {"valu": 1.0, "valu_pk": args.pk_cost, "trans": round(args.trans_cost, 3),
                           "note": "one slot = one v_mul_f32 (wave64); SALU, LDS and waits issue from other ports; three-operand VOP3 "
                                   "forms (v_fma_f32 1.10, v_bfi_b32 1.45 on the box) are counted as 1"}}
