@@ -833,19 +833,25 @@ class Decoder:
                                                status.ctypes.data, B, msgs.ctypes.data, n.ctypes.data, HOST_PTRS))
         return msgs, n
 
-    def osd_candidates(self, mag, cands, counts, status_in, order=1, max_hard_errors=OSD_MAX_HARD_ERRORS, status_out=None, info=None):
-        """ft8gpu_osd_candidates -> (status_out [B][cap] STATUS_DTYPE, info [B][cap] OSD_INFO_DTYPE), new arrays; records at and
-        behind counts[f] keep what status_out / info held (zeros when None)"""
-        mag = np.ascontiguousarray(mag, np.uint8).reshape(-1, MAG_ARRAY)
-        B = mag.shape[0]
+    def _cand_arrays(self, B, cands, counts, status_in, status_out, info, info_dtype):
+        """the arrays every *_candidates method shares, shaped for B frames: cands, counts, status_in as bytes, and new
+        status_out (bytes) and info arrays that start from what the caller handed in (zeros when None)"""
         cands = np.ascontiguousarray(cands)
         counts = np.ascontiguousarray(counts, np.int32)
         status_in = np.ascontiguousarray(status_in).view(np.uint8).reshape(B, self.max_candidates, 48)
         assert cands.shape == (B, self.max_candidates) and cands.dtype == CAND_DTYPE and counts.shape == (B,)
         out = np.zeros((B, self.max_candidates, 48), np.uint8) if status_out is None else \
             np.array(status_out, copy=True, order="C").view(np.uint8).reshape(B, self.max_candidates, 48)
-        inf = np.zeros((B, self.max_candidates), OSD_INFO_DTYPE) if info is None else \
-            np.array(info, copy=True, order="C").view(OSD_INFO_DTYPE).reshape(B, self.max_candidates)
+        inf = np.zeros((B, self.max_candidates), info_dtype) if info is None else \
+            np.array(info, copy=True, order="C").view(info_dtype).reshape(B, self.max_candidates)
+        return cands, counts, status_in, out, inf
+
+    def osd_candidates(self, mag, cands, counts, status_in, order=1, max_hard_errors=OSD_MAX_HARD_ERRORS, status_out=None, info=None):
+        """ft8gpu_osd_candidates -> (status_out [B][cap] STATUS_DTYPE, info [B][cap] OSD_INFO_DTYPE), new arrays; records at and
+        behind counts[f] keep what status_out / info held (zeros when None)"""
+        mag = np.ascontiguousarray(mag, np.uint8).reshape(-1, MAG_ARRAY)
+        B = mag.shape[0]
+        cands, counts, status_in, out, inf = self._cand_arrays(B, cands, counts, status_in, status_out, info, OSD_INFO_DTYPE)
         self._ck(self.lib.ft8gpu_osd_candidates(self.h, mag.ctypes.data, cands.ctypes.data, counts.ctypes.data, status_in.ctypes.data,
                                               B, int(order), int(max_hard_errors), out.ctypes.data, inf.ctypes.data, HOST_PTRS))
         return out.view(STATUS_DTYPE).reshape(B, self.max_candidates), inf
@@ -872,14 +878,7 @@ class Decoder:
         behind counts[f] keep what status_out / info held (zeros when None).  hyps: patterns or AP_HYP_DTYPE records"""
         mag = np.ascontiguousarray(mag, np.uint8).reshape(-1, MAG_ARRAY)
         B = mag.shape[0]
-        cands = np.ascontiguousarray(cands)
-        counts = np.ascontiguousarray(counts, np.int32)
-        status_in = np.ascontiguousarray(status_in).view(np.uint8).reshape(B, self.max_candidates, 48)
-        assert cands.shape == (B, self.max_candidates) and cands.dtype == CAND_DTYPE and counts.shape == (B,)
-        out = np.zeros((B, self.max_candidates, 48), np.uint8) if status_out is None else \
-            np.array(status_out, copy=True, order="C").view(np.uint8).reshape(B, self.max_candidates, 48)
-        inf = np.zeros((B, self.max_candidates), AP_INFO_DTYPE) if info is None else \
-            np.array(info, copy=True, order="C").view(AP_INFO_DTYPE).reshape(B, self.max_candidates)
+        cands, counts, status_in, out, inf = self._cand_arrays(B, cands, counts, status_in, status_out, info, AP_INFO_DTYPE)
         hyps = _ap_hyps(hyps)
         self._ck(self.lib.ft8gpu_ap_candidates(self.h, mag.ctypes.data, cands.ctypes.data, counts.ctypes.data, status_in.ctypes.data,
                                                B, hyps.ctypes.data, len(hyps), int(max_hard_errors), out.ctypes.data, inf.ctypes.data,
@@ -965,16 +964,9 @@ class Decoder:
         what status_out / info held (zeros when None)"""
         mag = np.ascontiguousarray(mag, np.uint8).reshape(-1, MAG_ARRAY)
         B = mag.shape[0]
-        cands = np.ascontiguousarray(cands)
-        counts = np.ascontiguousarray(counts, np.int32)
-        status_in = np.ascontiguousarray(status_in).view(np.uint8).reshape(B, self.max_candidates, 48)
+        cands, counts, status_in, out, inf = self._cand_arrays(B, cands, counts, status_in, status_out, info, MATCH_INFO_DTYPE)
         states = np.ascontiguousarray(states)
-        assert cands.shape == (B, self.max_candidates) and cands.dtype == CAND_DTYPE and counts.shape == (B,)
         assert states.dtype == EXPECT_STATE_DTYPE and states.shape == (B,)
-        out = np.zeros((B, self.max_candidates, 48), np.uint8) if status_out is None else \
-            np.array(status_out, copy=True, order="C").view(np.uint8).reshape(B, self.max_candidates, 48)
-        inf = np.zeros((B, self.max_candidates), MATCH_INFO_DTYPE) if info is None else \
-            np.array(info, copy=True, order="C").view(MATCH_INFO_DTYPE).reshape(B, self.max_candidates)
         self._ck(self.lib.ft8gpu_match_candidates(self.h, mag.ctypes.data, cands.ctypes.data, counts.ctypes.data, status_in.ctypes.data,
                                                   B, states.ctypes.data, int(max_age), int(max_hard_errors), out.ctypes.data,
                                                   inf.ctypes.data, HOST_PTRS))
@@ -1040,16 +1032,9 @@ class Decoder:
         counts[f] keep what status_out / info held (zeros when None)"""
         mag = np.ascontiguousarray(mag, np.uint8).reshape(-1, MAG_ARRAY)
         B = mag.shape[0]
-        cands = np.ascontiguousarray(cands)
-        counts = np.ascontiguousarray(counts, np.int32)
-        status_in = np.ascontiguousarray(status_in).view(np.uint8).reshape(B, self.max_candidates, 48)
+        cands, counts, status_in, out, inf = self._cand_arrays(B, cands, counts, status_in, status_out, info, COMBINE_INFO_DTYPE)
         states = np.ascontiguousarray(states)
-        assert cands.shape == (B, self.max_candidates) and cands.dtype == CAND_DTYPE and counts.shape == (B,)
         assert states.dtype == SOFTMEM_STATE_DTYPE and states.shape == (B,)
-        out = np.zeros((B, self.max_candidates, 48), np.uint8) if status_out is None else \
-            np.array(status_out, copy=True, order="C").view(np.uint8).reshape(B, self.max_candidates, 48)
-        inf = np.zeros((B, self.max_candidates), COMBINE_INFO_DTYPE) if info is None else \
-            np.array(info, copy=True, order="C").view(COMBINE_INFO_DTYPE).reshape(B, self.max_candidates)
         self._ck(self.lib.ft8gpu_combine_candidates(self.h, mag.ctypes.data, cands.ctypes.data, counts.ctypes.data, status_in.ctypes.data,
                                                     B, states.ctypes.data, int(max_age), int(min_agree), out.ctypes.data,
                                                     inf.ctypes.data, HOST_PTRS))
@@ -1118,14 +1103,7 @@ class Decoder:
         and behind counts[f] keep what status_out / info held (zeros when None).  max_per_frame None: max_candidates"""
         iq = np.ascontiguousarray(iq, np.float32).reshape(-1, 2, NSAMPLES)
         B = iq.shape[0]
-        cands = np.ascontiguousarray(cands)
-        counts = np.ascontiguousarray(counts, np.int32)
-        status_in = np.ascontiguousarray(status_in).view(np.uint8).reshape(B, self.max_candidates, 48)
-        assert cands.shape == (B, self.max_candidates) and cands.dtype == CAND_DTYPE and counts.shape == (B,)
-        out = np.zeros((B, self.max_candidates, 48), np.uint8) if status_out is None else \
-            np.array(status_out, copy=True, order="C").view(np.uint8).reshape(B, self.max_candidates, 48)
-        inf = np.zeros((B, self.max_candidates), DEMOD_INFO_DTYPE) if info is None else \
-            np.array(info, copy=True, order="C").view(DEMOD_INFO_DTYPE).reshape(B, self.max_candidates)
+        cands, counts, status_in, out, inf = self._cand_arrays(B, cands, counts, status_in, status_out, info, DEMOD_INFO_DTYPE)
         p = DemodParams(int(sets), int(max_hard_errors), int(self.max_candidates if max_per_frame is None else max_per_frame))
         self._ck(self.lib.ft8gpu_demod_candidates(self.h, iq.ctypes.data, cands.ctypes.data, counts.ctypes.data, status_in.ctypes.data,
                                                   B, C.byref(p), out.ctypes.data, inf.ctypes.data, HOST_PTRS))

@@ -9,10 +9,12 @@
 //   disagrees with the hypothesis (8), all-zero (5), hard errors on the unmasked positions (2), CRC (3), unpack77 (4),
 //   accepted (1).  The first accepted hypothesis wins.
 //
-// One wave64 per candidate, four per workgroup, the launch geometry of the LDPC kernel (decode.hip).  The soft bits, the BP
-// iteration in its counting form with both division streams behind the per-iteration guard, the CRC by linearity and the
-// record composed in LDS are the shared device code of cand_dev.h.  What is this file's own: apmag by a wave maximum, the
-// hypothesis loop inside the wave (masks and bits arrive as kernel arguments: scalar registers), and the judgement.  The
+// One wave64 per candidate, four per workgroup, the launch geometry of the LDPC kernel (decode.hip).  The head of the kernel,
+// the soft bits, the BP iteration in its counting form with both division streams behind the per-iteration guard, the tail
+// of the judgement (all-zero, hard errors, the CRC by linearity, the record composed in LDS) and the kernel that tags the
+// message records are the shared device code of cand_dev.h.  What is this file's own: the block order, apmag by a wave
+// maximum, the hypothesis loop inside the wave (masks and bits arrive as kernel arguments: scalar registers), rules 7 and 8
+// and the hard errors on the unmasked positions.  The
 // guard's premise holds for the forced values too: apmag is one of the candidate's own magnitudes, so a halved LLR is
 // still 0 or >= 0.0095 (cand_dev.h, guard_key).
 #include "cand_dev.h"
@@ -40,32 +42,21 @@ void ft8_ap_kernel(const uint8_t *__restrict__ mag, const ft8gpu_candidate *__re
                    unsigned blocks_per_frame, unsigned bpf_magic) {
     __shared__ __attribute__((aligned(16))) float s_mem[4][kWaveLds];
 
-    const int lane = threadIdx.x & 63;
-    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    static_assert(sizeof(ft8gpu_ap_info) == 8, "record sizes");
+    static_assert(offsetof(ft8gpu_ap_info, nhard) == 1 && offsetof(ft8gpu_ap_info, hyp) == 2 && offsetof(ft8gpu_ap_info, iters) == 3 &&
+                  offsetof(ft8gpu_ap_info, results) == 4, "info layout");
     // the LDPC kernel's block order and frame / candidate split (decode.hip: XCD-aware renumbering; one multiply-high, and
     // no division at all for one block per frame, where the constant does not exist)
     const unsigned nb = gridDim.x, per = nb >> 3, main_blocks = per << 3;
     const unsigned vb = blockIdx.x < main_blocks ? (blockIdx.x & 7u) * per + (blockIdx.x >> 3) : blockIdx.x;
-    const int frame = blocks_per_frame == 1u ? (int)vb : (int)__umulhi(vb, bpf_magic);
-    const int ci = (int)(vb - (unsigned)frame * blocks_per_frame) * 4 + wave;
-    if (frame >= nframes || ci >= max_candidates) return;
-    if (ci >= counts[frame]) return;                                  // wave-uniform: records behind the count are not touched
+    const CandWave w = cand_prologue<true>(vb, blocks_per_frame, bpf_magic, counts, status_in, status_out, info, nframes, max_candidates);
+    if (w.verdict != kCandRun) return;
+    const int lane = w.lane, frame = w.frame;
+    const size_t rec_index = w.rec_index;
+    const uint32_t *in32 = w.in32, mine = w.mine, dw0 = w.dw0;
+    uint32_t *out32 = w.out32, *info32 = w.info32;
 
-    const size_t rec_index = (size_t)frame * max_candidates + ci;
-    const uint32_t *in32 = reinterpret_cast<const uint32_t *>(status_in + rec_index);
-    uint32_t *out32 = reinterpret_cast<uint32_t *>(status_out + rec_index);
-    uint32_t *info32 = reinterpret_cast<uint32_t *>(info + rec_index);
-    static_assert(sizeof(ft8gpu_decode_status) == 48 && sizeof(ft8gpu_ap_info) == 8, "record sizes");
-    static_assert(offsetof(ft8gpu_ap_info, nhard) == 1 && offsetof(ft8gpu_ap_info, hyp) == 2 && offsetof(ft8gpu_ap_info, iters) == 3 &&
-                  offsetof(ft8gpu_ap_info, results) == 4, "info layout");
-
-    uint32_t mine, dw0;
-    if (!read_record(in32, lane, mine, dw0)) {                        // does not qualify
-        leave_record(out32, in32, info32, mine, 0u, lane);
-        return;
-    }
-
-    float *toc = s_mem[wave];
+    float *toc = s_mem[w.wave];
     float *llr = toc + kTocFloats;
 
     float cw0[3];
@@ -109,9 +100,7 @@ void ft8_ap_kernel(const uint8_t *__restrict__ mag, const ft8gpu_candidate *__re
         nhard = __popcll((B0 ^ H0) & ~m0) + __popcll((B1 ^ H1) & ~m1) + __popcll(B2 ^ H2);
         if (bp.min_errors != 0) result = 7;
         else if ((((B0 ^ b0) & m0) | ((B1 ^ b1) & m1)) != 0ull) result = 8;
-        else if ((B0 | B1 | B2) == 0ull) result = 5;                      // (bp_decode leaves at an all-zero word before it checks it)
-        else if (nhard > max_hard_errors) result = 2;
-        else result = compose_success_record(B0, B1, dw0, d_ldpc.crc_bit, rec32, lane);
+        else result = judge_word(B0, B1, B2, nhard, max_hard_errors, dw0, d_ldpc.crc_bit, rec32, lane);
         results |= (uint32_t)result << (8 * k);
         if (result == 1) break;
     }
@@ -123,29 +112,10 @@ void ft8_ap_kernel(const uint8_t *__restrict__ mag, const ft8gpu_candidate *__re
     }
 }
 
-// pad[1] of the message records AP gained: 1 + the accepted hypothesis.  One wave per slot of the pass.
-__global__ __launch_bounds__(256)
-void ft8_ap_tag_kernel(const ft8gpu_ap_info *__restrict__ info, const int32_t *__restrict__ map,
-                       const int32_t *__restrict__ n_before, const int32_t *__restrict__ n_msgs, int nslots,
-                       int max_candidates, ft8gpu_message *__restrict__ msgs) {
-    const int slot = blockIdx.x * 4 + (threadIdx.x >> 6), r = threadIdx.x & 63;
-    if (slot >= nslots) return;
-    const int frame = map ? map[slot] : slot;
-    int lo = n_before[frame], hi = n_msgs[frame];
-    lo = lo < 0 ? 0 : lo;
-    hi = hi > kMaxMessages ? kMaxMessages : hi;
-    if (r < lo || r >= hi) return;
-    ft8gpu_message *m = msgs + (size_t)frame * kMaxMessages + r;
-    const int ci = m->cand_index;
-    if (ci < max_candidates) m->pad[1] = (uint8_t)(1 + info[(size_t)slot * max_candidates + ci].hyp);
-}
-
 }  // namespace
 
 hipError_t ap_tables_init(hipStream_t s) {
-    static LdpcTables h;
-    fill_ldpc_tables(h);
-    return hipMemcpyToSymbolAsync(HIP_SYMBOL(d_ldpc), &h, sizeof(h), 0, hipMemcpyHostToDevice, s);
+    return upload_ldpc_tables(HIP_SYMBOL(d_ldpc), s);
 }
 
 hipError_t launch_ap(const uint8_t *mag, const ft8gpu_candidate *cands, const int32_t *counts,
@@ -161,19 +131,16 @@ hipError_t launch_ap(const uint8_t *mag, const ft8gpu_candidate *cands, const in
             if ((hyps[k].mask[i >> 3] >> sh) & 1u) set.mask[k][i >> 6] |= 1ull << (i & 63);
             if ((hyps[k].bits[i >> 3] >> sh) & 1u) set.bits[k][i >> 6] |= 1ull << (i & 63);
         }
-    const unsigned bpf = (unsigned)(max_candidates + 3) / 4;                  // blocks (of 4 candidate waves) per frame
-    const unsigned long long nblocks = (unsigned long long)nframes * bpf;
-    if (nblocks * bpf >= (1ull << 32)) return hipErrorInvalidValue;           // keeps the multiply-high division exact
-    const unsigned magic = bpf == 1u ? 0u : (unsigned)((1ull << 32) / bpf) + 1u;
-    hipLaunchKernelGGL(ft8_ap_kernel, dim3((unsigned)nblocks), dim3(256), 0, s, mag, cands, counts, status_in, status_out, info,
-                       nframes, max_candidates, ldpc_iters, force_ieee_div, nhyp, max_hard_errors, set, bpf, magic);
+    CandGrid g;
+    if (cand_grid(nframes, max_candidates, g, true) != hipSuccess) return hipErrorInvalidValue;
+    const unsigned magic = g.bpf == 1u ? 0u : (unsigned)((1ull << 32) / g.bpf) + 1u;
+    hipLaunchKernelGGL(ft8_ap_kernel, dim3(g.nblocks), dim3(256), 0, s, mag, cands, counts, status_in, status_out, info,
+                       nframes, max_candidates, ldpc_iters, force_ieee_div, nhyp, max_hard_errors, set, g.bpf, magic);
     return hipGetLastError();
 }
 
 hipError_t launch_ap_tag(const ft8gpu_ap_info *info, const int32_t *map, const int32_t *n_before, const int32_t *n_msgs,
                          int nslots, int max_candidates, ft8gpu_message *msgs, hipStream_t s) {
-    if (nslots < 1) return hipSuccess;
-    hipLaunchKernelGGL(ft8_ap_tag_kernel, dim3((nslots + 3) / 4), dim3(256), 0, s, info, map, n_before, n_msgs, nslots,
-                       max_candidates, msgs);
-    return hipGetLastError();
+    // pad[1] of the message records AP gained: 1 + the accepted hypothesis
+    return launch_tag(map, n_before, 1, n_msgs, nslots, msgs, TagInfo<1, ft8gpu_ap_info, &ft8gpu_ap_info::hyp, 1>{ info, max_candidates }, s);
 }

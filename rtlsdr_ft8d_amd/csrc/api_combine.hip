@@ -62,17 +62,14 @@ int ft8gpu_combine_candidates(ft8gpu_ctx *c, const uint8_t *mag, const ft8gpu_ca
     if (ensure_scratch(c, 0, dev ? 0 : piece * kStateBytes, dev ? 0 : piece * mc * sizeof(ft8gpu_decode_status),
                           dev ? 0 : piece * mc * sizeof(ft8gpu_combine_info)))
         return -1;
-    // records at and behind a frame's count keep the caller's bytes (both outputs are uploaded in the host form)
-    const StageArg a[] = { { mag, c->d_mag, kMagArray, kIn }, { cands, c->d_cands, mc * sizeof(ft8gpu_candidate), kIn },
-                           { counts, c->d_counts, sizeof(int32_t), kIn },
-                           { status_in, c->d_status, mc * sizeof(ft8gpu_decode_status), kIn },
-                           { states, c->d_scratch[1], kStateBytes, kIn },
-                           { status_out, c->d_scratch[2], mc * sizeof(ft8gpu_decode_status), kInOut },
-                           { info, c->d_scratch[3], mc * sizeof(ft8gpu_combine_info), kInOut } };
+    StageArg a[kCandRows + 1];
+    cand_stage_rows(a, c, { mag, c->d_mag, kMagArray, kIn }, cands, counts, status_in, status_out, c->d_scratch[2], info, c->d_scratch[3],
+                    sizeof(ft8gpu_combine_info));
+    a[kCandRows] = { states, c->d_scratch[1], kStateBytes, kIn };
     return for_each_chunk(c, nframes, flags & FT8GPU_DEVICE_PTRS, a, [&](int n, void *const *p) {
         HIP_TRY(launch_combine((const uint8_t *)p[0], (const ft8gpu_candidate *)p[1], (const int32_t *)p[2],
-                               (const ft8gpu_decode_status *)p[3], (ft8gpu_decode_status *)p[5], (ft8gpu_combine_info *)p[6], n, mc,
-                               (const ft8gpu_softmem_state *)p[4], max_age, min_agree, c->params.ldpc_iters, force_ieee(c),
+                               (const ft8gpu_decode_status *)p[3], (ft8gpu_decode_status *)p[4], (ft8gpu_combine_info *)p[5], n, mc,
+                               (const ft8gpu_softmem_state *)p[kCandRows], max_age, min_agree, c->params.ldpc_iters, force_ieee(c),
                                c->stream));
         return 0;
     });

@@ -48,12 +48,9 @@ int ft8gpu_demod_candidates(ft8gpu_ctx *c, const float *iq, const ft8gpu_candida
     if (ensure_scratch(c, 0, 0, dev ? 0 : piece * mc * sizeof(ft8gpu_decode_status), dev ? 0 : piece * mc * sizeof(ft8gpu_demod_info)))
         return -1;
     const ft8gpu_demod_params p = *params;
-    // records at and behind a frame's count keep the caller's bytes (both outputs are uploaded in the host form)
-    const StageArg a[] = { { iq, c->d_iq, kFrameBytes, kIn }, { cands, c->d_cands, mc * sizeof(ft8gpu_candidate), kIn },
-                           { counts, c->d_counts, sizeof(int32_t), kIn },
-                           { status_in, c->d_status, mc * sizeof(ft8gpu_decode_status), kIn },
-                           { status_out, c->d_scratch[2], mc * sizeof(ft8gpu_decode_status), kInOut },
-                           { info, c->d_scratch[3], mc * sizeof(ft8gpu_demod_info), kInOut } };
+    StageArg a[kCandRows];
+    cand_stage_rows(a, c, { iq, c->d_iq, kFrameBytes, kIn }, cands, counts, status_in, status_out, c->d_scratch[2], info, c->d_scratch[3],
+                    sizeof(ft8gpu_demod_info));
     return for_each_chunk(c, nframes, flags & FT8GPU_DEVICE_PTRS, a, [&](int n, void *const *q) {
         HIP_TRY(launch_demod((const float *)q[0], (const ft8gpu_candidate *)q[1], (const int32_t *)q[2],
                              (const ft8gpu_decode_status *)q[3], (ft8gpu_decode_status *)q[4], (ft8gpu_demod_info *)q[5], n, mc,

@@ -47,12 +47,9 @@ int ft8gpu_osd_candidates(ft8gpu_ctx *c, const uint8_t *mag, const ft8gpu_candid
     if (!mag || !cands || !counts || !status_in || !status_out || !info) return ft8_fail("NULL array argument");
     if (ensure_osd_buffers(c)) return -1;
     const int mc = c->params.max_candidates;
-    // records at and behind a frame's count keep the caller's bytes (both outputs are uploaded in the host form)
-    const StageArg a[] = { { mag, c->d_mag, kMagArray, kIn }, { cands, c->d_cands, mc * sizeof(ft8gpu_candidate), kIn },
-                           { counts, c->d_counts, sizeof(int32_t), kIn },
-                           { status_in, c->d_status, mc * sizeof(ft8gpu_decode_status), kIn },
-                           { status_out, c->d_osd_out, mc * sizeof(ft8gpu_decode_status), kInOut },
-                           { info, c->d_osd_info, mc * sizeof(ft8gpu_osd_info), kInOut } };
+    StageArg a[kCandRows];
+    cand_stage_rows(a, c, { mag, c->d_mag, kMagArray, kIn }, cands, counts, status_in, status_out, c->d_osd_out, info, c->d_osd_info,
+                    sizeof(ft8gpu_osd_info));
     return for_each_chunk(c, nframes, flags & FT8GPU_DEVICE_PTRS, a, [&](int n, void *const *p) {
         HIP_TRY(launch_osd((const uint8_t *)p[0], (const ft8gpu_candidate *)p[1], (const int32_t *)p[2],
                            (const ft8gpu_decode_status *)p[3], (ft8gpu_decode_status *)p[4], (ft8gpu_osd_info *)p[5], n, mc, order,

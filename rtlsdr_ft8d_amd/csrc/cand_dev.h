@@ -1,9 +1,12 @@
 // cand_dev.h -- device code of the one-wave-per-candidate kernels, kept once: the LDPC kernel (decode.hip) and the kernels
-// that give its failures a second chance (osd.hip, ap.hip, match.hip, combine.hip).  Wave helpers, the soft bits of a
-// candidate, the BP iteration in its counting form, the record of a success, the way a wave leaves a candidate alone, and
-// the LDPC tables with their host-side builder.  decode.hip takes the helpers and the table builders from here and keeps
-// its own kernel body (it has forms of the iteration the counting form does not need: the scalar group test, registers with
-// unspecified content, broadcast multiplies); its comments explain the layout the counting form shares.
+// that give its failures a second chance (osd.hip, ap.hip, match.hip, combine.hip, demod.hip).  Wave helpers, the soft bits
+// of a candidate and their renormalisation in index order, the BP iteration in its counting form, the judgement and the
+// record of a success, and the LDPC tables with their host-side builder and upload.  For the five second-chance kernels also
+// what surrounds those: the head of the kernel (which candidate a wave has, and whether it is left alone), the launch
+// geometry, and the one kernel that tags the message records a stage gained.  decode.hip takes the helpers and the table
+// builders from here and keeps its own kernel body (it has forms of the iteration the counting form does not need: the
+// scalar group test, registers with unspecified content, broadcast multiplies); its comments explain the layout the
+// counting form shares.
 // Plain functions in the translation unit's anonymous namespace; a __device__ table is instantiated by the file that uses it.
 #pragma once
 #include "ft8gpu_internal.h"
@@ -165,6 +168,61 @@ __device__ __forceinline__ bool soft_bits(const uint8_t *__restrict__ mag, int f
     return __all(finite);
 }
 
+// ftx_normalize_logl on 174 soft bits of any origin (a sum across slots, magnitudes of correlations): llr[0 .. 173] in the
+// wave's LDS, stores published; lane l gets llr[l + 64 r] normalised into cw[r] (0 where !has[r]).  The normaliser
+// accumulates in index order as the reference does -- every lane reads the 174 values at one address and keeps the same
+// two accumulators, so no reduction order has to be argued about.  Returns whether every value is finite (wave-uniform);
+// if so, ieee is set where the division guard below fails.
+//
+// The division guard.  guard_key's comment proves that iteration 0 needs no guard because every soft bit there is k * f / 2
+// with an integer k and f >= 0.0192, and ap.hip relies on the same fact.  Renormalised values have no such structure: x[i] is
+// any finite float, 2^-90 or a subnormal next to values of ordinary size.  The soft bits enter the messages of EVERY iteration
+// (x = (cwh + ah_a) + ah_b), and the argument of guard_key -- a sum of floats that are each 0 or >= 2^-59 is 0 or
+// >= 2^-82, nothing is subnormal, halving commutes with every rounding -- needs cwh = -x / 2 in that set as well.  So the
+// guard is evaluated ahead of iteration 0 on the candidate's own 174 soft bits, with the same key test as on the row
+// products: every x[i] is 0 or |x[i]| >= 2^-58 (tested on x, not on the halved value, which may round a subnormal to zero).
+// Where it holds, iteration 0 runs the fast form (x = cwh is in fast_tanh's domain) and every later iteration is guarded on
+// its products (bp_decode_counting evaluates the guard after iteration 0 too); where it fails the whole candidate runs in
+// the IEEE form, iteration 0 included.  That is sufficient: with all soft bits in the set, the premise of the proof for
+// iteration k > 0 holds unchanged, and the IEEE form needs no premise.
+constexpr uint32_t kGuardMinSoft = ((127u - 58u) << 24) - 1u;   // guard_key(0x1p-58f): the soft bits, halved exactly to >= 2^-59
+__device__ __forceinline__ bool renormalise_in_order(const float *llr, const bool (&has)[3], int lane, float (&cw)[3], int &ieee) {
+    float sum = 0.0f, sum2 = 0.0f;
+    for (int i = 0; i < 172; i += 4) {
+        const float4 v = *reinterpret_cast<const float4 *>(llr + i);
+        sum = sum + v.x; sum2 = sum2 + v.x * v.x;
+        sum = sum + v.y; sum2 = sum2 + v.y * v.y;
+        sum = sum + v.z; sum2 = sum2 + v.z * v.z;
+        sum = sum + v.w; sum2 = sum2 + v.w * v.w;
+    }
+    {
+        const float2 v = *reinterpret_cast<const float2 *>(llr + 172);
+        sum = sum + v.x; sum2 = sum2 + v.x * v.x;
+        sum = sum + v.y; sum2 = sum2 + v.y * v.y;
+    }
+    const float inv_n = 1.0f / 174;
+    const float variance = (sum2 - (sum * sum * inv_n)) * inv_n;
+    const float norm_factor = bpm::llr_norm_factor(variance);
+    bool finite = true;
+    uint32_t gk = 0xFFFFFFFFu;
+#pragma unroll
+    for (int r = 0; r < 3; ++r) {
+        cw[r] = has[r] ? llr[lane + 64 * r] * norm_factor : 0.0f;
+        finite = finite && (__float_as_uint(cw[r]) & 0x7F800000u) != 0x7F800000u;
+        gk = min(gk, guard_key(cw[r]));
+    }
+    if (!__all(finite)) return false;
+    if (!__all(gk >= kGuardMinSoft)) ieee = 1;        // a soft bit outside the set sends every iteration to the IEEE form
+    return true;
+}
+
+// hard decision (llr > 0, on the bit pattern) and 8-bit weight of a soft bit; neither where the position does not exist
+__device__ __forceinline__ void hard_and_weight(uint32_t bits, bool valid, bool &hbit, int &w) {
+    const float a = __uint_as_float(bits & 0x7FFFFFFFu);
+    hbit = valid && (bits >> 31) == 0u && (bits & 0x7FFFFFFFu) != 0u;
+    w = a >= 32.0f ? 255 : (int)(a * 8.0f);
+    w = valid ? w : 0;
+}
 // sum of the weights over the set bits of x: 8-bit weights as eight bit planes (osd.hip, match.hip)
 __device__ __forceinline__ uint32_t metric_of(const uint64_t x[3], const uint64_t (&P)[8][3]) {
     uint32_t m = 0;
@@ -188,11 +246,54 @@ __device__ __forceinline__ bool read_record(const uint32_t *in32, int lane, uint
     dw0 = (uint32_t)__builtin_amdgcn_readlane((int)mine, 0);
     return still_failing(dw0, (uint32_t)__builtin_amdgcn_readlane((int)mine, 2));
 }
-// the wave leaves its candidate as it is: the record copied, info = { code, 0 }
+// the wave leaves its candidate as it is: the record copied, info = { code, 0 } (demod.hip: { code, 0, 0, 0 })
 __device__ __forceinline__ void leave_record(uint32_t *out32, const uint32_t *in32, uint32_t *info32, uint32_t mine, uint32_t code,
-                                             int lane) {
+                                             int lane, int info_dwords = 2) {
     if (lane < 12 && out32 != in32) out32[lane] = mine;
-    if (lane < 2) info32[lane] = lane == 0 ? code : 0u;
+    if (lane < info_dwords) info32[lane] = lane == 0 ? code : 0u;
+}
+
+// The head of a second-chance kernel: one wave64 per candidate, four per workgroup, the launch geometry of the LDPC kernel.
+// vb is the workgroup's place in frame order (blockIdx.x, or what ap.hip's XCD renumbering makes of it; kMulHigh: ap.hip's
+// division by the launcher's magic, and none at all for one block per frame).  The verdict, wave-uniform:
+//   gone  outside the bounds or behind the frame's count: nothing is read or written, records behind the count keep their
+//         bytes, and nothing of the struct but the verdict is set (zeros would cost a gone wave moves: a launch of gone
+//         waves only took 2 % longer with them);
+//   left  the candidate does not qualify for a second chance (marked: or the select kernel's mark in dword 0 of its info
+//         record is 0, demod.hip): its record is copied, its info record zeroed;
+//   run   status_out may be status_in, so `mine` holds the record as it was.
+// (match.hip carries these lines written out; its kernel says why.)
+enum CandVerdict { kCandGone, kCandLeft, kCandRun };
+struct CandWave {
+    int lane, wave, frame, ci;
+    size_t rec_index;
+    const uint32_t *in32;
+    uint32_t *out32, *info32;
+    uint32_t mine, dw0;
+    CandVerdict verdict;
+};
+template <bool kMulHigh = false, class Info>
+__device__ __forceinline__ CandWave cand_prologue(unsigned vb, unsigned blocks_per_frame, unsigned bpf_magic, const int32_t *counts,
+                                                  const ft8gpu_decode_status *status_in, ft8gpu_decode_status *status_out, Info *info,
+                                                  int nframes, int max_candidates, bool marked = false) {
+    static_assert(sizeof(ft8gpu_decode_status) == 48 && sizeof(Info) % 4 == 0, "record sizes");
+    CandWave w;
+    w.lane = threadIdx.x & 63;
+    w.wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    w.frame = !kMulHigh ? (int)(vb / blocks_per_frame) : (blocks_per_frame == 1u ? (int)vb : (int)__umulhi(vb, bpf_magic));
+    w.ci = (int)(vb - (unsigned)w.frame * blocks_per_frame) * 4 + w.wave;
+    w.verdict = kCandGone;
+    if (w.frame >= nframes || w.ci >= max_candidates) return w;
+    if (w.ci >= counts[w.frame]) return w;
+    w.rec_index = (size_t)w.frame * max_candidates + w.ci;
+    w.in32 = reinterpret_cast<const uint32_t *>(status_in + w.rec_index);
+    w.out32 = reinterpret_cast<uint32_t *>(status_out + w.rec_index);
+    w.info32 = reinterpret_cast<uint32_t *>(info + w.rec_index);
+    bool run = read_record(w.in32, w.lane, w.mine, w.dw0);
+    if (marked) run = (uint32_t)__builtin_amdgcn_readfirstlane((int)w.info32[0]) != 0u && run;
+    w.verdict = run ? kCandRun : kCandLeft;
+    if (!run) leave_record(w.out32, w.in32, w.info32, w.mine, 0u, w.lane, (int)(sizeof(Info) / 4));
+    return w;
 }
 // the wave's last store: the composed record of a success, the record as it was otherwise
 __device__ __forceinline__ void store_record(uint32_t *out32, const uint32_t *in32, const uint32_t *rec32, uint32_t mine,
@@ -243,6 +344,14 @@ __device__ __forceinline__ int compose_success_record(uint64_t B0, uint64_t B1, 
     const uint32_t crc_extracted = (uint32_t)(__brevll(B1) >> 37) & 0x3FFFu;          // bits 77..90
     if (crc_extracted != crc_calc) return 3;
     return compose_record(B0, B1, dw0, crc_extracted, crc_calc, rec32, lane) < 0 ? 4 : 1;
+}
+// The judgement of a word with nhard hard errors, the first failing check names the result: 5 all-zero, 2 more hard errors
+// than the gate allows, then CRC and unpack77 as above.
+__device__ __forceinline__ int judge_word(uint64_t B0, uint64_t B1, uint64_t B2, int nhard, int max_hard_errors, uint32_t dw0,
+                                          const uint16_t *crc_bit, uint32_t *rec32, int lane) {
+    if ((B0 | B1 | B2) == 0ull) return 5;
+    if (nhard > max_hard_errors) return 2;
+    return compose_success_record(B0, B1, dw0, crc_bit, rec32, lane);
 }
 
 // ---- the LDPC tables ------------------------------------------------------------------------------------------------------
@@ -321,6 +430,12 @@ inline void fill_ldpc_tables(LdpcTables &h) {
     fill_rowmasks(h.rowmask, h.row_valid);
     fill_owners(h.own6, h.own7);
     fill_crc_bits(h.crc_bit);
+}
+// the tables into a translation unit's own __device__ LdpcTables (symbol = HIP_SYMBOL of it; the copy reads a static object)
+inline hipError_t upload_ldpc_tables(const LdpcTables &symbol, hipStream_t s) {
+    static LdpcTables h;
+    fill_ldpc_tables(h);
+    return hipMemcpyToSymbolAsync(symbol, &h, sizeof(h), 0, hipMemcpyHostToDevice, s);
 }
 
 // ---- bp_decode, counting form -------------------------------------------------------------------------------------------
@@ -540,6 +655,67 @@ __device__ __forceinline__ BpWord bp_decode_counting(const float (&cw)[3], const
         fast_ok = guard_ok && !force_ieee_div;
     }
     return BpWord{ B0, B1, B2, min_errors, iter };
+}
+// The word BP left on soft bits whose hard decisions are X, judged: 7 no codeword (nhard stays 0), then judge_word on its
+// hard errors.  The record is composed where the soft bits were (combine.hip, demod.hip): the sync ends their reads.
+__device__ __forceinline__ int judge_bp_word(const BpWord &bp, uint64_t X0, uint64_t X1, uint64_t X2, int max_hard_errors,
+                                             uint32_t dw0, const uint16_t *crc_bit, uint32_t *rec32, int lane, int &nhard) {
+    nhard = 0;
+    if (bp.min_errors != 0) return 7;
+    nhard = __popcll(bp.B0 ^ X0) + __popcll(bp.B1 ^ X1) + __popcll(bp.B2 ^ X2);
+    wave_lds_sync();
+    return judge_word(bp.B0, bp.B1, bp.B2, nhard, max_hard_errors, dw0, crc_bit, rec32, lane);   // (BP leaves at an all-zero word unchecked)
+}
+
+// ---- launch geometry and the tags of what a stage gained ----------------------------------------------------------------
+// one workgroup per 4 candidates: bpf blocks (of 4 candidate waves) per frame, frame after frame.  mul_high: ap.hip's
+// tighter bound, which keeps its multiply-high division exact.
+struct CandGrid { unsigned bpf, nblocks; };
+inline hipError_t cand_grid(int nframes, int max_candidates, CandGrid &g, bool mul_high = false) {
+    g.bpf = (unsigned)(max_candidates + 3) / 4;
+    const unsigned long long nblocks = (unsigned long long)nframes * g.bpf;
+    g.nblocks = (unsigned)nblocks;
+    return nblocks >= (1ull << 31) || (mul_high && nblocks * g.bpf >= (1ull << 32)) ? hipErrorInvalidValue : hipSuccess;
+}
+
+// What a tag writes into a message record.  TagConst: pad[kPad] = v.  TagInfo: pad[kPad] = kAdd + the byte kField of the info
+// record of the message's candidate, [slot][max_candidates]; where cand_index is out of range nothing, or 0 with kElseZero.
+template <int kPad>
+struct TagConst {
+    uint8_t v;
+    __device__ void operator()(ft8gpu_message *m, int) const { m->pad[kPad] = v; }
+};
+template <int kPad, class Info, uint8_t Info::*kField, int kAdd = 0, bool kElseZero = false>
+struct TagInfo {
+    const Info *info;
+    int max_candidates;
+    __device__ void operator()(ft8gpu_message *m, int slot) const {
+        const int ci = m->cand_index;
+        if (ci < max_candidates) m->pad[kPad] = (uint8_t)(kAdd + info[(size_t)slot * max_candidates + ci].*kField);
+        else if (kElseZero) m->pad[kPad] = 0;
+    }
+};
+// The message records the append step added to a frame, n_before[frame * stride] <= r < n_msgs[frame], get the stage's tag.
+// One wave per slot of the pass, four per workgroup; slot -> frame through map, or the slot itself (map == nullptr).
+template <class Tag>
+__global__ __launch_bounds__(256)
+void ft8_tag_kernel(const int32_t *__restrict__ map, const int32_t *__restrict__ n_before, int stride,
+                    const int32_t *__restrict__ n_msgs, int nslots, ft8gpu_message *__restrict__ msgs, Tag tag) {
+    const int slot = blockIdx.x * 4 + (threadIdx.x >> 6), r = threadIdx.x & 63;
+    if (slot >= nslots) return;
+    const int frame = map ? map[slot] : slot;
+    int lo = n_before[(size_t)frame * stride], hi = n_msgs[frame];
+    lo = lo < 0 ? 0 : lo;
+    hi = hi > kMaxMessages ? kMaxMessages : hi;
+    if (r < lo || r >= hi) return;
+    tag(msgs + (size_t)frame * kMaxMessages + r, slot);
+}
+template <class Tag>
+inline hipError_t launch_tag(const int32_t *map, const int32_t *n_before, int stride, const int32_t *n_msgs, int nslots,
+                             ft8gpu_message *msgs, Tag tag, hipStream_t s) {
+    if (nslots < 1) return hipSuccess;
+    hipLaunchKernelGGL(ft8_tag_kernel<Tag>, dim3((nslots + 3) / 4), dim3(256), 0, s, map, n_before, stride, n_msgs, nslots, msgs, tag);
+    return hipGetLastError();
 }
 
 }  // namespace

@@ -8,8 +8,9 @@
 //                             of its own because status_out may be status_in: the main kernel's waves overwrite records other
 //                             waves would count.
 //   ft8_demod_kernel          one wave per candidate, four per workgroup, the launch geometry of the LDPC kernel.  A wave whose
-//                             candidate is not marked copies the record and leaves; no workgroup-wide step exists, so a
-//                             workgroup without a marked candidate never touches LDS.
+//                             candidate is not marked copies the record and leaves (cand_dev.h's head of the kernel, with
+//                             the mark); no workgroup-wide step exists, so a workgroup without a marked candidate never
+//                             touches LDS.
 //     symbol correlation: lane l loads the samples l + 64 a, a < 8, of a symbol straight from global memory (64 consecutive
 //       floats per load), multiplies each by its base-frequency entry of w4 (read through the cache: the 64 indices of a load
 //       are k4 apart, no LDS layout serves every k4), forms the 8-point DFT over a in registers and applies its eight twiddles
@@ -22,9 +23,9 @@
 //       half that share a bank with the first within 32 lanes); sets 2 and 3 with lanes as tone tuples (b1, b2) and, for a
 //       triple, a loop over b3 -- the Z reads are eight distinct addresses in eight distinct banks, the rest broadcast.  The
 //       maxima are taken on the bit patterns (the magnitudes are non-negative), so their order does not matter.
-//     normalisation in index order by every lane alike, the guard ahead of iteration 0, bp_decode, the CRC and the record:
-//       combine.hip's sequence on cand_dev.h's code.
-//   ft8_demod_tag_kernel      pad[3] of the records the append step added = the accepted set.
+//     normalisation in index order by every lane alike with the guard ahead of iteration 0, bp_decode, the judgement with the
+//       CRC and the record: cand_dev.h's code, as for combine.hip.
+//   launch_demod_tag          pad[3] of the records the append step added = the accepted set (cand_dev.h's tag kernel).
 //
 // LDS: 9 152 bytes per wave (the BP tile and the soft bits of cand_dev.h, 3 456, and Z, 5 696), 36 608 per workgroup.  No
 // scratch.  Indices: (k4 * n) mod 4096 is formed in uint32, which is exact for every int32 k4.
@@ -41,7 +42,6 @@ constexpr int kZPitch = 9;                                      // floats per sy
 constexpr int kZPlane = 712;                                    // 79 rows of 9
 constexpr int kDemodLds = kWaveLds + 2 * kZPlane;
 constexpr int kHyp = 2 * FT8GPU_DEMOD_TRANGE + 1 + 2 * FT8GPU_DEMOD_FRANGE;    // 9 time offsets, then d = -2, -1, 1, 2
-constexpr uint32_t kGuardMinSoft = ((127u - 58u) << 24) - 1u;   // guard_key(0x1p-58f), as combine.hip
 static_assert(FT8GPU_NN * kZPitch <= kZPlane && kTab == 4096 && kHyp == 13, "layout");
 static_assert(sizeof(ft8gpu_demod_info) == 16 && sizeof(ft8gpu_message) == 64, "record sizes");
 
@@ -229,28 +229,15 @@ void ft8_demod_kernel(const float *__restrict__ iq, const ft8gpu_candidate *__re
                       int force_ieee_div, unsigned blocks_per_frame) {
     __shared__ __attribute__((aligned(16))) float s_mem[4][kDemodLds];
 
-    const int lane = threadIdx.x & 63;
-    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    const int frame = (int)(blockIdx.x / blocks_per_frame);
-    const int ci = (int)(blockIdx.x - (unsigned)frame * blocks_per_frame) * 4 + wave;
-    if (frame >= nframes || ci >= max_candidates) return;
-    if (ci >= counts[frame]) return;                                  // wave-uniform: records behind the count are not touched
+    // not marked by the select kernel: not attempted, the record copied, the four dwords of the info record zero
+    const CandWave w = cand_prologue(blockIdx.x, blocks_per_frame, 0u, counts, status_in, status_out, info, nframes, max_candidates, true);
+    if (w.verdict != kCandRun) return;
+    const int lane = w.lane, frame = w.frame;
+    const size_t rec_index = w.rec_index;
+    const uint32_t *in32 = w.in32, mine = w.mine, dw0 = w.dw0;
+    uint32_t *out32 = w.out32, *info32 = w.info32;
 
-    const size_t rec_index = (size_t)frame * max_candidates + ci;
-    const uint32_t *in32 = reinterpret_cast<const uint32_t *>(status_in + rec_index);
-    uint32_t *out32 = reinterpret_cast<uint32_t *>(status_out + rec_index);
-    uint32_t *info32 = reinterpret_cast<uint32_t *>(info + rec_index);
-
-    uint32_t mine, dw0;
-    const bool qualifies = read_record(in32, lane, mine, dw0);
-    const uint32_t mark = (uint32_t)__builtin_amdgcn_readfirstlane((int)info32[0]);
-    if (!qualifies || mark == 0u) {                                   // not attempted: the record copied, the info record zero
-        if (lane < 12 && out32 != in32) out32[lane] = mine;
-        if (lane < 4) info32[lane] = 0u;
-        return;
-    }
-
-    float *toc = s_mem[wave];
+    float *toc = s_mem[w.wave];
     float *llr = toc + kTocFloats;
     float *zr = toc + kWaveLds, *zi = zr + kZPlane;
 
@@ -354,51 +341,16 @@ void ft8_demod_kernel(const float *__restrict__ iq, const ft8gpu_candidate *__re
             result = 6;
             continue;
         }
-        float sum = 0.0f, sum2 = 0.0f;                                // every lane: the same 174 values in index order
-        for (int i = 0; i < 172; i += 4) {
-            const float4 v = *reinterpret_cast<const float4 *>(llr + i);
-            sum = sum + v.x; sum2 = sum2 + v.x * v.x;
-            sum = sum + v.y; sum2 = sum2 + v.y * v.y;
-            sum = sum + v.z; sum2 = sum2 + v.z * v.z;
-            sum = sum + v.w; sum2 = sum2 + v.w * v.w;
-        }
-        {
-            const float2 v = *reinterpret_cast<const float2 *>(llr + 172);
-            sum = sum + v.x; sum2 = sum2 + v.x * v.x;
-            sum = sum + v.y; sum2 = sum2 + v.y * v.y;
-        }
-        const float inv_n = 1.0f / 174;
-        const float variance = (sum2 - (sum * sum * inv_n)) * inv_n;
-        const float norm_factor = bpm::llr_norm_factor(variance);
         float cw[3];
-        bool finite = true;
-        uint32_t gk = 0xFFFFFFFFu;
-#pragma unroll
-        for (int r = 0; r < 3; ++r) {
-            cw[r] = has[r] ? llr[lane + 64 * r] * norm_factor : 0.0f;
-            finite = finite && (__float_as_uint(cw[r]) & 0x7F800000u) != 0x7F800000u;
-            gk = min(gk, guard_key(cw[r]));
-        }
-        if (!__all(finite)) {                                         // wave-uniform: BP does not run
+        int ieee = force_ieee_div ? 1 : 0;                            // and the guard ahead of iteration 0 (cand_dev.h)
+        if (!renormalise_in_order(llr, has, lane, cw, ieee)) {        // wave-uniform: BP does not run
             result = 6;
             continue;
         }
-        // the guard ahead of iteration 0 (combine.hip): a soft bit outside the set sends every iteration to the IEEE form
-        const int ieee = (force_ieee_div || !__all(gk >= kGuardMinSoft)) ? 1 : 0;
         const uint64_t X0 = __ballot(cw[0] > 0.0f), X1 = __ballot(cw[1] > 0.0f), X2 = __ballot(cw[2] > 0.0f);
 
         const BpWord bp = bp_decode_counting(cw, has, has2_mask, toc, ldpc_lane(d_ldpc, lane), lane, max_iters, ieee);
-        const uint64_t B0 = bp.B0, B1 = bp.B1, B2 = bp.B2;
-        if (bp.min_errors != 0) result = 7;
-        else {
-            nhard = __popcll(B0 ^ X0) + __popcll(B1 ^ X1) + __popcll(B2 ^ X2);
-            if ((B0 | B1 | B2) == 0ull) result = 5;
-            else if (nhard > max_hard_errors) result = 2;
-            else {
-                wave_lds_sync();                                      // the soft bits have been read
-                result = compose_success_record(B0, B1, dw0, d_ldpc.crc_bit, rec32, lane);
-            }
-        }
+        result = judge_bp_word(bp, X0, X1, X2, max_hard_errors, dw0, d_ldpc.crc_bit, rec32, lane, nhard);
         if (result == 1) break;
     }
     store_record(out32, in32, rec32, mine, result == 1, lane);
@@ -411,26 +363,10 @@ void ft8_demod_kernel(const float *__restrict__ iq, const ft8gpu_candidate *__re
     }
 }
 
-__global__ __launch_bounds__(256)
-void ft8_demod_tag_kernel(const int32_t *__restrict__ n_before, const int32_t *__restrict__ n_msgs, int nframes,
-                          const ft8gpu_demod_info *__restrict__ info, int max_candidates, ft8gpu_message *__restrict__ msgs) {
-    const int frame = blockIdx.x * 4 + (threadIdx.x >> 6), r = threadIdx.x & 63;
-    if (frame >= nframes) return;
-    int lo = n_before[frame], hi = n_msgs[frame];
-    lo = lo < 0 ? 0 : lo;
-    hi = hi > kMaxMessages ? kMaxMessages : hi;
-    if (r < lo || r >= hi) return;
-    ft8gpu_message *m = msgs + (size_t)frame * kMaxMessages + r;
-    const int ci = m->cand_index;
-    m->pad[3] = ci < max_candidates ? info[(size_t)frame * max_candidates + ci].set : 0;
-}
-
 }  // namespace
 
 hipError_t demod_tables_init(hipStream_t s) {
-    static LdpcTables h;
-    fill_ldpc_tables(h);
-    return hipMemcpyToSymbolAsync(HIP_SYMBOL(d_ldpc), &h, sizeof(h), 0, hipMemcpyHostToDevice, s);
+    return upload_ldpc_tables(HIP_SYMBOL(d_ldpc), s);
 }
 
 hipError_t launch_demod(const float *iq, const ft8gpu_candidate *cands, const int32_t *counts, const ft8gpu_decode_status *status_in,
@@ -438,20 +374,18 @@ hipError_t launch_demod(const float *iq, const ft8gpu_candidate *cands, const in
                         const SubTables *tab, int sets, int max_hard_errors, int max_per_frame, int ldpc_iters, int force_ieee_div,
                         hipStream_t s) {
     if (nframes < 1) return hipSuccess;
-    const unsigned bpf = (unsigned)(max_candidates + 3) / 4;                  // blocks (of 4 candidate waves) per frame
-    const unsigned long long nblocks = (unsigned long long)nframes * bpf;
-    if (nblocks >= (1ull << 31)) return hipErrorInvalidValue;
+    CandGrid g;
+    if (cand_grid(nframes, max_candidates, g) != hipSuccess) return hipErrorInvalidValue;
     hipLaunchKernelGGL(ft8_demod_select_kernel, dim3((unsigned)nframes), dim3(64), 0, s, counts, status_in, info, max_candidates,
                        max_per_frame);
-    hipLaunchKernelGGL(ft8_demod_kernel, dim3((unsigned)nblocks), dim3(256), 0, s, iq, cands, counts, status_in, status_out, info,
-                       nframes, max_candidates, tab, sets, max_hard_errors, ldpc_iters, force_ieee_div, bpf);
+    hipLaunchKernelGGL(ft8_demod_kernel, dim3(g.nblocks), dim3(256), 0, s, iq, cands, counts, status_in, status_out, info,
+                       nframes, max_candidates, tab, sets, max_hard_errors, ldpc_iters, force_ieee_div, g.bpf);
     return hipGetLastError();
 }
 
 hipError_t launch_demod_tag(const int32_t *n_before, const int32_t *n_msgs, int nframes, const ft8gpu_demod_info *info,
                             int max_candidates, ft8gpu_message *msgs, hipStream_t s) {
-    if (nframes < 1) return hipSuccess;
-    hipLaunchKernelGGL(ft8_demod_tag_kernel, dim3((nframes + 3) / 4), dim3(256), 0, s, n_before, n_msgs, nframes, info, max_candidates,
-                       msgs);
-    return hipGetLastError();
+    // pad[3] of the records the append step added: the accepted set, 0 where cand_index is out of range
+    return launch_tag(nullptr, n_before, 1, n_msgs, nframes, msgs,
+                      TagInfo<3, ft8gpu_demod_info, &ft8gpu_demod_info::set, 0, true>{ info, max_candidates }, s);
 }

@@ -185,6 +185,22 @@ int for_each_chunk(ft8gpu_ctx *c, int nframes, int flags, const StageArg (&a)[N]
     return 0;
 }
 
+// The array arguments every second-chance stage entry has (OSD, AP, match, combine, demod), as rows 0 .. 5 of a[]: the first
+// input (mag, or iq for demod), cands, counts, status_in, then status_out and info with their staging buffers.  Records at and
+// behind a frame's count keep the caller's bytes: both outputs are uploaded in the host form.  A stage's own arrays follow
+// from row kCandRows.
+constexpr int kCandRows = 6;
+inline void cand_stage_rows(StageArg *a, const ft8gpu_ctx *c, const StageArg &first, const void *cands, const void *counts,
+                            const void *status_in, void *status_out, void *out_stage, void *info, void *info_stage, size_t info_bytes) {
+    const size_t mc = (size_t)c->params.max_candidates;
+    a[0] = first;
+    a[1] = { cands, c->d_cands, mc * sizeof(ft8gpu_candidate), kIn };
+    a[2] = { counts, c->d_counts, sizeof(int32_t), kIn };
+    a[3] = { status_in, c->d_status, mc * sizeof(ft8gpu_decode_status), kIn };
+    a[4] = { status_out, out_stage, mc * sizeof(ft8gpu_decode_status), kInOut };
+    a[5] = { info, info_stage, mc * info_bytes, kInOut };
+}
+
 // The pieces of [nstreams][nslots] frames that hold at most `bound` frames each: whole receivers (all their slots) while a
 // receiver fits, else runs of consecutive slots of one receiver.  each(fn) calls fn(r0, rg, s0, ns, f0) piece by piece, in the
 // order of the frames: rg receivers from r0, their slots [s0, s0 + ns), first frame f0 = r0 * nslots + s0; ns < nslots only

@@ -7,8 +7,8 @@
 //   ft8_expect_encode_kernel  one lane per table entry, once per frame and call: CRC-14 and the 83 generator parities of the
 //                             payload, the codeword as six dwords in position order, and per round of 64 entries the mask
 //                             of the live ones (used != 0, not expired at the state's slot).
-//   ft8_match_kernel          one wave64 per candidate, four per workgroup, the launch geometry of the LDPC kernel.  A wave
-//                             whose candidate does not qualify copies the record and leaves.  Lanes are table entries: 512
+//   ft8_match_kernel          one wave64 per candidate, four per workgroup, the launch geometry of the LDPC kernel (its head
+//                             is a copy of cand_dev.h's, the kernel says why).  Lanes are table entries: 512
 //                             entries are eight rounds of 64, and a round without a live entry is skipped on the scalar
 //                             side.  h and the weights are wave-uniform: three 64-bit words and eight bit planes of three
 //                             words (ballots, SGPRs), so the metric of an entry is 24 and / popcount pairs on its c_j ^ h
@@ -85,19 +85,19 @@ void ft8_match_kernel(const uint8_t *__restrict__ mag, const ft8gpu_candidate *_
                       unsigned blocks_per_frame) {
     __shared__ __attribute__((aligned(16))) uint32_t s_mem[4][kMatchLds];
 
+    // cand_dev.h's cand_prologue, written out: behind the shared routine this kernel's address arithmetic came out a dozen
+    // VALU instructions longer (42 registers for 41) and the stage 1 % slower on 4096 frames, whichever way its exits were put
     const int lane = threadIdx.x & 63;
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     const int frame = (int)(blockIdx.x / blocks_per_frame);
     const int ci = (int)(blockIdx.x - (unsigned)frame * blocks_per_frame) * 4 + wave;
     if (frame >= nframes || ci >= max_candidates) return;
     if (ci >= counts[frame]) return;                                  // wave-uniform: records behind the count are not touched
-
     const size_t rec_index = (size_t)frame * max_candidates + ci;
     const uint32_t *in32 = reinterpret_cast<const uint32_t *>(status_in + rec_index);
     uint32_t *out32 = reinterpret_cast<uint32_t *>(status_out + rec_index);
     uint32_t *info32 = reinterpret_cast<uint32_t *>(info + rec_index);
     static_assert(sizeof(ft8gpu_decode_status) == 48 && sizeof(ft8gpu_match_info) == 8, "record sizes");
-
     uint32_t mine, dw0;
     if (!read_record(in32, lane, mine, dw0)) {                        // does not qualify
         leave_record(out32, in32, info32, mine, 0u, lane);
@@ -126,14 +126,12 @@ void ft8_match_kernel(const uint8_t *__restrict__ mag, const ft8gpu_candidate *_
     uint64_t H[3], P[8][3];
 #pragma unroll
     for (int q = 0; q < 3; ++q) {
-        const uint32_t bits = __float_as_uint(cw[q]);
-        const float a = __uint_as_float(bits & 0x7FFFFFFFu);
-        const bool hbit = has[q] && (bits >> 31) == 0u && (bits & 0x7FFFFFFFu) != 0u;        // llr > 0
-        int w = a >= 32.0f ? 255 : (int)(a * 8.0f);
-        w = has[q] ? w : 0;
+        bool hbit;
+        int wt;
+        hard_and_weight(__float_as_uint(cw[q]), has[q], hbit, wt);
         H[q] = __ballot(hbit);
 #pragma unroll
-        for (int b = 0; b < 8; ++b) P[b][q] = __ballot((w >> b) & 1);
+        for (int b = 0; b < 8; ++b) P[b][q] = __ballot((wt >> b) & 1);
     }
 
     // ---- every live entry: lanes are entries, a round is 64 of them ----------------------------------------------------
@@ -243,18 +241,6 @@ void ft8_expect_update_kernel(const ft8gpu_message *__restrict__ msgs, const int
     if (lane == 0) { st->cursor = cursor; st->slot = slot; }
 }
 
-__global__ __launch_bounds__(256)
-void ft8_match_tag_kernel(const int32_t *__restrict__ n_before, int stride, const int32_t *__restrict__ n_msgs, int nframes,
-                          ft8gpu_message *__restrict__ msgs) {
-    const int frame = blockIdx.x * 4 + (threadIdx.x >> 6), r = threadIdx.x & 63;
-    if (frame >= nframes) return;
-    int lo = n_before[(size_t)frame * stride], hi = n_msgs[frame];
-    lo = lo < 0 ? 0 : lo;
-    hi = hi > kMaxMessages ? kMaxMessages : hi;
-    if (r < lo || r >= hi) return;
-    msgs[(size_t)frame * kMaxMessages + r].pad[2] = 1;
-}
-
 }  // namespace
 
 hipError_t launch_expect_encode(const ft8gpu_expect_state *states, int nframes, uint32_t max_age, const MsgTables *tab,
@@ -274,13 +260,12 @@ hipError_t launch_match(const uint8_t *mag, const ft8gpu_candidate *cands, const
                         const ft8gpu_decode_status *status_in, ft8gpu_decode_status *status_out, ft8gpu_match_info *info,
                         int nframes, int max_candidates, const void *work, int max_hard_errors, hipStream_t s) {
     if (nframes < 1) return hipSuccess;
-    const unsigned bpf = (unsigned)(max_candidates + 3) / 4;
-    const unsigned long long nblocks = (unsigned long long)nframes * bpf;
-    if (nblocks >= (1ull << 31)) return hipErrorInvalidValue;
+    CandGrid g;
+    if (cand_grid(nframes, max_candidates, g) != hipSuccess) return hipErrorInvalidValue;
     const uint32_t *cw = (const uint32_t *)work;
     const uint64_t *live = (const uint64_t *)((const char *)work + (size_t)nframes * kExpectCwBytes);
-    hipLaunchKernelGGL(ft8_match_kernel, dim3((unsigned)nblocks), dim3(256), 0, s, mag, cands, counts, status_in, status_out, info,
-                       nframes, max_candidates, cw, live, max_hard_errors, bpf);
+    hipLaunchKernelGGL(ft8_match_kernel, dim3(g.nblocks), dim3(256), 0, s, mag, cands, counts, status_in, status_out, info,
+                       nframes, max_candidates, cw, live, max_hard_errors, g.bpf);
     return hipGetLastError();
 }
 
@@ -293,7 +278,5 @@ hipError_t launch_expect_update(const ft8gpu_message *msgs, const int32_t *n_msg
 
 hipError_t launch_match_tag(const int32_t *n_before, int stride, const int32_t *n_msgs, int nframes, ft8gpu_message *msgs,
                             hipStream_t s) {
-    if (nframes < 1) return hipSuccess;
-    hipLaunchKernelGGL(ft8_match_tag_kernel, dim3((nframes + 3) / 4), dim3(256), 0, s, n_before, stride, n_msgs, nframes, msgs);
-    return hipGetLastError();
+    return launch_tag(nullptr, n_before, stride, n_msgs, nframes, msgs, TagConst<2>{ 1 }, s);    // pad[2] = 1: matched
 }

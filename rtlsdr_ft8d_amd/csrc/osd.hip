@@ -6,8 +6,8 @@
 //   the 91 first independent columns of the generator in that order are the basis; reduced echelon form; the patterns
 //   c0, c0 ^ R_k, c0 ^ R_i ^ R_j; the one with the smallest (metric, index) is judged: all-zero, hard errors, CRC, unpack77.
 //
-// One wave64 per candidate, four per workgroup, the launch geometry of the LDPC kernel.  A wave whose candidate does not
-// qualify copies the record and leaves.  Everything else is wave-local:
+// One wave64 per candidate, four per workgroup, the launch geometry of the LDPC kernel; the head of the kernel, which leaves a
+// candidate that does not qualify as it is, is cand_dev.h's.  Everything else is wave-local:
 //   * sort: 174 keys in LDS, every lane counts the keys that precede its three (a rank, no exchange network);
 //   * the generator with its COLUMNS in sorted order: lane k fetches the column mask (91 row bits) of the position ranked k,
 //     and 91 x 3 ballots turn the column masks into rows -- lane l then holds rows l and 64 + l as three 64-bit words each,
@@ -20,7 +20,8 @@
 //     and spreads j over the lanes.  (metric << 13 | index) through one butterfly minimum is the best pattern with the
 //     rule's tie break;
 //   * the best pattern returns to codeword order through the ranks, and the epilogue is the LDPC kernel's: CRC-14 by
-//     linearity, unpack77 on two 64-bit words, the 48-byte record composed in LDS (cand_dev.h, as the soft bits).
+//     linearity, unpack77 on two 64-bit words, the 48-byte record composed in LDS (cand_dev.h, as the soft bits, the
+//     judgement, the launch geometry and the kernel that tags the message records OSD gained).
 #include "cand_dev.h"
 
 namespace {
@@ -63,26 +64,15 @@ void ft8_osd_kernel(const uint8_t *__restrict__ mag, const ft8gpu_candidate *__r
                     int order, int max_hard_errors, unsigned blocks_per_frame) {
     __shared__ __attribute__((aligned(16))) uint32_t s_mem[4][kOsdLds];
 
-    const int lane = threadIdx.x & 63;
-    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    const int frame = (int)(blockIdx.x / blocks_per_frame);
-    const int ci = (int)(blockIdx.x - (unsigned)frame * blocks_per_frame) * 4 + wave;
-    if (frame >= nframes || ci >= max_candidates) return;
-    if (ci >= counts[frame]) return;                                  // wave-uniform: records behind the count are not touched
+    static_assert(sizeof(ft8gpu_osd_info) == 8, "record sizes");
+    const CandWave w = cand_prologue(blockIdx.x, blocks_per_frame, 0u, counts, status_in, status_out, info, nframes, max_candidates);
+    if (w.verdict != kCandRun) return;
+    const int lane = w.lane, frame = w.frame;
+    const size_t rec_index = w.rec_index;
+    const uint32_t *in32 = w.in32, mine = w.mine, dw0 = w.dw0;
+    uint32_t *out32 = w.out32, *info32 = w.info32;
 
-    const size_t rec_index = (size_t)frame * max_candidates + ci;
-    const uint32_t *in32 = reinterpret_cast<const uint32_t *>(status_in + rec_index);
-    uint32_t *out32 = reinterpret_cast<uint32_t *>(status_out + rec_index);
-    uint32_t *info32 = reinterpret_cast<uint32_t *>(info + rec_index);
-    static_assert(sizeof(ft8gpu_decode_status) == 48 && sizeof(ft8gpu_osd_info) == 8, "record sizes");
-
-    uint32_t mine, dw0;
-    if (!read_record(in32, lane, mine, dw0)) {                        // does not qualify
-        leave_record(out32, in32, info32, mine, 0u, lane);
-        return;
-    }
-
-    uint32_t *s = s_mem[wave];
+    uint32_t *s = s_mem[w.wave];
     uint32_t *perm = s + kOffPerm;
     uint32_t *rows = s + kOffRows;
 
@@ -122,14 +112,12 @@ void ft8_osd_kernel(const uint8_t *__restrict__ mag, const ft8gpu_candidate *__r
         const int k = lane + 64 * q;
         const bool valid = k < kLdpcN;
         const int n = valid ? (int)perm[k] : 0;
-        const uint32_t bits = s[n];
-        const float a = __uint_as_float(bits & 0x7FFFFFFFu);
-        const bool hbit = valid && (bits >> 31) == 0u && (bits & 0x7FFFFFFFu) != 0u;       // llr > 0
-        int w = a >= 32.0f ? 255 : (int)(a * 8.0f);
-        w = valid ? w : 0;
+        bool hbit;
+        int wt;
+        hard_and_weight(s[n], valid, hbit, wt);
         Hs[q] = __ballot(hbit);
 #pragma unroll
-        for (int b = 0; b < 8; ++b) P[b][q] = __ballot((w >> b) & 1);
+        for (int b = 0; b < 8; ++b) P[b][q] = __ballot((wt >> b) & 1);
         const uint32_t *col = d_osd.col[n];
         CL[q] = valid ? ((uint64_t)col[0] | ((uint64_t)col[1] << 32)) : 0ull;
         CH[q] = valid ? col[2] : 0u;
@@ -280,32 +268,12 @@ void ft8_osd_kernel(const uint8_t *__restrict__ mag, const ft8gpu_candidate *__r
 
     // ---- judge the best pattern: all-zero, hard errors, CRC, unpack77 -------------------------------------------------
     uint32_t *rec32 = s + kOffRec;
-    int result;
-    if ((B0 | B1 | B2) == 0ull) result = 5;
-    else if (nhard > max_hard_errors) result = 2;
-    else result = compose_success_record(B0, B1, dw0, d_osd.crc_bit, rec32, lane);
+    const int result = judge_word(B0, B1, B2, nhard, max_hard_errors, dw0, d_osd.crc_bit, rec32, lane);
     store_record(out32, in32, rec32, mine, result == 1, lane);
     if (lane == 0) {
         info32[0] = (uint32_t)result | ((uint32_t)nhard << 8) | ((uint32_t)pattern << 16);
         info32[1] = metric;
     }
-}
-
-// pad[0] of the message records OSD gained: the hard errors of the pattern behind them.  One wave per slot of the pass.
-__global__ __launch_bounds__(256)
-void ft8_osd_tag_kernel(const ft8gpu_osd_info *__restrict__ info, const int32_t *__restrict__ map,
-                        const int32_t *__restrict__ n_before, const int32_t *__restrict__ n_msgs, int nslots,
-                        int max_candidates, ft8gpu_message *__restrict__ msgs) {
-    const int slot = blockIdx.x * 4 + (threadIdx.x >> 6), r = threadIdx.x & 63;
-    if (slot >= nslots) return;
-    const int frame = map ? map[slot] : slot;
-    int lo = n_before[frame], hi = n_msgs[frame];
-    lo = lo < 0 ? 0 : lo;
-    hi = hi > kMaxMessages ? kMaxMessages : hi;
-    if (r < lo || r >= hi) return;
-    ft8gpu_message *m = msgs + (size_t)frame * kMaxMessages + r;
-    const int ci = m->cand_index;
-    if (ci < max_candidates) m->pad[0] = info[(size_t)slot * max_candidates + ci].nhard;
 }
 
 }  // namespace
@@ -329,18 +297,15 @@ hipError_t launch_osd(const uint8_t *mag, const ft8gpu_candidate *cands, const i
                       const ft8gpu_decode_status *status_in, ft8gpu_decode_status *status_out, ft8gpu_osd_info *info,
                       int nframes, int max_candidates, int order, int max_hard_errors, hipStream_t s) {
     if (nframes < 1) return hipSuccess;
-    const unsigned bpf = (unsigned)(max_candidates + 3) / 4;
-    const unsigned long long nblocks = (unsigned long long)nframes * bpf;
-    if (nblocks >= (1ull << 31)) return hipErrorInvalidValue;
-    hipLaunchKernelGGL(ft8_osd_kernel, dim3((unsigned)nblocks), dim3(256), 0, s, mag, cands, counts, status_in, status_out, info,
-                       nframes, max_candidates, order, max_hard_errors, bpf);
+    CandGrid g;
+    if (cand_grid(nframes, max_candidates, g) != hipSuccess) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(ft8_osd_kernel, dim3(g.nblocks), dim3(256), 0, s, mag, cands, counts, status_in, status_out, info,
+                       nframes, max_candidates, order, max_hard_errors, g.bpf);
     return hipGetLastError();
 }
 
 hipError_t launch_osd_tag(const ft8gpu_osd_info *info, const int32_t *map, const int32_t *n_before, const int32_t *n_msgs,
                           int nslots, int max_candidates, ft8gpu_message *msgs, hipStream_t s) {
-    if (nslots < 1) return hipSuccess;
-    hipLaunchKernelGGL(ft8_osd_tag_kernel, dim3((nslots + 3) / 4), dim3(256), 0, s, info, map, n_before, n_msgs, nslots,
-                       max_candidates, msgs);
-    return hipGetLastError();
+    // pad[0] of the message records OSD gained: the hard errors of the pattern behind them
+    return launch_tag(map, n_before, 1, n_msgs, nslots, msgs, TagInfo<0, ft8gpu_osd_info, &ft8gpu_osd_info::nhard>{ info, max_candidates }, s);
 }

@@ -53,6 +53,38 @@ def test_the_two_record_kernels_keep_their_lds_and_their_waves():
         assert K.waves_per_simd(k) >= 3
 
 
+def test_the_second_chance_kernels_keep_their_lds_and_their_waves():
+    """The five kernels that give the LDPC kernel's failures a second chance share their head, renormalisation, judgement and
+    launch geometry (csrc/cand_dev.h), and one tag kernel serves all five stages.  Before that, with a copy of those lines in
+    every file, they compiled to (VGPRs, SGPRs, LDS bytes, waves per SIMD by this tool's count): OSD 68, 106, 16 704, 7; AP 108,
+    106, 13 824, 4; match 41, 94, 3 264, 8; combine 73, 76, 13 824, 6; demod 142, 106, 36 608, 3, no scratch anywhere.  The
+    register counts may move; what must hold is no scratch, the same LDS and no fewer waves.  The tag kernel's instances use
+    neither scratch nor LDS and run eight waves per SIMD."""
+    sys.path.insert(0, os.path.join(ROOT, "tools"))
+    import kernel_resources as K
+    before = {"ft8_osd_kernel": (16704, 7), "ft8_ap_kernel": (13824, 4), "ft8_match_kernel": (3264, 8),
+              "ft8_combine_kernel": (13824, 6), "ft8_demod_kernel": (36608, 3)}
+    seen, tags = {}, []
+    for src in ("osd.hip", "ap.hip", "match.hip", "combine.hip", "demod.hip"):
+        ks = K.kernels_of(K.assemble(os.path.join(K.CSRC, src)))
+        for k, nice in zip(ks, K.demangle([k["symbol"] for k in ks])):
+            seen[nice] = k
+            if nice.startswith("ft8_tag_kernel<"):
+                tags.append((src, nice, k))
+    for name, (lds, waves) in before.items():
+        assert name in seen, (name, sorted(seen))
+        k = seen[name]
+        print(name, k, "waves", K.waves_per_simd(k))
+        assert k["scratch_bytes_per_lane"] == 0
+        assert k["lds_bytes"] == lds
+        assert K.waves_per_simd(k) >= waves
+    assert sorted(src for src, _, _ in tags) == ["ap.hip", "combine.hip", "demod.hip", "match.hip", "osd.hip"], tags
+    for src, nice, k in tags:
+        print(src, nice, k)
+        assert k["scratch_bytes_per_lane"] == 0 and k["lds_bytes"] == 0 and K.waves_per_simd(k) == 8
+    assert not [n for n in seen if n.endswith("_tag_kernel")], sorted(seen)     # the five copies are gone
+
+
 def test_committed_counter_evidence_describes_these_kernel_sources():
     """profiles/pmc_traffic.json carries the hash of csrc/ it was collected on; bench.py reports the counter-derived roofline
     figures (traffic, valu_*) only while that hash matches the tree.  A mismatch is not an error of the code -- it means

@@ -21,7 +21,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 
 
-KERNELS = ("ft8_ap_kernel", "ft8_ap_tag_kernel", "ft8_osd_kernel", "ft8_decode_kernel", "ft8_append_kernel")
+KERNELS = ("ft8_ap_kernel", "ft8_tag_kernel", "ft8_osd_kernel", "ft8_decode_kernel", "ft8_append_kernel")
 FORMS = ("ap1", "ap1_osd1", "ap2", "ap2_osd1")           # the AP launches of one step, in order
 HYPS = {1: ("CQ ? ?",), 2: ("CQ ? ?", "CQ DX ? ?")}
 

@@ -20,7 +20,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 
 
-KERNELS = ("ft8_osd_kernel", "ft8_osd_tag_kernel", "ft8_decode_kernel", "ft8_append_kernel")
+KERNELS = ("ft8_osd_kernel", "ft8_tag_kernel", "ft8_decode_kernel", "ft8_append_kernel")
 FORMS = ("p1_o1", "p1_o2", "p2_o1_pass1", "p2_o1_pass2", "p2_o2_pass1", "p2_o2_pass2")   # OSD launches of one step, in order
 
 
