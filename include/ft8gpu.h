@@ -1314,6 +1314,86 @@ int ft8gpu_wide_frames(ft8gpu_ctx *ctx, const uint8_t *raw, int ncaptures, size_
 int ft8gpu_decode_wide(ft8gpu_ctx *ctx, const uint8_t *raw, int ncaptures, size_t npairs, const int32_t *freq_bin,
                        int nchannels, ft8gpu_message *msgs, int32_t *n_msgs, int flags);
 
+/* ---- PCM front end: 48 .. 768 ksps real or complex samples, many channels from one capture -------------------------------------
+ * (DESIGN.md "PCM front end"; not in the reference.)  Sound cards deliver 48 kHz real audio; Hermes-Lite 2, Red Pitaya, Airspy
+ * HF+, SDRplay and Flex DAX-IQ deliver complex baseband at 48 .. 768 ksps, and SDR programs save it as two-channel .wav files.
+ * Every channel the caller names becomes one frame of the decoder; a capture's samples are read once for all of them.  The rule is
+ * exact: float32, one IEEE operation per step, nothing fused; every sum is sequential from +0 in the stated order; every index is
+ * integer arithmetic.
+ *
+ * Input.  rate = 3200 D, D one of 15, 30, 60, 120, 240 (ft8gpu_pcm_decimation); M = D / 3.  format = FT8GPU_PCM_S16 or
+ *   FT8GPU_PCM_F32, plus FT8GPU_PCM_COMPLEX or not.  Real: pcm [ncaptures][nsamples], x[n] = (a[n], 0).  Complex: I and Q
+ *   interleaved, pcm [ncaptures][2 * nsamples], x[n] = (a[2n], a[2n+1]).  S16: a = (float)s * 2^-15 (exact); F32: the caller's
+ *   floats as they are.  1 <= nsamples <= FT8GPU_PCM_MAX_SAMPLES_PER_D * D (15 s); x is zero outside 0 <= n < nsamples.  A capture
+ *   need not start at any alignment beyond that of its sample type.
+ * Channel.  freq_bin in units of 6.25 Hz from the input's 0 Hz (the centre of complex input, the audio axis of real input); the
+ *   frame's bins 0 .. 511 are the 1600 Hz above it.  Complex: -256 D <= freq_bin <= 256 D - 256; real: 0 <= freq_bin <= 256 D -
+ *   256.  F = freq_bin + 128 is the band's centre; c = floor((F + 16) / 32); q = F - 32 c, in [-16, 15].
+ * Stage A, at 3200 D sps.  w1[i] = (cos, -sin)(2 pi i / (16 D)), each the float of the double value, i = 0 .. 16 D - 1
+ *   (ft8gpu_pcm_mixer1): 200 Hz per step.  u[n] = x[n] * w1[(n c) mod 16 D] (the mathematical mod).  Complex input:
+ *   ur = xr * wr - xi * wi, ui = xr * wi + xi * wr, four products, one subtraction, one addition.  Real input: ur = xr * wr,
+ *   ui = xr * wi, two products.
+ *   Taps (ft8gpu_pcm_taps_a), in double: t[k] = (sinc((8000 * d) / (3200 D)) * I0(9 * sqrt(1 - (d / (4 M))^2))) / I0(9), d = k -
+ *   4 M, k = 0 .. 8 M (sinc and I0 as in the audio stage above); s = the sum of t, k ascending from 0; hA[k] = (float)(t[k] / s).
+ *   A Kaiser low-pass (beta 9) with its cutoff at 4000 Hz, 8 M + 1 taps centred on 4 M.
+ *   v[m] = sum over k = 0 .. 8 M, ascending, of hA[k] * u[M m + 4 M - k], real and imaginary parts separately, each term a product
+ *   and then an add, for 0 <= m < 144000; v is zero outside that range.  9600 sps, output m centred on input sample M m.
+ * Stage B, at 9600 sps.  w2[i] = (cos, -sin)(2 pi i / 1536) (ft8gpu_pcm_mixer2); z[m] = v[m] * w2[(m q) mod 1536]: zr = vr * wr -
+ *   vi * wi, zi = vr * wi + vi * wr.
+ *   Taps (ft8gpu_pcm_taps_b): the same formula with sinc((3200 * d) / 9600) and d / 23, d = k - 23, k = 0 .. 46; hB[47] = 0.
+ *   y[p] = sum over k = 0 .. 46, ascending, of hB[k] * z[3 p + 23 - k], for 0 <= p < 48000.
+ *   out[p] = y[p] * j^p as swaps and negations: p mod 4 = 0: (yr, yi); 1: (-yi, yr); 2: (-yr, -yi); 3: (yi, -yr), where -a is
+ *   0 - a, so that a zero stays +0: a silent capture gives +0 everywhere.  Output p is centred on input sample D p: a record's
+ *   dt_s is on the capture's time axis.
+ *   The frame is planar, [2][48000].  normalise != 0 then scales the frame by (float)(0.5 / (double)max(1e-24f, peak)), peak the
+ *   largest |value| of both planes: the peak normalisation of ft8gpu_rx_decimate.
+ * Any float input is defined: infinities, NaNs and subnormals are kept, not flushed.  An output that is a NaN by this rule is a NaN
+ * in every implementation (sign and payload unspecified); every other output is the same bytes everywhere.  Every capture starts
+ * from zero state.
+ * Whole chain, float taps, every D, q = -16, 0, 15, every 3.125 Hz of the input band (tests/test_pcm_cpu.py), with the taps of this header's own I0 series: at most
+ * -91.4 dB at or beyond 2400 Hz from the band's centre (the only offsets that alias into the bins the decoder reads; -91.4 dB at
+ * D = 15, -92.0 .. -92.1 dB at the other rates), within -0.0070 .. +0.0005 dB up to 800 Hz from it.  With 6 M + 1 taps in stage A
+ * the passband would droop to -0.116 dB, hence 8 M + 1. */
+#define FT8GPU_PCM_S16           0          /* int16_t samples */
+#define FT8GPU_PCM_F32           1          /* float samples */
+#define FT8GPU_PCM_COMPLEX       2          /* added to either: I and Q interleaved */
+#define FT8GPU_PCM_MAX_SAMPLES_PER_D 48000  /* nsamples <= 48000 D: 15 s */
+#define FT8GPU_PCM_MAX_SAMPLES   11520000   /* 15 s at 768 ksps */
+#define FT8GPU_PCM_MAX_D         240
+#define FT8GPU_PCM_MIX2          1536
+#define FT8GPU_PCM_TAPS_B        48
+#define FT8GPU_PCM_MAX_CHANNELS  16
+/* rate -> D (15, 30, 60, 120 or 240), 0 for a rate the front end does not take */
+int  ft8gpu_pcm_decimation(int rate);
+/* the tables of the rule (host, plain C): w1 as 16 D float pairs, w2 as 1536 float pairs, hA[0 .. 8 M] (exactly 8 M + 1 floats are
+ * written, no padding; returns 8 M + 1, or -1 for an unknown D), hB[0 .. 47].  An unknown D writes nothing. */
+void ft8gpu_pcm_mixer1(int D, float *out);
+void ft8gpu_pcm_mixer2(float out[2 * FT8GPU_PCM_MIX2]);
+int  ft8gpu_pcm_taps_a(int D, float *out);
+void ft8gpu_pcm_taps_b(float out[FT8GPU_PCM_TAPS_B]);
+/* stage entry: pcm [ncaptures][nsamples] (complex: [2 * nsamples]) of `format`, freq_bin [nchannels] (host memory in both pointer
+ * forms) -> iq [ncaptures][nchannels][2][48000].  Host or device pointers by `flags` (device form: pcm aligned to its sample type,
+ * iq 16-byte aligned), captures in chunks of max_frames.  Refused before anything is enqueued, the outputs untouched: a NULL
+ * context or array, an unknown format or rate, nchannels outside [1, 16], a freq_bin out of range for the format, nsamples
+ * outside [1, 48000 D], a misaligned pointer (device form).  The 9600 sps planes between the stages are allocated on the first
+ * call (a failed allocation is reported and leaves the context usable) and freed at ft8gpu_destroy. */
+int  ft8gpu_pcm_frames(ft8gpu_ctx *ctx, const void *pcm, int format, int rate, int ncaptures, int nsamples,
+                       const int32_t *freq_bin, int nchannels, float *iq, int normalise, int flags);
+/* The whole path: the frames capture * nchannels + channel, normalised, go through the ft8gpu_decode_messages path, at most
+ * max_frames at a time.  Then the channels of a capture are merged as ft8gpu_decode_wide merges them: a record is dropped if its
+ * 12 a91 bytes equal those of a record already kept for the capture whose channel lies less than 256 bins away; a kept record
+ * gets freq_hz = (cand.freq_offset + freq_bin + (float)cand.freq_sub / 2) * 6.25f and pad[0] = the channel's index; the walk
+ * stops at 50 * nchannels records.  msgs [ncaptures][50 * nchannels], n_msgs [ncaptures]; records at and behind n_msgs[c] are
+ * left untouched.  Arguments are refused as by ft8gpu_pcm_frames. */
+int  ft8gpu_decode_pcm(ft8gpu_ctx *ctx, const void *pcm, int format, int rate, int ncaptures, int nsamples,
+                       const int32_t *freq_bin, int nchannels, ft8gpu_message *msgs, int32_t *n_msgs, int flags);
+/* Reads a RIFF/WAVE file: format tag 1 at 16 bit or tag 3 (IEEE float) at 32 bit, or tag 0xFFFE (extensible) carrying one of the
+ * two; one channel (real) or two (I, Q); 48000, 96000, 192000, 384000 or 768000 Hz.  out gets the samples as the file holds them
+ * (little-endian), truncated to cap_bytes and to 15 s; *format, *rate and *nsamples (per channel) describe them.
+ * Chunks are skipped and padded as by ft8gpu_read_wav.  Everything else is refused with a line on stderr that names what was
+ * found: 0 = ok, -1 = refused (*nsamples = 0, *format = -1, *rate = 0). */
+int  ft8gpu_read_wav_pcm(const char *path, void *out, size_t cap_bytes, int *format, int *rate, int32_t *nsamples);
+
 /* ---- tooling: encoder + synthetic frames (pack77 / ft8_encode / CPFSK synth of
  *      decoderSelfTest, rtlsdr_ft8d.c:924-955) --------------------------------------------- */
 /* Message text -> 77 bits in 10 bytes (pack77, :927); 0 = ok, -1 = the text fits no message type.  Tokens are separated

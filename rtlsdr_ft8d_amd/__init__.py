@@ -103,6 +103,12 @@ WIDE_MIX1, WIDE_MIX2 = 6000, 3072    # FT8GPU_WIDE_MIX1 / _MIX2
 WIDE_TAPS = 96                   # FT8GPU_WIDE_TAPS
 WIDE_MAX_CHANNELS = 16           # FT8GPU_WIDE_MAX_CHANNELS
 WIDE_MAX_BIN = 176000            # FT8GPU_WIDE_MAX_BIN
+PCM_S16, PCM_F32, PCM_COMPLEX = 0, 1, 2   # FT8GPU_PCM_S16 / _F32 / _COMPLEX (added to either)
+PCM_RATES = (48000, 96000, 192000, 384000, 768000)   # 3200 D, D = 15 .. 240
+PCM_MIX2 = 1536                  # FT8GPU_PCM_MIX2
+PCM_TAPS_B = 48                  # FT8GPU_PCM_TAPS_B
+PCM_MAX_CHANNELS = 16            # FT8GPU_PCM_MAX_CHANNELS
+PCM_MAX_SAMPLES = 11520000       # FT8GPU_PCM_MAX_SAMPLES
 GFSK_SPS_IQ, GFSK_SPS_AUDIO = 512, 1920   # FT8GPU_GFSK_SPS_IQ / _AUDIO
 GFSK_TWIDDLES = 4096             # FT8GPU_GFSK_TWIDDLES
 GFSK_MAX_SIGNALS = 64            # FT8GPU_GFSK_MAX_SIGNALS
@@ -198,6 +204,8 @@ ABI_SYMBOLS = [
     "ft8gpu_gfsk_pulse", "ft8gpu_gfsk_ramp", "ft8gpu_gfsk_twiddles", "ft8gpu_synth_gfsk_frames", "ft8gpu_synth_gfsk_audio",
     "ft8gpu_write_wav",
     "ft8gpu_wide_mixer1", "ft8gpu_wide_mixer2", "ft8gpu_wide_taps", "ft8gpu_wide_frames", "ft8gpu_decode_wide",
+    "ft8gpu_pcm_decimation", "ft8gpu_pcm_mixer1", "ft8gpu_pcm_mixer2", "ft8gpu_pcm_taps_a", "ft8gpu_pcm_taps_b", "ft8gpu_pcm_frames",
+    "ft8gpu_decode_pcm", "ft8gpu_read_wav_pcm",
     "ft8_find_sync", "ft8_decode", "ft8_encode", "pack77",            # ft8_lib level (include/ft8_lib/ft8/*.h)
     "initFFTW", "freeFFTW", "ft8_subsystem", "ft8gpu_read_raw_iq", "ft8gpu_read_c2", "ft8gpu_write_raw_iq",
 ]
@@ -398,6 +406,17 @@ def _declare(L):
             f.restype = None
         L.ft8gpu_wide_frames.argtypes = [vp, vp, C.c_int, C.c_size_t, vp, C.c_int, vp, C.c_int, C.c_int]
         L.ft8gpu_decode_wide.argtypes = [vp, vp, C.c_int, C.c_size_t, vp, C.c_int, vp, vp, C.c_int]
+    if hasattr(L, "ft8gpu_pcm_frames"):                   # absent from older builds loaded by load_library_at
+        L.ft8gpu_pcm_decimation.argtypes = [C.c_int]
+        L.ft8gpu_pcm_mixer1.argtypes = [C.c_int, vp]
+        L.ft8gpu_pcm_mixer1.restype = None
+        L.ft8gpu_pcm_taps_a.argtypes = [C.c_int, vp]
+        for f in (L.ft8gpu_pcm_mixer2, L.ft8gpu_pcm_taps_b):
+            f.argtypes = [vp]
+            f.restype = None
+        L.ft8gpu_pcm_frames.argtypes = [vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, vp, C.c_int, vp, C.c_int, C.c_int]
+        L.ft8gpu_decode_pcm.argtypes = [vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, vp, C.c_int, vp, vp, C.c_int]
+        L.ft8gpu_read_wav_pcm.argtypes = [C.c_char_p, vp, C.c_size_t, C.POINTER(C.c_int), C.POINTER(C.c_int), i32p]
     L.ft8gpu_rx_decimate.argtypes = [vp, vp, C.c_int, C.c_size_t, vp, C.c_int, C.c_int]
     if hasattr(L, "ft8gpu_rx_stream"):                    # absent from older builds loaded by load_library_at
         L.ft8gpu_rx_stream.argtypes = [vp, vp, C.c_int, C.c_int, C.c_size_t, vp, vp, vp, C.c_int, C.c_int]
@@ -1325,6 +1344,57 @@ class Decoder:
         self._ck(self.lib.ft8gpu_decode_wide(self.h, _ptr(raw_dev), int(ncaptures), int(npairs), bins.ctypes.data, len(bins),
                                            _ptr(msgs_dev), _ptr(n_msgs_dev), DEVICE_PTRS))
 
+    @staticmethod
+    def _pcm_captures(pcm, complex_iq):
+        """[ncaptures][nsamples] (complex: [ncaptures][2 * nsamples], I and Q interleaved, or a complex64 array), int16 or float32
+        -> (array, format, nsamples)"""
+        pcm = np.asarray(pcm)
+        if pcm.dtype == np.complex64:
+            pcm, complex_iq = np.ascontiguousarray(pcm).view(np.float32), True
+        pcm = np.ascontiguousarray(pcm, np.int16 if pcm.dtype == np.int16 else np.float32)
+        assert pcm.ndim == 2 and (not complex_iq or pcm.shape[1] % 2 == 0)
+        fmt = (PCM_S16 if pcm.dtype == np.int16 else PCM_F32) | (PCM_COMPLEX if complex_iq else 0)
+        return pcm, fmt, pcm.shape[1] // (2 if complex_iq else 1)
+
+    def pcm_frames(self, pcm, rate, freq_bins, complex_iq=False, normalise=False):
+        """the PCM front end (ft8gpu_pcm_frames): captures at 48 .. 768 ksps, real [ncaptures][nsamples] or complex [ncaptures][2 *
+        nsamples], int16 or float32 -> iq [ncaptures][nchannels][2][48000], the 1600 Hz above 6.25 * freq_bin Hz of the input's
+        0 Hz as a frame of the decoder"""
+        pcm, fmt, nsamples = self._pcm_captures(pcm, complex_iq)
+        bins = np.ascontiguousarray(freq_bins, np.int32).reshape(-1)
+        out = np.zeros((pcm.shape[0], len(bins), 2, NSAMPLES), np.float32)
+        self._ck(self.lib.ft8gpu_pcm_frames(self.h, pcm.ctypes.data, fmt, int(rate), pcm.shape[0], nsamples, bins.ctypes.data, len(bins),
+                                          out.ctypes.data, int(normalise), HOST_PTRS))
+        return out
+
+    def pcm_frames_dev(self, pcm_dev, fmt, rate, ncaptures, nsamples, freq_bins, iq_dev, normalise=False):
+        """pcm_dev [ncaptures][nsamples] samples of fmt (aligned to the sample type) and iq_dev [ncaptures][nchannels][2][48000]
+        (16-byte aligned) in HBM; freq_bins stay on the host"""
+        bins = np.ascontiguousarray(freq_bins, np.int32).reshape(-1)
+        self._ck(self.lib.ft8gpu_pcm_frames(self.h, _ptr(pcm_dev), int(fmt), int(rate), int(ncaptures), int(nsamples), bins.ctypes.data,
+                                          len(bins), _ptr(iq_dev), int(normalise), DEVICE_PTRS))
+
+    def decode_pcm(self, pcm, rate, freq_bins, complex_iq=False, msgs=None):
+        """the whole path from PCM captures (ft8gpu_decode_pcm) -> (msgs [ncaptures][50 * nchannels], n_msgs [ncaptures]): every
+        channel's messages, a message heard in two overlapping channels once, freq_hz on the input's own axis, pad[0] the channel
+        it was taken from"""
+        pcm, fmt, nsamples = self._pcm_captures(pcm, complex_iq)
+        bins = np.ascontiguousarray(freq_bins, np.int32).reshape(-1)
+        shape = (pcm.shape[0], MAX_MESSAGES * max(len(bins), 1))
+        if msgs is None:
+            msgs = np.zeros(shape, MESSAGE_DTYPE)
+        assert msgs.dtype == MESSAGE_DTYPE and msgs.shape == shape and msgs.flags["C_CONTIGUOUS"]
+        n = np.zeros(pcm.shape[0], np.int32)
+        self._ck(self.lib.ft8gpu_decode_pcm(self.h, pcm.ctypes.data, fmt, int(rate), pcm.shape[0], nsamples, bins.ctypes.data, len(bins),
+                                          msgs.ctypes.data, n.ctypes.data, HOST_PTRS))
+        return msgs, n
+
+    def decode_pcm_dev(self, pcm_dev, fmt, rate, ncaptures, nsamples, freq_bins, msgs_dev, n_msgs_dev):
+        """pcm_dev, msgs_dev [ncaptures][50 * nchannels] and n_msgs_dev [ncaptures] in HBM; freq_bins stay on the host"""
+        bins = np.ascontiguousarray(freq_bins, np.int32).reshape(-1)
+        self._ck(self.lib.ft8gpu_decode_pcm(self.h, _ptr(pcm_dev), int(fmt), int(rate), int(ncaptures), int(nsamples), bins.ctypes.data,
+                                          len(bins), _ptr(msgs_dev), _ptr(n_msgs_dev), DEVICE_PTRS))
+
     def ap_candidates_dev(self, mag_dev, cands_dev, counts_dev, status_in_dev, nframes, hyps, max_hard_errors, status_out_dev, info_dev):
         """status_out_dev may be status_in_dev; info_dev: [nframes][max_candidates] 8-byte records; hyps stay on the host"""
         hyps = _ap_hyps(hyps)
@@ -1677,6 +1747,54 @@ def wide_taps():
     out = np.zeros(WIDE_TAPS, np.float32)
     load_library().ft8gpu_wide_taps(out.ctypes.data)
     return out
+
+
+def _pcm_d(D):
+    if 3200 * int(D) not in PCM_RATES:
+        raise Ft8GpuError(f"D = {D} is not one of 15, 30, 60, 120, 240")
+    return int(D)
+
+
+def pcm_mixer1(D):
+    """ft8gpu_pcm_mixer1: w1[i] = (cos, -sin)(2 pi i / (16 D)) as float32 [16 D][2]"""
+    out = np.zeros((16 * _pcm_d(D), 2), np.float32)
+    load_library().ft8gpu_pcm_mixer1(int(D), out.ctypes.data)
+    return out
+
+
+def pcm_mixer2():
+    """ft8gpu_pcm_mixer2: w2[i] = (cos, -sin)(2 pi i / 1536) as float32 [1536][2]"""
+    out = np.zeros((PCM_MIX2, 2), np.float32)
+    load_library().ft8gpu_pcm_mixer2(out.ctypes.data)
+    return out
+
+
+def pcm_taps_a(D):
+    """ft8gpu_pcm_taps_a: the first stage's low-pass at 3200 D sps as float32 [8 (D / 3) + 1]"""
+    out = np.zeros(8 * (_pcm_d(D) // 3) + 1, np.float32)
+    assert load_library().ft8gpu_pcm_taps_a(int(D), out.ctypes.data) == out.shape[0]
+    return out
+
+
+def pcm_taps_b():
+    """ft8gpu_pcm_taps_b: the second stage's low-pass at 9600 sps as float32 [48], 47 taps and a zero"""
+    out = np.zeros(PCM_TAPS_B, np.float32)
+    load_library().ft8gpu_pcm_taps_b(out.ctypes.data)
+    return out
+
+
+def read_wav_pcm(path, cap_bytes=8 * PCM_MAX_SAMPLES):
+    """ft8gpu_read_wav_pcm: a .wav of 16-bit PCM or 32-bit float, one channel (real) or two (I, Q), at 48 .. 768 kHz ->
+    (samples, format, rate): int16 or float32 [nsamples] (two channels: [2 * nsamples], interleaved), at most 15 s.  Anything else
+    raises; the library names what it found on stderr."""
+    cap = max(int(cap_bytes), 0)
+    out = np.zeros(cap, np.uint8)
+    fmt, rate, n = C.c_int(0), C.c_int(0), C.c_int32(0)
+    if load_library().ft8gpu_read_wav_pcm(os.fsencode(path), out.ctypes.data, cap, C.byref(fmt), C.byref(rate), C.byref(n)) != 0:
+        raise Ft8GpuError(f"{path}: not a readable PCM .wav of the PCM front end (the reason is on stderr)")
+    dtype = np.float32 if fmt.value & PCM_F32 else np.int16
+    count = n.value * (2 if fmt.value & PCM_COMPLEX else 1)
+    return out[:count * np.dtype(dtype).itemsize].view(dtype).copy(), fmt.value, rate.value
 
 
 def read_wav(path, cap=AUDIO_NSAMPLES):

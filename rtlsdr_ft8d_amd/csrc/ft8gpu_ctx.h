@@ -1,7 +1,7 @@
 // ft8gpu_ctx.h -- the context object and the helpers every host-side translation unit of the C ABI shares: api_context.hip,
 // api_mem.hip, api_pipeline.hip, api_multi.hip, api_stages.hip, api_messages.hip, api_multipass.hip, api_osd.hip, api_ap.hip,
 // api_glue.hip, api_rx_stream.hip, api_callhash.hip, api_match.hip, api_combine.hip, api_refine.hip, api_subtract.hip,
-// api_demod.hip, api_audio.hip, api_gfsk.hip, api_wide.hip.  Not installed.
+// api_demod.hip, api_audio.hip, api_gfsk.hip, api_wide.hip, api_pcm.hip.  Not installed.
 #pragma once
 #include "ctx_mem.h"
 #include "ft8gpu_internal.h"
@@ -123,6 +123,14 @@ struct ft8gpu_ctx {
     int32_t *d_rep_len = nullptr;
     uint32_t *d_rep_time = nullptr;
     size_t rep_cap = 0, rep_len_cap = 0, rep_time_cap = 0;
+    struct PcmTables *d_pcmtab = nullptr;  // PCM front end, lazily on its first call: the constant tables of every rate,
+    void *d_pcm_planes = nullptr;          //   the 9600 sps planes between its stages (a run of captures times the channels),
+    void *d_pcm_raw = nullptr;             //   host-pointer staging of a chunk's captures,
+    float *d_pcm_iq = nullptr;             //   the frame buffer of the whole path and of the host form [max_frames][2][48000],
+    ft8gpu_message *d_pcm_cmsgs = nullptr; //   the channels' records [captures][channels][50] and counts of a chunk,
+    int32_t *d_pcm_cn = nullptr;
+    ft8gpu_message *d_pcm_msgs = nullptr;  //   and host-pointer staging of the merged records
+    size_t pcm_planes_cap = 0, pcm_raw_cap = 0, pcm_cmsgs_cap = 0, pcm_cn_cap = 0, pcm_msgs_cap = 0;
 };
 
 // Every ABI entry that touches a context holds its mutex (two host threads on one context serialise instead
