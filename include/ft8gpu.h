@@ -717,6 +717,159 @@ int  ft8gpu_expect_insert(ft8gpu_expect_state *state, const uint8_t payload[10],
 /* the same with the payload ft8gpu_pack77 gives for text, as kind 0; -1 if the packer refuses the text */
 int  ft8gpu_expect_insert_text(ft8gpu_expect_state *state, const char *text);
 
+/* ---- call hints: a-priori decoding from the calls a receiver heard in earlier slots ----------------------------------------
+ * (DESIGN.md "Call hints"; not in the reference.)  Between AP's fixed guesses for the whole batch and a whole expected message
+ * lies most QSO traffic: a station heard in slot t sends again in t + 2 with the same call in the second field and new content,
+ * and its partner answers in t + 1 with both calls swapped and a third field nobody can predict.  A receiver keeps a table of
+ * call fields, and a candidate BP fails on is decoded again by the per-hypothesis rule of ft8gpu_ap_candidates under the
+ * few table entries its hard decisions agree with best.  The rule is exact; the preselection is integers only.
+ *
+ * State.  One ft8gpu_hint_state per receiver, caller-owned, in host or device memory like the arrays of the call (16-byte
+ * aligned in the device form).  entry[i]: a = field 1, payload bits 0..28 as a number, MSB first (n28 << 1 | flag), read
+ * & 0x1FFFFFFF; b = field 2, payload bits 29..57, likewise; stamp = the value of `slot` at the last write or refresh;
+ * kind 1 = "A ? ?", 2 = "? B ?", 3 = "A B ?"; phase (read & 1) = the slot parity at which the message is expected.  cursor
+ * (read modulo 512) is where the next new entry goes, slot the number of slots consumed so far, pad is zero.
+ * An entry is live when used != 0, kind is 1, 2 or 3, it is not expired -- max_age != 0 and (uint32_t)(slot - stamp) >
+ * max_age (unsigned: the counter may wrap) -- and, with use_phase != 0, ((slot ^ phase) & 1) == 0.  Expiry and phase are
+ * judged only when candidates are tried: an expired entry stays in the table and can be refreshed.
+ * The hypothesis of an entry (ft8gpu_hint_hypothesis): bits 74..76 are always masked, value 001 (i3 = 1); kind & 1 masks bits
+ * 0..28 with a, kind & 2 masks bits 29..57 with b.  nmask is 32 or 61.
+ *
+ * Trying candidates (ft8gpu_hint_candidates; the states are read only).
+ *   A candidate qualifies as for AP: its status record has ok == 0 and ldpc_errors != 0; one that does not gets status_out =
+ *   status_in and an all-zero info record.  llr, h and apmag are AP's; a non-finite llr[i] or apmag == 0: result 6, nothing
+ *   is tried.
+ *   Preselection.  For each live entry j, nbad_j = the number of masked positions where h differs from the hypothesis.  The
+ *   entry passes when nbad_j * 64 <= max_bad_per_64 * nmask_j.  Passing entries are ordered by nbad_j / nmask_j, compared by
+ *   cross-multiplication (key = nbad_j * 61 for nmask 32, nbad_j * 32 for nmask 61); ties go to the larger nmask, then to the
+ *   smaller index.  No passing entry: result 0, the info record is all zero and the status is copied.
+ *   The first `tries` passing entries are tried in that order, each by exactly the per-hypothesis rule of
+ *   ft8gpu_ap_candidates (the codes 7, 8, 5, 2, 3, 4, 1; the hard errors counted on the unmasked positions; the record
+ *   written on acceptance; 5 cannot occur: bit 76 of every hypothesis is 1, so a word that agrees with it is not all-zero, and
+ *   bp_decode leaves at an all-zero word as "no codeword", 7).  The first accepted entry wins.  For any candidate, the stage's status bytes equal those of
+ *   ft8gpu_ap_candidates called with these hypotheses in this order.
+ *
+ * Update (ft8gpu_hint_update).  Each receiver takes its slots in order, within a slot the records [0, n) in order, n =
+ * n_msgs[f] clamped to [0, 50].  Only records of type 1 (bits 74..76 = 1) count.  A field is a clear call when its n28 >=
+ * NTOKENS + MAX22 (the constants of the call hash rule): CQ and the other tokens, and hashed calls, are not.  With F1 = bits
+ * 0..28, F2 = bits 29..57 and p = slot & 1, in this order:
+ *   F2 clear:          insert(2, 0, F2, p)        the sender sends again
+ *   F2 clear:          insert(1, F2, 0, p ^ 1)    somebody calls the sender
+ *   F1 and F2 clear:   insert(3, F1, F2, p)       same direction, next step
+ *   F1 and F2 clear:   insert(3, F2, F1, p ^ 1)   the reply
+ *   insert(kind, a, b, phase): if an entry with used != 0 and the same (kind, a & 0x1FFFFFFF, b & 0x1FFFFFFF, phase & 1)
+ *   exists, expired or not (the smallest index if a caller-built state holds several), its stamp = slot.  Otherwise
+ *   entry[cursor % 512] = { a, b, stamp = slot, kind, used = 1, phase, pad = 0 } and cursor = cursor % 512 + 1.
+ * After the slot's records slot increments (unsigned, it wraps), also for a slot without records. */
+#define FT8GPU_HINT_ENTRIES 512
+typedef struct {
+    uint32_t a;              /*  0 */
+    uint32_t b;              /*  4 */
+    uint32_t stamp;          /*  8 */
+    uint8_t  kind;           /* 12 */
+    uint8_t  used;           /* 13 */
+    uint8_t  phase;          /* 14 */
+    uint8_t  pad;            /* 15 */
+} ft8gpu_hint_entry;
+typedef struct {
+    ft8gpu_hint_entry entry[FT8GPU_HINT_ENTRIES];       /*    0 */
+    uint32_t cursor;                                    /* 8192 */
+    uint32_t slot;                                      /* 8196 */
+    uint32_t pad[2];                                    /* 8200  zero */
+} ft8gpu_hint_state;
+typedef struct {
+    uint8_t  result;         /* 0 not attempted or no passing entry, 1 accepted, 2..5, 7, 8 the failing check, 6 unusable soft bits */
+    uint8_t  nhard;          /* result, nhard, iters: of the last entry tried */
+    uint8_t  ntried;         /* the number of entries tried, 0 .. tries */
+    uint8_t  iters;
+    uint8_t  results[FT8GPU_AP_MAX_HYPOTHESES];     /* the code of every entry tried, 0 for the others */
+    uint16_t index[FT8GPU_AP_MAX_HYPOTHESES];       /* the table indices tried, in order; 0 beyond ntried */
+} ft8gpu_hint_info;
+/* Recommended preselection gate, tries and max_hard_errors, from profiles/hint_gain.json (tools/hint_gain.py on one MI355X: a
+ * sweep over gates 8 .. 24, tries 1 / 2 / 4 and hard-error gates 30 / 40 / 50 / 174 on 96 receivers x 4 slots of QSOs that
+ * advance one step per slot at 20 and at 30 signals per frame, -24 .. 0 dB, the tables filled by the update rule alone and
+ * pre-filled with 236 entries from unrelated calls, and on 384 noise frames against full tables of unrelated entries).  No
+ * parameter set of the sweep accepts a message that was not sent, on any row, so the values are those of the largest gain:
+ * +246 / +367 planted messages over BP's 3848 / 4754 (+6.4 % / +7.7 %; 239 / 354 with the unrelated entries), where "CQ ? ?"
+ * a-priori decoding gains 13 / 26 and matching with derive 117 / 161 (and accepts 34 / 49 siblings of what was sent).  They
+ * cost 2.8 .. 3.9 BP runs per failing candidate; gate 16 with 2 tries keeps 85 % of the gain (208 / 313) for 0.54 .. 0.83.
+ * 24 is the sweep's upper edge: a wider gate has not been measured.  What "nothing wrong" bounds: at 24 / 4 the noise row ran
+ * 15 584 BP tries on 3977 failing candidates and the QSO rows about 90 000 without a wrong acceptance, so the rate is below
+ * about 3e-5 per try (95 %), not zero.  A hard-error gate below 40 loses messages, above it
+ * gains none. */
+#define FT8GPU_HINT_MAX_BAD_PER_64 24
+#define FT8GPU_HINT_TRIES 4
+#define FT8GPU_HINT_MAX_HARD_ERRORS 40
+typedef struct {
+    int32_t  tries;              /* 1 .. FT8GPU_AP_MAX_HYPOTHESES */
+    int32_t  max_bad_per_64;     /* 0 .. 64: the preselection gate */
+    int32_t  max_hard_errors;    /* 0 .. 174 */
+    uint32_t max_age;            /* slots; 0 = entries never expire */
+    int32_t  use_phase;          /* != 0: only entries of the slot's parity are live */
+} ft8gpu_hint_params;
+#ifndef __cplusplus
+_Static_assert(sizeof(ft8gpu_hint_entry) == 16 && offsetof(ft8gpu_hint_entry, b) == 4 && offsetof(ft8gpu_hint_entry, stamp) == 8 &&
+               offsetof(ft8gpu_hint_entry, kind) == 12 && offsetof(ft8gpu_hint_entry, used) == 13 &&
+               offsetof(ft8gpu_hint_entry, phase) == 14, "ft8gpu_hint_entry layout");
+_Static_assert(sizeof(ft8gpu_hint_state) == 8208 && offsetof(ft8gpu_hint_state, cursor) == 8192 &&
+               offsetof(ft8gpu_hint_state, slot) == 8196 && offsetof(ft8gpu_hint_state, pad) == 8200, "ft8gpu_hint_state layout");
+_Static_assert(sizeof(ft8gpu_hint_info) == 16 && offsetof(ft8gpu_hint_info, nhard) == 1 && offsetof(ft8gpu_hint_info, ntried) == 2 &&
+               offsetof(ft8gpu_hint_info, iters) == 3 && offsetof(ft8gpu_hint_info, results) == 4 &&
+               offsetof(ft8gpu_hint_info, index) == 8, "ft8gpu_hint_info layout");
+_Static_assert(sizeof(ft8gpu_hint_params) == 20 && offsetof(ft8gpu_hint_params, max_bad_per_64) == 4 &&
+               offsetof(ft8gpu_hint_params, max_hard_errors) == 8 && offsetof(ft8gpu_hint_params, max_age) == 12 &&
+               offsetof(ft8gpu_hint_params, use_phase) == 16, "ft8gpu_hint_params layout");
+#else
+static_assert(sizeof(ft8gpu_hint_entry) == 16 && offsetof(ft8gpu_hint_entry, b) == 4 && offsetof(ft8gpu_hint_entry, stamp) == 8 &&
+              offsetof(ft8gpu_hint_entry, kind) == 12 && offsetof(ft8gpu_hint_entry, used) == 13 &&
+              offsetof(ft8gpu_hint_entry, phase) == 14, "ft8gpu_hint_entry layout");
+static_assert(sizeof(ft8gpu_hint_state) == 8208 && offsetof(ft8gpu_hint_state, cursor) == 8192 &&
+              offsetof(ft8gpu_hint_state, slot) == 8196 && offsetof(ft8gpu_hint_state, pad) == 8200, "ft8gpu_hint_state layout");
+static_assert(sizeof(ft8gpu_hint_info) == 16 && offsetof(ft8gpu_hint_info, nhard) == 1 && offsetof(ft8gpu_hint_info, ntried) == 2 &&
+              offsetof(ft8gpu_hint_info, iters) == 3 && offsetof(ft8gpu_hint_info, results) == 4 &&
+              offsetof(ft8gpu_hint_info, index) == 8, "ft8gpu_hint_info layout");
+static_assert(sizeof(ft8gpu_hint_params) == 20 && offsetof(ft8gpu_hint_params, max_bad_per_64) == 4 &&
+              offsetof(ft8gpu_hint_params, max_hard_errors) == 8 && offsetof(ft8gpu_hint_params, max_age) == 12 &&
+              offsetof(ft8gpu_hint_params, use_phase) == 16, "ft8gpu_hint_params layout");
+#endif
+/* stage entry: mag [nframes][94208], cands / status_in / status_out / info [nframes][max_candidates], counts [nframes],
+ * states [nframes] (the state of the receiver each frame belongs to; 16-byte aligned in the device form); host or device
+ * pointers by `flags`, params in host memory.  Records below counts[f] are written, records at and behind it are not
+ * touched.  status_out may be status_in. */
+int ft8gpu_hint_candidates(ft8gpu_ctx *ctx, const uint8_t *mag, const ft8gpu_candidate *cands, const int32_t *counts,
+                           const ft8gpu_decode_status *status_in, int nframes, const ft8gpu_hint_state *states,
+                           const ft8gpu_hint_params *params, ft8gpu_decode_status *status_out, ft8gpu_hint_info *info,
+                           int flags);
+/* stage entry of the update rule: msgs [nstreams][nslots][50], n_msgs [nstreams][nslots], state [nstreams], one object per
+ * receiver, read at entry and written at exit; host or device pointers by `flags` (device form: msgs and state 16-byte
+ * aligned).  The host form stages whole receivers, or runs of slots of one receiver, at most max_frames frames at a time;
+ * the result does not depend on the cut. */
+int ft8gpu_hint_update(ft8gpu_ctx *ctx, const ft8gpu_message *msgs, const int32_t *n_msgs, int nstreams, int nslots,
+                       ft8gpu_hint_state *state, int flags);
+/* The whole path over iq [nstreams][nslots][2][48000], for the frame of receiver r at slot t:
+ *   1. the records [0, n1) are byte for byte those of ft8gpu_decode_messages;
+ *   2. ft8gpu_hint_candidates runs in place on that frame's BP status records, against the receiver's state as the slots
+ *      0 .. t - 1 left it;
+ *   3. the append step of the multi-pass path adds, in candidate order, every unique gained message not yet among the
+ *      frame's records, up to 50 in all; pad[2] of such a record is 3 (1 is match, 2 is combine);
+ *   4. the update rule runs over the frame's final records.
+ * n_by_stage [nstreams][nslots][2] (NULL: not written): the count after BP and after the hint stage.  nslots slots in one
+ * call leave the bytes that nslots calls of one slot leave, in msgs, n_msgs and the state.  Not composed with AP, OSD,
+ * match or multi-pass. */
+int ft8gpu_decode_messages_hinted(ft8gpu_ctx *ctx, const float *iq, int nstreams, int nslots, ft8gpu_hint_state *state,
+                                  const ft8gpu_hint_params *params, ft8gpu_message *msgs, int32_t *n_msgs,
+                                  int32_t *n_by_stage, int flags);
+/* Host helpers of the table (plain C, no GPU). */
+void ft8gpu_hint_reset(ft8gpu_hint_state *state);
+/* insert(kind, a, b, phase) of the update rule at state->slot; a and b are stored & 0x1FFFFFFF, phase & 1; kind 1, 2 or 3,
+ * else -1 */
+int  ft8gpu_hint_insert(ft8gpu_hint_state *state, int kind, uint32_t a, uint32_t b, int phase);
+/* the same from a pattern of ft8gpu_ap_from_text with FIELD1 or CALL2 (or both) known and THIRD `?`: "K1ABC ? ?" lists a
+ * caller's own call, "? W9XYZ ?", "K1ABC W9XYZ ?".  The field that is `?` is stored as 0.  -1: not such a pattern */
+int  ft8gpu_hint_insert_text(ft8gpu_hint_state *state, const char *pattern, int phase);
+/* the hypothesis of an entry as ft8gpu_ap_candidates takes it; -1 (and *out all zero) if kind is not 1, 2 or 3 */
+int  ft8gpu_hint_hypothesis(const ft8gpu_hint_entry *entry, ft8gpu_ap_hypothesis *out);
+
 /* ---- soft-bit memory: the soft bits of undecoded candidates summed over a receiver's slots ---------------------------------
  * (DESIGN.md "Soft-bit memory"; not in the reference, where every 15 s slot starts from nothing.)  A station that repeats its
  * message at the same audio frequency and clock offset, every time just below BP's threshold, is never decoded at all: the

@@ -63,6 +63,16 @@ EXPECT_STATE_DTYPE = np.dtype([("entry", EXPECT_ENTRY_DTYPE, (EXPECT_ENTRIES,)),
 MATCH_INFO_DTYPE = np.dtype([("result", "u1"), ("nhard", "u1"), ("index", "<u2"), ("metric", "<i4")])
 MATCH_MAX_HARD_ERRORS = 49  # FT8GPU_MATCH_MAX_HARD_ERRORS, the recommended gate
 assert EXPECT_ENTRY_DTYPE.itemsize == 16 and EXPECT_STATE_DTYPE.itemsize == 8208 and MATCH_INFO_DTYPE.itemsize == 8
+# ft8gpu_hint_entry / ft8gpu_hint_state / ft8gpu_hint_info: the call hints of a receiver (ft8gpu_hint_candidates)
+HINT_ENTRIES = 512          # FT8GPU_HINT_ENTRIES
+HINT_ENTRY_DTYPE = np.dtype([("a", "<u4"), ("b", "<u4"), ("stamp", "<u4"), ("kind", "u1"), ("used", "u1"), ("phase", "u1"), ("pad", "u1")])
+HINT_STATE_DTYPE = np.dtype([("entry", HINT_ENTRY_DTYPE, (HINT_ENTRIES,)), ("cursor", "<u4"), ("slot", "<u4"), ("pad", "<u4", (2,))])
+HINT_INFO_DTYPE = np.dtype([("result", "u1"), ("nhard", "u1"), ("ntried", "u1"), ("iters", "u1"), ("results", "u1", (4,)),
+                            ("index", "<u2", (4,))])
+HINT_MAX_BAD_PER_64 = 24    # FT8GPU_HINT_MAX_BAD_PER_64, FT8GPU_HINT_TRIES, FT8GPU_HINT_MAX_HARD_ERRORS: the recommended values
+HINT_TRIES = 4
+HINT_MAX_HARD_ERRORS = 40
+assert HINT_ENTRY_DTYPE.itemsize == 16 and HINT_STATE_DTYPE.itemsize == 8208 and HINT_INFO_DTYPE.itemsize == 16
 # ft8gpu_softmem_entry / ft8gpu_softmem_state / ft8gpu_combine_info: the soft-bit memory of a receiver (ft8gpu_combine_candidates)
 SOFTMEM_ENTRIES = 128       # FT8GPU_SOFTMEM_ENTRIES
 SOFTMEM_ENTRY_DTYPE = np.dtype([("cand", CAND_DTYPE), ("used", "u1"), ("count", "u1"), ("pad", "<u2"), ("stamp", "<u4"),
@@ -142,6 +152,13 @@ class ExpectParams(C.Structure):
     _fields_ = [("max_hard_errors", C.c_int32), ("max_age", C.c_uint32), ("derive", C.c_int32)]
 
 
+class HintParams(C.Structure):
+    """ft8gpu_hint_params: tries 1..4, max_bad_per_64 0..64, max_hard_errors 0..174, max_age in slots (0: never expires),
+    use_phase != 0: only entries of the slot's parity are live"""
+    _fields_ = [("tries", C.c_int32), ("max_bad_per_64", C.c_int32), ("max_hard_errors", C.c_int32), ("max_age", C.c_uint32),
+                ("use_phase", C.c_int32)]
+
+
 class CombineParams(C.Structure):
     """ft8gpu_combine_params: min_agree 0..174, max_age in slots (0: never expires), store_per_slot 0..128"""
     _fields_ = [("min_agree", C.c_int32), ("max_age", C.c_uint32), ("store_per_slot", C.c_int32)]
@@ -170,6 +187,7 @@ STREAM_LEGACY = 1                       # FT8GPU_STREAM_LEGACY (= hipStreamLegac
 DBG_FORCE_IEEE_DIV, DBG_PIPELINE_FORM, DBG_NO_OVERLAP = 1, 2, 4      # FT8GPU_DBG_* test hooks (per context)
 # selector bits of the alternative (bit-identical) kernel forms: accepted by the A/B build only (csrc/ft8gpu_internal.h)
 AB_WATERFALL_LDS, AB_HEAP_LANE_PER_FRAME, AB_HEAP_WAVE_PER_FRAME = 8, 16, 32
+AB_HINT_IN_WAVE = 64                                                 # call hints: the form without the pre-kernel (A/B build)
 
 
 class Ft8GpuError(RuntimeError):
@@ -195,6 +213,8 @@ ABI_SYMBOLS = [
     "ft8gpu_callhash_insert", "ft8gpu_callhash_lookup", "ft8gpu_format_resolved",
     "ft8gpu_match_candidates", "ft8gpu_expect_update", "ft8gpu_decode_messages_expected", "ft8gpu_expect_reset",
     "ft8gpu_expect_insert", "ft8gpu_expect_insert_text",
+    "ft8gpu_hint_candidates", "ft8gpu_hint_update", "ft8gpu_decode_messages_hinted", "ft8gpu_hint_reset", "ft8gpu_hint_insert",
+    "ft8gpu_hint_insert_text", "ft8gpu_hint_hypothesis",
     "ft8gpu_combine_candidates", "ft8gpu_softmem_update", "ft8gpu_decode_messages_combined", "ft8gpu_softmem_reset",
     "ft8gpu_refine_messages", "ft8gpu_decode_messages_refined", "ft8gpu_refined_estimate", "ft8gpu_format_messages_refined",
     "ft8gpu_subtract_messages", "ft8gpu_decode_messages_subtracted", "ft8gpu_subtract_twiddles",
@@ -361,6 +381,15 @@ def _declare(L):
         L.ft8gpu_expect_reset.restype = None
         L.ft8gpu_expect_insert.argtypes = [vp, vp, C.c_int]
         L.ft8gpu_expect_insert_text.argtypes = [vp, C.c_char_p]
+    if hasattr(L, "ft8gpu_hint_candidates"):
+        L.ft8gpu_hint_candidates.argtypes = [vp, vp, vp, vp, vp, C.c_int, vp, C.POINTER(HintParams), vp, vp, C.c_int]
+        L.ft8gpu_hint_update.argtypes = [vp, vp, vp, C.c_int, C.c_int, vp, C.c_int]
+        L.ft8gpu_decode_messages_hinted.argtypes = [vp, vp, C.c_int, C.c_int, vp, C.POINTER(HintParams), vp, vp, vp, C.c_int]
+        L.ft8gpu_hint_reset.argtypes = [vp]
+        L.ft8gpu_hint_reset.restype = None
+        L.ft8gpu_hint_insert.argtypes = [vp, C.c_int, C.c_uint32, C.c_uint32, C.c_int]
+        L.ft8gpu_hint_insert_text.argtypes = [vp, C.c_char_p, C.c_int]
+        L.ft8gpu_hint_hypothesis.argtypes = [vp, vp]
     if hasattr(L, "ft8gpu_combine_candidates"):           # absent from older builds loaded by load_library_at
         L.ft8gpu_combine_candidates.argtypes = [vp, vp, vp, vp, vp, C.c_int, vp, C.c_uint32, C.c_int, vp, vp, C.c_int]
         L.ft8gpu_softmem_update.argtypes = [vp, vp, vp, vp, vp, vp, C.c_int, vp, C.c_int, C.c_int]
@@ -567,6 +596,41 @@ def expect_insert_text(state, text):
     """ft8gpu_expect_insert_text: the message as ft8gpu_pack77 packs it, as a heard entry (in place)"""
     if load_library().ft8gpu_expect_insert_text(_one_expect_state(state).ctypes.data, text.encode()) != 0:
         raise ValueError(f"cannot pack {text!r} as an FT8 message")
+
+
+def hint_state(n=1):
+    """n reset tables of call hints (HINT_STATE_DTYPE [n], all zero: what ft8gpu_hint_reset leaves)"""
+    return np.zeros(n, HINT_STATE_DTYPE)
+
+
+def _one_hint_state(state):
+    assert isinstance(state, np.ndarray) and state.dtype == HINT_STATE_DTYPE and state.size == 1 and state.flags["C_CONTIGUOUS"]
+    return state
+
+
+def hint_reset(state):
+    """ft8gpu_hint_reset on one state (a HINT_STATE_DTYPE array of one element, in place)"""
+    load_library().ft8gpu_hint_reset(_one_hint_state(state).ctypes.data)
+
+
+def hint_insert(state, kind, a, b, phase):
+    """ft8gpu_hint_insert: insert(kind, a, b, phase) of the update rule at the state's slot (in place)"""
+    if load_library().ft8gpu_hint_insert(_one_hint_state(state).ctypes.data, int(kind), int(a) & 0xFFFFFFFF, int(b) & 0xFFFFFFFF,
+                                         int(phase)) != 0:
+        raise ValueError(f"kind {kind} is not 1, 2 or 3")
+
+
+def hint_insert_text(state, pattern, phase):
+    """ft8gpu_hint_insert_text: "K1ABC ? ?", "? W9XYZ ?" or "K1ABC W9XYZ ?" as an entry expected at slot parity `phase`"""
+    if load_library().ft8gpu_hint_insert_text(_one_hint_state(state).ctypes.data, pattern.encode(), int(phase)) != 0:
+        raise ValueError(f"not a call hint pattern: {pattern!r}")
+
+
+def hint_hypothesis(entry):
+    """ft8gpu_hint_hypothesis: the AP_HYP_DTYPE record of one HINT_ENTRY_DTYPE entry, or None if its kind is not 1, 2 or 3"""
+    e = np.array(entry, HINT_ENTRY_DTYPE, ndmin=1)
+    out = np.zeros(1, AP_HYP_DTYPE)
+    return out[0] if load_library().ft8gpu_hint_hypothesis(e.ctypes.data, out.ctypes.data) == 0 else None
 
 
 def format_resolved(msgs, resolved, n):
@@ -1043,6 +1107,74 @@ class Decoder:
         self._ck(self.lib.ft8gpu_decode_messages_expected(self.h, _ptr(iq_dev), nstreams, nslots, _ptr(state_dev), C.byref(p),
                                                           _ptr(msgs_dev), _ptr(n_msgs_dev),
                                                           None if n_by_stage_dev is None else _ptr(n_by_stage_dev), DEVICE_PTRS))
+
+    def hint_candidates(self, mag, cands, counts, status_in, states, tries=HINT_TRIES, max_bad_per_64=HINT_MAX_BAD_PER_64,
+                        max_hard_errors=HINT_MAX_HARD_ERRORS, max_age=0, use_phase=True,
+                        status_out=None, info=None):
+        """ft8gpu_hint_candidates.  states: HINT_STATE_DTYPE [B], the table of the receiver each frame belongs to (read only)
+        -> (status_out [B][cap] STATUS_DTYPE, info [B][cap] HINT_INFO_DTYPE), new arrays; records at and behind counts[f] keep
+        what status_out / info held (zeros when None)"""
+        mag = np.ascontiguousarray(mag, np.uint8).reshape(-1, MAG_ARRAY)
+        B = mag.shape[0]
+        cands, counts, status_in, out, inf = self._cand_arrays(B, cands, counts, status_in, status_out, info, HINT_INFO_DTYPE)
+        states = np.ascontiguousarray(states)
+        assert states.dtype == HINT_STATE_DTYPE and states.shape == (B,)
+        p = HintParams(int(tries), int(max_bad_per_64), int(max_hard_errors), int(max_age), int(bool(use_phase)))
+        self._ck(self.lib.ft8gpu_hint_candidates(self.h, mag.ctypes.data, cands.ctypes.data, counts.ctypes.data, status_in.ctypes.data,
+                                                 B, states.ctypes.data, C.byref(p), out.ctypes.data, inf.ctypes.data, HOST_PTRS))
+        return out.view(STATUS_DTYPE).reshape(B, self.max_candidates), inf
+
+    def hint_candidates_dev(self, mag_dev, cands_dev, counts_dev, status_in_dev, nframes, states_dev, tries, max_bad_per_64,
+                            max_hard_errors, max_age, use_phase, status_out_dev, info_dev):
+        """status_out_dev may be status_in_dev; states_dev: [nframes] 8208-byte tables, 16-byte aligned; info_dev: 16-byte records"""
+        p = HintParams(int(tries), int(max_bad_per_64), int(max_hard_errors), int(max_age), int(bool(use_phase)))
+        self._ck(self.lib.ft8gpu_hint_candidates(self.h, _ptr(mag_dev), _ptr(cands_dev), _ptr(counts_dev), _ptr(status_in_dev), nframes,
+                                                 _ptr(states_dev), C.byref(p), _ptr(status_out_dev), _ptr(info_dev), DEVICE_PTRS))
+
+    def hint_update(self, msgs, n_msgs, state=None):
+        """ft8gpu_hint_update.  msgs: MESSAGE_DTYPE [nstreams][nslots][50], n_msgs: int32 [nstreams][nslots]; state:
+        HINT_STATE_DTYPE [nstreams] as a previous call returned it, or None for reset tables (the caller's array stays as it
+        is) -> the exit state [nstreams]"""
+        msgs = np.ascontiguousarray(msgs)
+        n_msgs = np.ascontiguousarray(n_msgs, np.int32)
+        nstreams, nslots = n_msgs.shape
+        assert msgs.dtype == MESSAGE_DTYPE and msgs.shape == (nstreams, nslots, MAX_MESSAGES)
+        state = np.zeros(nstreams, HINT_STATE_DTYPE) if state is None else np.array(state, HINT_STATE_DTYPE, copy=True, ndmin=1)
+        assert state.shape == (nstreams,)
+        self._ck(self.lib.ft8gpu_hint_update(self.h, msgs.ctypes.data, n_msgs.ctypes.data, nstreams, nslots, state.ctypes.data, HOST_PTRS))
+        return state
+
+    def hint_update_dev(self, msgs_dev, n_msgs_dev, nstreams, nslots, state_dev):
+        """all arrays in HBM; msgs and state 16-byte aligned; the states are updated in place"""
+        self._ck(self.lib.ft8gpu_hint_update(self.h, _ptr(msgs_dev), _ptr(n_msgs_dev), nstreams, nslots, _ptr(state_dev), DEVICE_PTRS))
+
+    def decode_messages_hinted(self, iq, tries=HINT_TRIES, max_bad_per_64=HINT_MAX_BAD_PER_64, max_hard_errors=HINT_MAX_HARD_ERRORS, state=None,
+                               max_age=0, use_phase=True, msgs=None):
+        """ft8gpu_decode_messages_hinted.  iq: float32 [nstreams][nslots][2][48000]; state as in hint_update
+        -> (msgs [nstreams][nslots][50], n_msgs [nstreams][nslots], n_by_stage [nstreams][nslots][2]: the count after BP and
+        after the hint stage, the exit state [nstreams]); pad[2] of a record gained by a call hint is 3"""
+        iq = np.ascontiguousarray(iq, np.float32)
+        nstreams, nslots = iq.shape[:2]
+        assert iq.shape[2:] == (2, NSAMPLES)
+        state = np.zeros(nstreams, HINT_STATE_DTYPE) if state is None else np.array(state, HINT_STATE_DTYPE, copy=True, ndmin=1)
+        assert state.shape == (nstreams,)
+        if msgs is None:
+            msgs = np.zeros((nstreams, nslots, MAX_MESSAGES), MESSAGE_DTYPE)
+        assert msgs.dtype == MESSAGE_DTYPE and msgs.shape == (nstreams, nslots, MAX_MESSAGES) and msgs.flags["C_CONTIGUOUS"]
+        n = np.zeros((nstreams, nslots), np.int32)
+        nbs = np.zeros((nstreams, nslots, 2), np.int32)
+        p = HintParams(int(tries), int(max_bad_per_64), int(max_hard_errors), int(max_age), int(bool(use_phase)))
+        self._ck(self.lib.ft8gpu_decode_messages_hinted(self.h, iq.ctypes.data, nstreams, nslots, state.ctypes.data, C.byref(p),
+                                                        msgs.ctypes.data, n.ctypes.data, nbs.ctypes.data, HOST_PTRS))
+        return msgs, n, nbs, state
+
+    def decode_messages_hinted_dev(self, iq_dev, nstreams, nslots, state_dev, tries, max_bad_per_64, max_hard_errors, max_age, use_phase,
+                                   msgs_dev, n_msgs_dev, n_by_stage_dev=None):
+        """the same with every array in HBM (iq, msgs and state 16-byte aligned); n_by_stage_dev: [nstreams][nslots][2] or None"""
+        p = HintParams(int(tries), int(max_bad_per_64), int(max_hard_errors), int(max_age), int(bool(use_phase)))
+        self._ck(self.lib.ft8gpu_decode_messages_hinted(self.h, _ptr(iq_dev), nstreams, nslots, _ptr(state_dev), C.byref(p),
+                                                        _ptr(msgs_dev), _ptr(n_msgs_dev),
+                                                        None if n_by_stage_dev is None else _ptr(n_by_stage_dev), DEVICE_PTRS))
 
     def combine_candidates(self, mag, cands, counts, status_in, states, max_age=0, min_agree=COMBINE_MIN_AGREE,
                            status_out=None, info=None):

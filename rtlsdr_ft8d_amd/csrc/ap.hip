@@ -82,6 +82,8 @@ void ft8_ap_kernel(const uint8_t *__restrict__ mag, const ft8gpu_candidate *__re
 
     for (int k = 0; k < nhyp; ++k) {                                  // wave-uniform
         const uint64_t m0 = hyps.mask[k][0], m1 = hyps.mask[k][1], b0 = hyps.bits[k][0], b1 = hyps.bits[k][1];
+        // (These lines, down to the judgement, exist a second time as cand_dev.h's ap_try, which hint.hip calls: change both.
+        // tests/test_gpu_hint.py holds the hint stage to this kernel candidate by candidate.)
         // ---- the hypothesis's soft bits: +-apmag on the masked positions ------------------------------------------------
         float cw[3];
         {

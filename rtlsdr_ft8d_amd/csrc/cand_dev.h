@@ -667,6 +667,36 @@ __device__ __forceinline__ int judge_bp_word(const BpWord &bp, uint64_t X0, uint
     return judge_word(bp.B0, bp.B1, bp.B2, nhard, max_hard_errors, dw0, crc_bit, rec32, lane);   // (BP leaves at an all-zero word unchecked)
 }
 
+// One a-priori hypothesis on a candidate (ap.hip, hint.hip; include/ft8gpu.h "a-priori decoding"): the masked positions
+// (m0, m1 over codeword positions 0..63 and 64..127, bits b0, b1) become +-apmag, BP runs on the result, and the word it
+// leaves is judged against the candidate's hard decisions (H0, H1, H2) -- 7 no codeword, 8 it differs from the hypothesis on a
+// masked position, then judge_word on the hard errors of the unmasked positions.  The record of an accepted word is composed
+// in rec32.  Wave-uniform arguments but cw0 / has; returns the result code.
+// (ap.hip carries these lines written out in its loop: called from there, the routine gives the same results but moves the
+// kernel's blocks and registers, and ft8_ap_kernel is kept instruction for instruction what it was.)
+__device__ __forceinline__ int ap_try(const float (&cw0)[3], const bool (&has)[3], uint64_t has2_mask, float *toc, const LdpcLane &L,
+                                      int lane, int max_iters, int force_ieee_div, float apmag, uint64_t m0, uint64_t m1, uint64_t b0,
+                                      uint64_t b1, uint64_t H0, uint64_t H1, uint64_t H2, int max_hard_errors, uint32_t dw0,
+                                      const uint16_t *crc_bit, uint32_t *rec32, int &nhard, int &iters_out) {
+    float cw[3];
+    {
+        const bool f0 = ((m0 >> lane) & 1ull) != 0ull, f1 = ((m1 >> lane) & 1ull) != 0ull;
+        cw[0] = f0 ? (((b0 >> lane) & 1ull) ? apmag : -apmag) : cw0[0];
+        cw[1] = f1 ? (((b1 >> lane) & 1ull) ? apmag : -apmag) : cw0[1];
+        cw[2] = cw0[2];
+    }
+    const BpWord bp = bp_decode_counting(cw, has, has2_mask, toc, L, lane, max_iters, force_ieee_div);
+    const uint64_t B0 = bp.B0, B1 = bp.B1, B2 = bp.B2;
+    iters_out = bp.iter < 255 ? bp.iter : 255;
+    // hard errors: unmasked positions at which the word differs from h (the mask covers payload positions only)
+    nhard = __popcll((B0 ^ H0) & ~m0) + __popcll((B1 ^ H1) & ~m1) + __popcll(B2 ^ H2);
+    int result;
+    if (bp.min_errors != 0) result = 7;
+    else if ((((B0 ^ b0) & m0) | ((B1 ^ b1) & m1)) != 0ull) result = 8;
+    else result = judge_word(B0, B1, B2, nhard, max_hard_errors, dw0, crc_bit, rec32, lane);
+    return result;
+}
+
 // ---- launch geometry and the tags of what a stage gained ----------------------------------------------------------------
 // one workgroup per 4 candidates: bpf blocks (of 4 candidate waves) per frame, frame after frame.  mul_high: ap.hip's
 // tighter bound, which keeps its multiply-high division exact.

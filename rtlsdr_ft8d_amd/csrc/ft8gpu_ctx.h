@@ -87,6 +87,7 @@ struct ft8gpu_ctx {
     int32_t *d_nap = nullptr;              //   the counts before the AP append [max_frames]
     bool combine_tables = false;           // soft-bit memory: the constant tables are uploaded (on its first call)
     bool demod_tables = false;             // demodulation from the I/Q samples: likewise
+    bool hint_tables = false;              // call hints: likewise
     struct SubTables *d_subtab = nullptr;  // subtraction in the I/Q samples, lazily on its first call: the constant tables,
     uint32_t *d_sub_scratch = nullptr;     //   what the estimate kernel leaves for the apply kernel [sub_frames][50][2560],
     int sub_frames = 0;

@@ -44,7 +44,8 @@ struct Ft8Tables {                 // device-resident constant tables, built on 
 #define FT8GPU_AB_WATERFALL_LDS        8u   /* last FFT stage: second exchange through LDS instead of register transposes across the wave's rows */
 #define FT8GPU_AB_HEAP_LANE_PER_FRAME 16u   /* heap replay: one lane per frame for every launch the cap allows (<= 128) */
 #define FT8GPU_AB_HEAP_WAVE_PER_FRAME 32u   /* heap replay: one wave per frame for every launch */
-constexpr unsigned kDbgAccepted = FT8GPU_DBG_ALL | 56u;
+#define FT8GPU_AB_HINT_IN_WAVE        64u   /* call hints: no pre-kernel, the table entries are converted in the wave (hint.hip) */
+constexpr unsigned kDbgAccepted = FT8GPU_DBG_ALL | 120u;
 #else
 constexpr unsigned kDbgAccepted = FT8GPU_DBG_ALL;
 #endif
