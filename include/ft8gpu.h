@@ -1654,6 +1654,92 @@ int ft8gpu_synth_gfsk_audio(ft8gpu_ctx *ctx, const ft8gpu_synth_signal *signals,
  * (a line on stderr says why). */
 int ft8gpu_write_wav(const char *path, const int16_t *pcm, int32_t nsamples);
 
+/* ---- Fading channel: the GFSK signal over one or two Rayleigh-fading HF paths ----------------------------------------------------
+ * (DESIGN.md "Fading channel"; tests/ft8_spec_channel.py restates the rule and the device output at noise_sigma == 0 equals that
+ * byte for byte.)  An ft8gpu_channel per signal, parallel to the ft8gpu_synth_signal array, gives every path of the signal a
+ * complex gain that varies in time with a Gaussian Doppler spectrum, and an optional second path a delay.  The rule is exact in
+ * the sense of "GFSK synthesis": integer phases, float32, one IEEE operation per step, nothing fused, sums sequential from +0.
+ *
+ * Gain process.  A (signal, path) has M = 16 sinusoids, evaluated on a grid of 100 points per second and interpolated linearly
+ *   between them.  The grid step is S = 32 samples in the I/Q mode and S = 120 in the audio mode, so both modes have the same
+ *   grid in time; a signal of 79 sps samples spans 1264 steps, grid points 0 .. 1264.
+ * Taps (ft8gpu_channel_taps, host, plain C, no libm but the exact llrint).  q_m = FT8GPU_CHANNEL_QUANTILES[m], the standard normal
+ *   quantile at (m + 0.5) / 16;  f_m = ((double)spread_hz / 2.0) * q_m  (spread_hz is two sigma of the Doppler spectrum);
+ *     gstep_m = (uint32_t)(int64_t)llrint(f_m / 100.0 * 4294967296.0)      -- turns per grid step in units of 2^-32; negative wraps
+ *     theta_m = (uint32_t)(mix(mix(seed ^ 0x4641444531) ^ mix((clip << 12) + (signal << 5) + (path << 4) + m)) >> 32)
+ *   in uint64 arithmetic; clip is the global clip index (first_* + the clip's index in the call), signal the signal's index in
+ *   its clip, path 0 or 1, and mix is splitmix64's step:
+ *     mix(x): x += 0x9E3779B97F4A7C15; x = (x ^ (x >> 30)) * 0xBF58476D1CE4E5B9; x = (x ^ (x >> 27)) * 0x94D049BB133111EB; x ^ (x >> 31).
+ * Path amplitudes (host).  g2 = path2_gain;  r = sqrtf(1.0f + g2 * g2);  w_0 = 1.0f / r;  w_1 = g2 / r: the mean power of a faded
+ *   signal is that of the unfaded one.  With g2 == 0 there is no second path (it is skipped, not added as zeros).
+ * Grid value of path p at grid point j, with gc and gf of "GFSK synthesis":  ph = theta_m + gstep_m * j in wrapping uint32
+ *   arithmetic, ic = ph >> 20, jf = (ph >> 8) & 4095,
+ *     co_m = gc[ic].c * gf[jf].c - gc[ic].s * gf[jf].s;   si_m = gc[ic].s * gf[jf].c + gc[ic].c * gf[jf].s     (as the carrier's)
+ *     G[j] = w_p * (0.25f * (co_0 + co_1 + ... + co_15)),  the same with si:  each sum sequential from +0 in the order of m, then
+ *   the product by 0.25f, then the product by w_p.
+ * Per sample.  For the local sample n' in [0, 79 sps) of a path:  j = n' div S, k = n' mod S, t = (float)k / (float)S,
+ *     Gr = G[j].c + (G[j + 1].c - G[j].c) * t,  Gi the same with .s    (a subtraction, a product, an addition)
+ *   xr = a * co, xi = a * si are the unfaded rule's contribution at n' (a = amplitude * env(n')).  The path contributes
+ *     re = xr * Gr - xi * Gi;   im = xr * Gi + xi * Gr            (two products, then one subtraction or addition)
+ *   to output sample start + n' (path 0) or start + d + n' (path 1),  d = lrintf(delay_ms * (float)rate / 1000.0f), left to
+ *   right, where that lies inside the clip: a path is cut at the clip's ends as a signal is.  Path 1 is the same waveform with
+ *   its own taps.  The audio mode keeps re.
+ * Output sample.  Signals are added in signal order from +0, within a signal path 0 before path 1.  A signal whose channel has
+ *   mode == 0 is added by the unfaded rule, byte for byte, and its other fields are not looked at.  Noise, peak normalisation and
+ *   the int16 form follow as in "GFSK synthesis"; the noise stays outside the exact contract.  spread_hz == 0 is no special
+ *   case: every gstep is 0 and the gain is one constant Rayleigh draw per path (block fading).
+ * Refused before anything is enqueued, for a channel with mode == 1: a field that is not finite, spread_hz outside [0, 20],
+ *   delay_ms outside [0, 10], path2_gain outside [0, 4]; for any channel: mode > 1. */
+typedef struct {
+    float    spread_hz;   /* two-sided Doppler spread (2 sigma of a Gaussian Doppler spectrum) of each path, [0, 20] */
+    float    delay_ms;    /* delay of the second path, [0, 10] */
+    float    path2_gain;  /* amplitude of path 2 relative to path 1, [0, 4]; 0 = one path */
+    uint32_t mode;        /* 0 = none: the signal is synthesised by the unfaded rule, byte for byte; 1 = faded */
+} ft8gpu_channel;
+#ifndef __cplusplus
+_Static_assert(sizeof(ft8gpu_channel) == 16 && offsetof(ft8gpu_channel, delay_ms) == 4 && offsetof(ft8gpu_channel, path2_gain) == 8 &&
+               offsetof(ft8gpu_channel, mode) == 12, "ft8gpu_channel layout");
+#else
+static_assert(sizeof(ft8gpu_channel) == 16 && offsetof(ft8gpu_channel, delay_ms) == 4 && offsetof(ft8gpu_channel, path2_gain) == 8 &&
+              offsetof(ft8gpu_channel, mode) == 12, "ft8gpu_channel layout");
+#endif
+#define FT8GPU_CHANNEL_NONE    0u
+#define FT8GPU_CHANNEL_FADED   1u
+#define FT8GPU_CHANNEL_TAPS    16      /* M */
+#define FT8GPU_CHANNEL_STEP_IQ     32  /* S: samples per grid step */
+#define FT8GPU_CHANNEL_STEP_AUDIO  120
+#define FT8GPU_CHANNEL_GRID    1265    /* grid points of one path: 79 sps / S + 1 */
+/* the standard normal quantiles at (m + 0.5) / 16, m = 0 .. 15, to 15 decimals */
+#define FT8GPU_CHANNEL_QUANTILES { \
+    -1.862731867421651, -1.318010897303537, -1.009990169249582, -0.776421761147928, -0.579132162255556, -0.402250065321725, \
+    -0.237202109328788, -0.078412412733112,  0.078412412733112,  0.237202109328788,  0.402250065321725,  0.579132162255556, \
+     0.776421761147928,  1.009990169249582,  1.318010897303537,  1.862731867421651 }
+/* initialisers for the usual HF conditions (spread / delay, two equal paths); conveniences, not part of the rule */
+#define FT8GPU_CHANNEL_QUIET     { 0.1f, 0.5f, 1.0f, FT8GPU_CHANNEL_FADED }
+#define FT8GPU_CHANNEL_MODERATE  { 0.5f, 1.0f, 1.0f, FT8GPU_CHANNEL_FADED }
+#define FT8GPU_CHANNEL_DISTURBED { 1.0f, 2.0f, 1.0f, FT8GPU_CHANNEL_FADED }
+#define FT8GPU_CHANNEL_FLUTTER   { 10.0f, 0.5f, 1.0f, FT8GPU_CHANNEL_FADED }
+/* gstep[16], theta[16] of one (signal, path); either may be NULL.  0 = ok, -1 = spread_hz outside [0, 20] or not finite, or
+ * path outside {0, 1} */
+int ft8gpu_channel_taps(uint64_t seed, uint64_t clip, uint32_t signal, uint32_t path, float spread_hz, uint32_t *gstep, uint32_t *theta);
+/* 0 if the entries below take the channel; else which field they refuse: 1 spread_hz, 2 delay_ms, 3 path2_gain, 4 mode */
+int ft8gpu_channel_check(const ft8gpu_channel *ch);
+/* The rule on the host, plain C, for one clip: signals [nsig] and channels [nsig] (NULL: all unfaded) -> out, the sum before
+ * noise and normalisation, [2][48000] floats (FT8GPU_GFSK_IQ; nsamples is ignored) or [nsamples] (FT8GPU_GFSK_AUDIO).  `clip`
+ * is the global clip index.  0 = ok, -1 = an argument the entries below refuse, or out of memory for the tables. */
+int ft8gpu_channel_clip(int mode, const ft8gpu_synth_signal *signals, const ft8gpu_channel *channels, int nsig, int nsamples,
+                        uint64_t seed, uint64_t clip, float *out);
+/* ft8gpu_synth_gfsk_frames / _audio with channels, a host array [n][nsig] parallel to signals in both pointer forms.  channels ==
+ * NULL is the unfaded entry; a call whose channels all have mode 0 gives its bytes, noise included.  The taps are keyed by seed
+ * (the noise's) and the global clip index, so any chunking and any partition of a job by first_* gives the same clips.  The grid
+ * values take 2 * 1265 * 8 bytes of device memory per signal of a chunk, allocated when first needed and freed at ft8gpu_destroy. */
+int ft8gpu_synth_gfsk_frames_faded(ft8gpu_ctx *ctx, const ft8gpu_synth_signal *signals, const ft8gpu_channel *channels, int nframes,
+                                   int nsig_per_frame, float noise_sigma, uint64_t seed, uint64_t first_frame, float peak,
+                                   float *iq_out, int flags);
+int ft8gpu_synth_gfsk_audio_faded(ft8gpu_ctx *ctx, const ft8gpu_synth_signal *signals, const ft8gpu_channel *channels, int nclips,
+                                  int nsig_per_clip, int nsamples, float noise_sigma, uint64_t seed, uint64_t first_clip, float peak,
+                                  int format, void *pcm_out, int flags);
+
 /* ---- RX front end: rtlsdr_callback(), rtlsdr_ft8d.c:76-202 ------------
  * Whole raw RTL-SDR captures (unsigned 8-bit I,Q interleaved at 2.4 Msps) -> the 15 s / ~3200 sps
  * float frames the decoder consumes: fs/4 mixer, CIC (N = 2, comb delay 2, effective ratio 751),

@@ -123,6 +123,14 @@ GFSK_SPS_IQ, GFSK_SPS_AUDIO = 512, 1920   # FT8GPU_GFSK_SPS_IQ / _AUDIO
 GFSK_TWIDDLES = 4096             # FT8GPU_GFSK_TWIDDLES
 GFSK_MAX_SIGNALS = 64            # FT8GPU_GFSK_MAX_SIGNALS
 GFSK_TILE = 8192                 # FT8GPU_GFSK_TILE: output samples per workgroup of the kernel as built
+# ft8gpu_channel (16 bytes): a signal's fading channel, parallel to SIGNAL_DTYPE records (include/ft8gpu.h "Fading channel")
+CHANNEL_DTYPE = np.dtype([("spread_hz", "<f4"), ("delay_ms", "<f4"), ("path2_gain", "<f4"), ("mode", "<u4")])
+assert CHANNEL_DTYPE.itemsize == 16
+CHANNEL_NONE, CHANNEL_FADED = 0, 1   # FT8GPU_CHANNEL_NONE / _FADED
+CHANNEL_TAPS = 16                # FT8GPU_CHANNEL_TAPS
+CHANNEL_GRID = 1265              # FT8GPU_CHANNEL_GRID
+# FT8GPU_CHANNEL_QUIET / _MODERATE / _DISTURBED / _FLUTTER: (spread_hz, delay_ms, path2_gain, mode)
+CHANNEL_PRESETS = {"quiet": (0.1, 0.5, 1.0, 1), "moderate": (0.5, 1.0, 1.0, 1), "disturbed": (1.0, 2.0, 1.0, 1), "flutter": (10.0, 0.5, 1.0, 1)}
 assert DEMOD_INFO_DTYPE.itemsize == 16
 
 
@@ -223,6 +231,7 @@ ABI_SYMBOLS = [
     "ft8gpu_audio_taps", "ft8gpu_audio_mixer", "ft8gpu_audio_frames", "ft8gpu_decode_audio", "ft8gpu_read_wav",
     "ft8gpu_gfsk_pulse", "ft8gpu_gfsk_ramp", "ft8gpu_gfsk_twiddles", "ft8gpu_synth_gfsk_frames", "ft8gpu_synth_gfsk_audio",
     "ft8gpu_write_wav",
+    "ft8gpu_channel_taps", "ft8gpu_channel_check", "ft8gpu_channel_clip", "ft8gpu_synth_gfsk_frames_faded", "ft8gpu_synth_gfsk_audio_faded",
     "ft8gpu_wide_mixer1", "ft8gpu_wide_mixer2", "ft8gpu_wide_taps", "ft8gpu_wide_frames", "ft8gpu_decode_wide",
     "ft8gpu_pcm_decimation", "ft8gpu_pcm_mixer1", "ft8gpu_pcm_mixer2", "ft8gpu_pcm_taps_a", "ft8gpu_pcm_taps_b", "ft8gpu_pcm_frames",
     "ft8gpu_decode_pcm", "ft8gpu_read_wav_pcm",
@@ -429,6 +438,13 @@ def _declare(L):
         L.ft8gpu_synth_gfsk_audio.argtypes = [vp, vp, C.c_int, C.c_int, C.c_int, C.c_float, C.c_uint64, C.c_uint64, C.c_float, C.c_int,
                                               vp, C.c_int]
         L.ft8gpu_write_wav.argtypes = [C.c_char_p, vp, C.c_int32]
+    if hasattr(L, "ft8gpu_synth_gfsk_frames_faded"):      # absent from older builds loaded by load_library_at
+        L.ft8gpu_channel_taps.argtypes = [C.c_uint64, C.c_uint64, C.c_uint32, C.c_uint32, C.c_float, vp, vp]
+        L.ft8gpu_channel_check.argtypes = [vp]
+        L.ft8gpu_channel_clip.argtypes = [C.c_int, vp, vp, C.c_int, C.c_int, C.c_uint64, C.c_uint64, vp]
+        L.ft8gpu_synth_gfsk_frames_faded.argtypes = [vp, vp, vp, C.c_int, C.c_int, C.c_float, C.c_uint64, C.c_uint64, C.c_float, vp, C.c_int]
+        L.ft8gpu_synth_gfsk_audio_faded.argtypes = [vp, vp, vp, C.c_int, C.c_int, C.c_int, C.c_float, C.c_uint64, C.c_uint64, C.c_float,
+                                                    C.c_int, vp, C.c_int]
     if hasattr(L, "ft8gpu_wide_frames"):                  # absent from older builds loaded by load_library_at
         for f in (L.ft8gpu_wide_mixer1, L.ft8gpu_wide_mixer2, L.ft8gpu_wide_taps):
             f.argtypes = [vp]
@@ -1691,6 +1707,51 @@ class Decoder:
         self._ck(self.lib.ft8gpu_synth_gfsk_audio(self.h, signals.ctypes.data, int(nclips), int(nsig), int(nsamples), float(noise_sigma),
                                                 int(seed), int(first_clip), float(peak), int(fmt), _ptr(pcm_out_dev), DEVICE_PTRS))
 
+    @staticmethod
+    def _gfsk_channels(channels, nclips, nsig):
+        """None (the unfaded entries) or CHANNEL_DTYPE [nclips][nsig] -> the pointer the faded entries take"""
+        if channels is None:
+            return None, None
+        channels = np.ascontiguousarray(channels)
+        assert channels.dtype == CHANNEL_DTYPE and channels.size == nclips * nsig
+        return channels, channels.ctypes.data
+
+    def synth_gfsk_frames_faded(self, signals, channels, nframes, nsig, noise_sigma=0.0, seed=0, first_frame=0, peak=0.0):
+        """ft8gpu_synth_gfsk_frames_faded: synth_gfsk_frames with channels [nframes][nsig] of CHANNEL_DTYPE (None: unfaded); the
+        taps are keyed by seed and the global frame index"""
+        signals = self._gfsk_signals(signals, nframes, nsig)
+        channels, cp = self._gfsk_channels(channels, nframes, nsig)
+        out = np.zeros((nframes, 2, NSAMPLES), np.float32)
+        self._ck(self.lib.ft8gpu_synth_gfsk_frames_faded(self.h, signals.ctypes.data, cp, int(nframes), int(nsig), float(noise_sigma),
+                                                       int(seed), int(first_frame), float(peak), out.ctypes.data, HOST_PTRS))
+        return out
+
+    def synth_gfsk_frames_faded_dev(self, signals, channels, nframes, nsig, noise_sigma, seed, first_frame, peak, iq_out_dev):
+        """iq_out_dev [nframes][2][48000] float32 in HBM; signals and channels stay on the host"""
+        signals = self._gfsk_signals(signals, nframes, nsig)
+        channels, cp = self._gfsk_channels(channels, nframes, nsig)
+        self._ck(self.lib.ft8gpu_synth_gfsk_frames_faded(self.h, signals.ctypes.data, cp, int(nframes), int(nsig), float(noise_sigma),
+                                                       int(seed), int(first_frame), float(peak), _ptr(iq_out_dev), DEVICE_PTRS))
+
+    def synth_gfsk_audio_faded(self, signals, channels, nclips, nsig, nsamples=AUDIO_NSAMPLES, noise_sigma=0.0, seed=0, first_clip=0,
+                               peak=0.0, fmt=AUDIO_F32):
+        """ft8gpu_synth_gfsk_audio_faded: synth_gfsk_audio with channels [nclips][nsig] of CHANNEL_DTYPE (None: unfaded)"""
+        signals = self._gfsk_signals(signals, nclips, nsig)
+        channels, cp = self._gfsk_channels(channels, nclips, nsig)
+        out = np.zeros((nclips, max(int(nsamples), 0)), np.int16 if fmt == AUDIO_S16 else np.float32)
+        self._ck(self.lib.ft8gpu_synth_gfsk_audio_faded(self.h, signals.ctypes.data, cp, int(nclips), int(nsig), int(nsamples),
+                                                      float(noise_sigma), int(seed), int(first_clip), float(peak), int(fmt),
+                                                      out.ctypes.data, HOST_PTRS))
+        return out
+
+    def synth_gfsk_audio_faded_dev(self, signals, channels, nclips, nsig, nsamples, noise_sigma, seed, first_clip, peak, fmt, pcm_out_dev):
+        """pcm_out_dev [nclips][nsamples] of fmt in HBM; signals and channels stay on the host"""
+        signals = self._gfsk_signals(signals, nclips, nsig)
+        channels, cp = self._gfsk_channels(channels, nclips, nsig)
+        self._ck(self.lib.ft8gpu_synth_gfsk_audio_faded(self.h, signals.ctypes.data, cp, int(nclips), int(nsig), int(nsamples),
+                                                      float(noise_sigma), int(seed), int(first_clip), float(peak), int(fmt),
+                                                      _ptr(pcm_out_dev), DEVICE_PTRS))
+
     # ---- device memory helpers of the C ABI (a plain C caller has no HIP headers) ---------------
     def dev_alloc(self, nbytes):
         p = self.lib.ft8gpu_dev_alloc(self.h, nbytes)
@@ -1960,6 +2021,38 @@ def gfsk_twiddles():
     gc, gf = np.zeros((GFSK_TWIDDLES, 2), np.float32), np.zeros((GFSK_TWIDDLES, 2), np.float32)
     load_library().ft8gpu_gfsk_twiddles(gc.ctypes.data, gf.ctypes.data)
     return gc, gf
+
+
+def channel_preset(name, shape=()):
+    """CHANNEL_DTYPE records of one of the presets "quiet", "moderate", "disturbed", "flutter" (FT8GPU_CHANNEL_*), or "none" """
+    out = np.zeros(shape, CHANNEL_DTYPE)
+    if name != "none":
+        out["spread_hz"], out["delay_ms"], out["path2_gain"], out["mode"] = CHANNEL_PRESETS[name]
+    return out
+
+
+def channel_taps(seed, clip, signal, path, spread_hz):
+    """ft8gpu_channel_taps: (gstep, theta), uint32 [16] each, of one (signal, path) of global clip `clip` """
+    gstep, theta = np.zeros(CHANNEL_TAPS, np.uint32), np.zeros(CHANNEL_TAPS, np.uint32)
+    if load_library().ft8gpu_channel_taps(int(seed), int(clip), int(signal), int(path), float(spread_hz), gstep.ctypes.data, theta.ctypes.data) != 0:
+        raise Ft8GpuError(f"channel_taps: spread_hz {spread_hz} outside [0, 20] or path {path} outside (0, 1)")
+    return gstep, theta
+
+
+def channel_clip(mode, signals, channels, nsamples=AUDIO_NSAMPLES, seed=0, clip=0):
+    """ft8gpu_channel_clip: the fading rule on the host for one clip, before noise and normalisation: signals [nsig] of
+    SIGNAL_DTYPE, channels [nsig] of CHANNEL_DTYPE or None -> float32 [2][48000] (GFSK_IQ) or [nsamples] (GFSK_AUDIO)"""
+    signals = np.ascontiguousarray(signals).reshape(-1)
+    assert signals.dtype == SIGNAL_DTYPE
+    cp = None
+    if channels is not None:
+        channels = np.ascontiguousarray(channels).reshape(-1)
+        assert channels.dtype == CHANNEL_DTYPE and channels.size == signals.size
+        cp = channels.ctypes.data
+    out = np.zeros((2, NSAMPLES) if mode == GFSK_IQ else max(int(nsamples), 1), np.float32)
+    if load_library().ft8gpu_channel_clip(int(mode), signals.ctypes.data, cp, signals.size, int(nsamples), int(seed), int(clip), out.ctypes.data) != 0:
+        raise Ft8GpuError("channel_clip: an argument the synthesiser's entries refuse")
+    return out
 
 
 def write_wav(path, pcm):

@@ -5,10 +5,15 @@
 // on the host, and cut the clips with for_each_chunk.  With peak == 0 the kernel writes the caller's format directly; otherwise
 // it writes floats (into the output itself where that holds floats) and leaves the tiles' maxima, and a second launch scales.
 // Everything here is allocated on the first GFSK call, so ft8gpu_create's footprint is unchanged.
+// With channels ("Fading channel") of which at least one is faded, the host also derives the taps, delays and path amplitudes,
+// and every chunk gets a launch that fills its paths' grid values in front of the faded kernel; a call without a faded signal is
+// the unfaded one.
 #include "gfsk.h"
 #include "ft8gpu_ctx.h"
 
 #include <math.h>
+#include <string.h>
+#include <algorithm>
 #include <vector>
 
 namespace {
@@ -27,8 +32,9 @@ int ensure_gfsk_tables(ft8gpu_ctx *c) {
 }
 
 // the refusals of both entries; on success hdr holds the nclips * nsig headers
-int check_gfsk_args(int mode, const ft8gpu_synth_signal *signals, int nclips, int nsig, int nsamples, float noise_sigma, float peak,
-                    int format, std::vector<GfskHeader> *hdr) {
+int check_gfsk_args(int mode, const ft8gpu_synth_signal *signals, const ft8gpu_channel *channels, int nclips, int nsig, int nsamples,
+                    float noise_sigma, uint64_t seed, uint64_t first, float peak, int format, std::vector<GfskHeader> *hdr,
+                    std::vector<GfskChannel> *chs) {
     const int rate = mode == FT8GPU_GFSK_IQ ? 3200 : FT8GPU_AUDIO_RATE;
     if (format != FT8GPU_AUDIO_S16 && format != FT8GPU_AUDIO_F32) return ft8_fail("unknown audio format %d", format);
     if (nsamples < 1 || nsamples > FT8GPU_AUDIO_NSAMPLES)
@@ -62,13 +68,43 @@ int check_gfsk_args(int mode, const ft8gpu_synth_signal *signals, int nclips, in
         h.e[80] = sg.tones[FT8GPU_NN - 1];
         h.e[81] = h.e[82] = h.e[83] = 0;
     }
+    if (!channels) return 0;
+    bool faded = false;
+    for (size_t g = 0; g < total; ++g) {
+        const ft8gpu_channel &ch = channels[g];
+        const int clip = (int)(g / nsig), s = (int)(g % nsig);
+        switch (ft8gpu_channel_check(&ch)) {
+        case 1: return ft8_fail("channel of signal %d of clip %d: spread_hz %g out of range [0, 20] or not finite", s, clip, (double)ch.spread_hz);
+        case 2: return ft8_fail("channel of signal %d of clip %d: delay_ms %g out of range [0, 10] or not finite", s, clip, (double)ch.delay_ms);
+        case 3: return ft8_fail("channel of signal %d of clip %d: path2_gain %g out of range [0, 4] or not finite", s, clip, (double)ch.path2_gain);
+        case 4: return ft8_fail("channel of signal %d of clip %d: unknown mode %u", s, clip, (unsigned)ch.mode);
+        }
+        faded = faded || ch.mode == FT8GPU_CHANNEL_FADED;
+    }
+    if (!faded) return 0;                                   // all unfaded: the unfaded entry
+    chs->resize(total);
+    for (size_t g = 0; g < total; ++g) {
+        const ft8gpu_channel &ch = channels[g];
+        GfskChannel &k = (*chs)[g];
+        memset(&k, 0, sizeof k);
+        if (ch.mode != FT8GPU_CHANNEL_FADED) continue;
+        const float g2 = ch.path2_gain, r = sqrtf(1.0f + g2 * g2);
+        k.w[0] = 1.0f / r;
+        k.w[1] = g2 / r;
+        k.d = (int32_t)lrintf(ch.delay_ms * (float)rate / 1000.0f);
+        k.paths = g2 == 0.0f ? 1u : 2u;
+        for (uint32_t p = 0; p < k.paths; ++p)
+            ft8gpu_channel_taps(seed, first + (uint64_t)(g / nsig), (uint32_t)(g % nsig), p, ch.spread_hz, k.gstep[p], k.theta[p]);
+    }
     return 0;
 }
 
-int synth_gfsk(ft8gpu_ctx *c, int mode, const ft8gpu_synth_signal *signals, int nclips, int nsig, int nsamples, float noise_sigma,
-               uint64_t seed, uint64_t first, float peak, int format, void *out, int flags) {
+int synth_gfsk(ft8gpu_ctx *c, int mode, const ft8gpu_synth_signal *signals, const ft8gpu_channel *channels, int nclips, int nsig,
+               int nsamples, float noise_sigma, uint64_t seed, uint64_t first, float peak, int format, void *out, int flags) {
     std::vector<GfskHeader> hdr;
-    if (nclips >= 0 && check_gfsk_args(mode, signals, nclips, nsig, nsamples, noise_sigma, peak, format, &hdr)) return -1;
+    std::vector<GfskChannel> chs;                           // empty: no signal of the call is faded
+    if (nclips >= 0 && check_gfsk_args(mode, signals, channels, nclips, nsig, nsamples, noise_sigma, seed, first, peak, format, &hdr, &chs))
+        return -1;
     CHECK_COMMON(c, nclips);
     if (nclips == 0) return 0;
     if (!out) return ft8_fail("NULL array argument");
@@ -86,20 +122,33 @@ int synth_gfsk(ft8gpu_ctx *c, int mode, const ft8gpu_synth_signal *signals, int 
     if (!hdr.empty()) {
         if (c->mem.grow(&c->d_gfsk_hdr, &c->gfsk_hdr_cap, hdr.size() * sizeof(GfskHeader), "the GFSK signal headers")) return -1;
         HIP_TRY(hipMemcpyAsync(c->d_gfsk_hdr, hdr.data(), hdr.size() * sizeof(GfskHeader), hipMemcpyHostToDevice, c->stream));
-        HIP_TRY(hipStreamSynchronize(c->stream));           // hdr is gone when this call returns
+        if (!chs.empty()) {
+            const size_t per_clip = (size_t)nsig * 2 * kGfskGrid * sizeof(float2);
+            if (c->mem.grow(&c->d_gfsk_ch, &c->gfsk_ch_cap, chs.size() * sizeof(GfskChannel), "the GFSK channel headers")) return -1;
+            if (c->mem.grow(&c->d_gfsk_grid, &c->gfsk_grid_cap, std::min((size_t)nclips, mf) * per_clip, "the GFSK channels' grid values")) return -1;
+            HIP_TRY(hipMemcpyAsync(c->d_gfsk_ch, chs.data(), chs.size() * sizeof(GfskChannel), hipMemcpyHostToDevice, c->stream));
+        }
+        HIP_TRY(hipStreamSynchronize(c->stream));           // hdr and chs are gone when this call returns
     }
     const StageArg a[] = { { out, c->d_gfsk_out, out_bytes, kOut } };
     size_t done = 0;                                        // clips of the chunks before this one
     return for_each_chunk(c, nclips, flags & FT8GPU_DEVICE_PTRS, a, [&](int n, void *const *p) {
         const GfskHeader *h = c->d_gfsk_hdr + done * (size_t)nsig;
         const uint64_t g0 = first + (uint64_t)done;
+        const GfskChannel *k = chs.empty() ? nullptr : c->d_gfsk_ch + done * (size_t)nsig;
         done += (size_t)n;
+        if (k) HIP_TRY(launch_gfsk_grid(k, n, nsig, c->d_gfsktab, c->d_gfsk_grid, c->stream));
+        // one launch of either kernel: fmt and the maxima as the caller or the second pass wants them
+        auto launch = [&](int fmt, void *dst, float *tile_max) {
+            return k ? launch_gfsk_faded(mode, fmt, h, k, c->d_gfsk_grid, n, nsig, nsamples, c->d_gfsktab, noise_sigma, seed, g0, dst, tile_max, c->stream)
+                     : launch_gfsk(mode, fmt, h, n, nsig, nsamples, c->d_gfsktab, noise_sigma, seed, g0, dst, tile_max, c->stream);
+        };
         if (!(peak > 0.0f)) {
-            HIP_TRY(launch_gfsk(mode, format, h, n, nsig, nsamples, c->d_gfsktab, noise_sigma, seed, g0, p[0], nullptr, c->stream));
+            HIP_TRY(launch(format, p[0], nullptr));
             return 0;
         }
         float *x = format == FT8GPU_AUDIO_S16 ? c->d_gfsk_x : (float *)p[0];
-        HIP_TRY(launch_gfsk(mode, FT8GPU_AUDIO_F32, h, n, nsig, nsamples, c->d_gfsktab, noise_sigma, seed, g0, x, c->d_gfsk_max, c->stream));
+        HIP_TRY(launch(FT8GPU_AUDIO_F32, x, c->d_gfsk_max));
         HIP_TRY(launch_gfsk_normalise(format, x, c->d_gfsk_max, n, (int)len, ntiles, peak, p[0], c->stream));
         return 0;
     });
@@ -111,13 +160,25 @@ extern "C" {
 
 int ft8gpu_synth_gfsk_frames(ft8gpu_ctx *c, const ft8gpu_synth_signal *signals, int nframes, int nsig, float noise_sigma, uint64_t seed,
                              uint64_t first_frame, float peak, float *iq_out, int flags) {
-    return synth_gfsk(c, FT8GPU_GFSK_IQ, signals, nframes, nsig, kNSamples, noise_sigma, seed, first_frame, peak, FT8GPU_AUDIO_F32,
+    return synth_gfsk(c, FT8GPU_GFSK_IQ, signals, nullptr, nframes, nsig, kNSamples, noise_sigma, seed, first_frame, peak, FT8GPU_AUDIO_F32,
                       iq_out, flags);
 }
 
 int ft8gpu_synth_gfsk_audio(ft8gpu_ctx *c, const ft8gpu_synth_signal *signals, int nclips, int nsig, int nsamples, float noise_sigma,
                             uint64_t seed, uint64_t first_clip, float peak, int format, void *pcm_out, int flags) {
-    return synth_gfsk(c, FT8GPU_GFSK_AUDIO, signals, nclips, nsig, nsamples, noise_sigma, seed, first_clip, peak, format, pcm_out, flags);
+    return synth_gfsk(c, FT8GPU_GFSK_AUDIO, signals, nullptr, nclips, nsig, nsamples, noise_sigma, seed, first_clip, peak, format, pcm_out, flags);
+}
+
+int ft8gpu_synth_gfsk_frames_faded(ft8gpu_ctx *c, const ft8gpu_synth_signal *signals, const ft8gpu_channel *channels, int nframes, int nsig,
+                                   float noise_sigma, uint64_t seed, uint64_t first_frame, float peak, float *iq_out, int flags) {
+    return synth_gfsk(c, FT8GPU_GFSK_IQ, signals, channels, nframes, nsig, kNSamples, noise_sigma, seed, first_frame, peak, FT8GPU_AUDIO_F32,
+                      iq_out, flags);
+}
+
+int ft8gpu_synth_gfsk_audio_faded(ft8gpu_ctx *c, const ft8gpu_synth_signal *signals, const ft8gpu_channel *channels, int nclips, int nsig,
+                                  int nsamples, float noise_sigma, uint64_t seed, uint64_t first_clip, float peak, int format, void *pcm_out,
+                                  int flags) {
+    return synth_gfsk(c, FT8GPU_GFSK_AUDIO, signals, channels, nclips, nsig, nsamples, noise_sigma, seed, first_clip, peak, format, pcm_out, flags);
 }
 
 }  // extern "C"

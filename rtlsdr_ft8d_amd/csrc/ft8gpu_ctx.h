@@ -113,6 +113,9 @@ struct ft8gpu_ctx {
     struct GfskTables *d_gfsktab = nullptr;    // GFSK synthesiser, lazily on its first call: the constant tables,
     struct GfskHeader *d_gfsk_hdr = nullptr;   //   the signal headers of a call (grown as needed),
     size_t gfsk_hdr_cap = 0;
+    struct GfskChannel *d_gfsk_ch = nullptr;   //   with channels: the signals' channel headers of a call and the grid values
+    float2 *d_gfsk_grid = nullptr;             //   [chunk][nsig][2][1265] of a chunk's paths (both grown as needed),
+    size_t gfsk_ch_cap = 0, gfsk_grid_cap = 0;
     float *d_gfsk_x = nullptr;             //   the floats before normalisation where the output is int16 [max_frames][180000],
     void *d_gfsk_out = nullptr;            //   host-pointer staging of the output [max_frames][180000] floats (I/Q: [2][48000]),
     float *d_gfsk_max = nullptr;           //   and the tiles' maxima [max_frames][22]
