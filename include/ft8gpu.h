@@ -1337,10 +1337,95 @@ int ft8gpu_demod_candidates(ft8gpu_ctx *ctx, const float *iq, const ft8gpu_candi
  *   3. the append step of the multi-pass path adds, in candidate order, every unique gained message not yet among the frame's
  *      records, up to 50 in all; pad[3] of such a record is the accepted set (1 .. 3).
  * n_by_stage [nframes][2] (NULL: not written): the count after BP and after the stage.  Host or device pointers by `flags`
- * (device form: iq and msgs 16-byte aligned), chunked by max_frames.  Not composed with multi-pass, OSD, AP, matching or
- * combining: feeding these soft bits to those stages is left to a later change. */
+ * (device form: iq and msgs 16-byte aligned), chunked by max_frames.  Composed with AP on its own soft bits below
+ * (ft8gpu_decode_messages_demod_ap); not composed with multi-pass, OSD, matching, call hints or combining: feeding these soft
+ * bits to those stages is left to a later change, and ft8gpu_demod_soft's array is the interface they would use. */
 int ft8gpu_decode_messages_demod(ft8gpu_ctx *ctx, const float *iq, int nframes, const ft8gpu_demod_params *params,
                                  ft8gpu_message *msgs, int32_t *n_msgs, int32_t *n_by_stage, int flags);
+
+/* ---- a-priori decoding on the soft bits demodulated from the I/Q samples --------------------------------------------------------
+ * (DESIGN.md "A-priori decoding on the demodulated soft bits"; not in the reference.)  The demodulation above is the only stage
+ * that improves the soft bits themselves; ft8gpu_demod_soft hands them out, and ft8gpu_ap_soft_candidates runs the a-priori rule
+ * on them.  tests/ft8_spec_apsoft.py restates both, and the device output equals the restatement byte for byte.
+ *
+ * The soft-bit array: soft [nframes][max_candidates][3][FT8GPU_SOFT_STRIDE] float32, 2112 bytes per candidate; row n - 1 belongs
+ * to set n, elements 174 and 175 of a row are +0.
+ * ft8gpu_demod_soft is ft8gpu_demod_candidates with one more output: status_out and info are byte for byte those of
+ * ft8gpu_demod_candidates with the same arguments.  For every record below counts[f], row n - 1 holds x, the output of
+ * ftx_normalize_logl that set n's bp_decode ran on, where the candidate was attempted, set n is named in `sets`, no earlier set
+ * was accepted and the set's result is not 6 (the accepted set's own row is written too); every other row is 176 times +0
+ * (candidates not attempted, sets not named or not reached, non-finite sets).  Records at and behind the count keep the
+ * caller's bytes, in all three arrays.  Host or device pointers by `flags` (device form: iq and soft 16-byte aligned). */
+#define FT8GPU_SOFT_STRIDE 176
+int ft8gpu_demod_soft(ft8gpu_ctx *ctx, const float *iq, const ft8gpu_candidate *cands, const int32_t *counts,
+                      const ft8gpu_decode_status *status_in, int nframes, const ft8gpu_demod_params *params,
+                      ft8gpu_decode_status *status_out, ft8gpu_demod_info *info, float *soft, int flags);
+/* AP on a soft-bit array.  A candidate qualifies as for AP: ok == 0 and ldpc_errors != 0.  The sets named in `sets` (1 .. 7,
+ * bit n - 1 = set n) are walked in ascending n.  A row with a non-finite value among its 174, or with apmag = max |row[i]| == 0,
+ * is unusable: nothing is tried on it and its code is 6 (in results[n - 1][0]).  Within a usable row the hypotheses run in table
+ * order, each exactly by the per-hypothesis rule of ft8gpu_ap_candidates with llr = the row as it stands -- nothing is
+ * normalised again: forced positions at +-apmag, bp_decode(llr_k, ldpc_iters) bit-exact to the LDPC kernel's iteration, nhard
+ * on the unmasked positions against h = row > 0, and the codes 7, 8, 5, 2, 3, 4, 1 in that order.  The first accepted
+ * (set, hypothesis) ends the candidate, and the status record becomes that of a BP success as AP writes it; otherwise it is
+ * unchanged.  result, nhard, hyp, iters speak of the accepted (set, hypothesis) or of the last one tried, `set` names its set;
+ * if no set is usable, result = 6 and set = 0.  A candidate that does not qualify gets its record copied and an all-zero info
+ * record; records at and behind counts[f] are not touched.  status_out may be status_in.  Any contents of soft give defined
+ * output (elements 174 and 175 of a row are not read).  hyps [nhyp], always in host memory, are validated as
+ * ft8gpu_ap_candidates validates them; nhyp in [1, 4], max_hard_errors in [0, 174], ldpc_iters is the context's.  Host or
+ * device pointers by `flags` (device form: soft 16-byte aligned). */
+typedef struct {
+    uint8_t result;          /*  0  0 not attempted, 1 accepted, 2..5, 7, 8 as ft8gpu_ap_info, 6 no usable set */
+    uint8_t nhard, hyp, iters;   /* of (set, hyp) */
+    uint8_t set;             /*  4  1 .. 3: the accepted set, or the last one tried; 0 when none was */
+    uint8_t pad[3];          /*     zero */
+    uint8_t results[3][FT8GPU_AP_MAX_HYPOTHESES];   /*  8  the code of every (set, hypothesis) tried, 0 for the others;
+                                                            a set that is unusable has 6 in results[n-1][0] */
+} ft8gpu_apsoft_info;
+/* Recommended max_hard_errors, from profiles/demod_ap_gain.json (tools/demod_ap_gain.py, on the CPU with the oracle's stages and
+ * the restatements, on the rows of tools/demod_gain.py behind the demodulation at its recommended values; gates 20, 25, 30, 36,
+ * 40, 45, 50, 60, 174; "CQ ? ?" alone, and with three call hypotheses nobody on the air carries).  On the 96 CQ frames of 20
+ * stations (1046 of 1920 by BP, +120 by the demodulation, 4840 candidates still failing) AP on these soft bits gains 35, 48, 48,
+ * 49 planted messages at gates 20, 25, 30, 36 and 49 from there to 174.  One station per frame, 64 frames each, gained behind
+ * the demodulation at gate 36 and above: -23 dB 2, -22 dB 2 (demodulation 1), -21 dB 14 (10), -20 dB 11 (35, BP 6), -19 dB 8
+ * (41, BP 15: all 64 decoded), none needed from -18 dB; at 20 and 25 the -21 dB row gains 10 and 13.  No row accepts a message
+ * that was not on the air at any gate under either table -- not on the 96 noise frames (942 failing candidates) either -- so by
+ * the rule of FT8GPU_DEMOD_MAX_HARD_ERRORS the largest swept gate, 174 -- no gate -- is the recommended one: a gate only costs
+ * messages here, and what keeps a wrong word out is BP under the forced bits with the CRC and unpack77 behind it.  The three
+ * unrelated call hypotheses change no figure of the sweep. */
+#define FT8GPU_APSOFT_MAX_HARD_ERRORS 174
+int ft8gpu_ap_soft_candidates(ft8gpu_ctx *ctx, const float *soft, const int32_t *counts, const ft8gpu_decode_status *status_in,
+                              int nframes, int sets, const ft8gpu_ap_hypothesis *hyps, int nhyp, int max_hard_errors,
+                              ft8gpu_decode_status *status_out, ft8gpu_apsoft_info *info, int flags);
+/* The whole path over iq [nframes][2][48000]: steps 1 to 3 of ft8gpu_decode_messages_demod (through the kernel that writes the
+ * soft bits); then ft8gpu_ap_soft_candidates runs in place on the status records with sets = demod.sets, the append step adds
+ * its unique gained messages in candidate order, and pad[1] = 1 + the accepted hypothesis, pad[3] = the accepted set on them.
+ * n_by_stage [nframes][3] (NULL: not written): the count after BP, after the demodulation and after AP.  nhyp = 0: no AP --
+ * the messages, counts and first two columns of ft8gpu_decode_messages_demod, column 2 equal to column 1.  Chunked by
+ * max_frames; the soft array of a chunk (max_frames x max_candidates x 2112 bytes) is the context's, allocated on the first
+ * call with nhyp > 0 -- a failed allocation returns -1 with the error text and leaves the context usable. */
+typedef struct {
+    ft8gpu_demod_params demod;
+    int32_t nhyp;                   /* 0 (no AP) .. FT8GPU_AP_MAX_HYPOTHESES */
+    int32_t ap_max_hard_errors;     /* 0 .. 174; FT8GPU_APSOFT_MAX_HARD_ERRORS is the recommended value */
+    ft8gpu_ap_hypothesis hyps[FT8GPU_AP_MAX_HYPOTHESES];
+} ft8gpu_demod_ap_params;
+int ft8gpu_decode_messages_demod_ap(ft8gpu_ctx *ctx, const float *iq, int nframes, const ft8gpu_demod_ap_params *params,
+                                    ft8gpu_message *msgs, int32_t *n_msgs, int32_t *n_by_stage, int flags);
+#ifndef __cplusplus
+_Static_assert(sizeof(ft8gpu_apsoft_info) == 20 && offsetof(ft8gpu_apsoft_info, nhard) == 1 && offsetof(ft8gpu_apsoft_info, hyp) == 2 &&
+               offsetof(ft8gpu_apsoft_info, iters) == 3 && offsetof(ft8gpu_apsoft_info, set) == 4 &&
+               offsetof(ft8gpu_apsoft_info, pad) == 5 && offsetof(ft8gpu_apsoft_info, results) == 8, "ft8gpu_apsoft_info layout");
+_Static_assert(sizeof(ft8gpu_demod_ap_params) == 100 && offsetof(ft8gpu_demod_ap_params, nhyp) == 12 &&
+               offsetof(ft8gpu_demod_ap_params, ap_max_hard_errors) == 16 && offsetof(ft8gpu_demod_ap_params, hyps) == 20,
+               "ft8gpu_demod_ap_params layout");
+#else
+static_assert(sizeof(ft8gpu_apsoft_info) == 20 && offsetof(ft8gpu_apsoft_info, nhard) == 1 && offsetof(ft8gpu_apsoft_info, hyp) == 2 &&
+              offsetof(ft8gpu_apsoft_info, iters) == 3 && offsetof(ft8gpu_apsoft_info, set) == 4 &&
+              offsetof(ft8gpu_apsoft_info, pad) == 5 && offsetof(ft8gpu_apsoft_info, results) == 8, "ft8gpu_apsoft_info layout");
+static_assert(sizeof(ft8gpu_demod_ap_params) == 100 && offsetof(ft8gpu_demod_ap_params, nhyp) == 12 &&
+              offsetof(ft8gpu_demod_ap_params, ap_max_hard_errors) == 16 && offsetof(ft8gpu_demod_ap_params, hyps) == 20,
+              "ft8gpu_demod_ap_params layout");
+#endif
 
 /* ---- 12 kHz audio: a resampler in front of the decoder ------------------------------------------------------------------------
  * (DESIGN.md "Audio front end"; not in the reference, whose frames come from the RTL-SDR front end or from .iq / .c2 files.)

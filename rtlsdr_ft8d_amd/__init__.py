@@ -99,6 +99,12 @@ DEMOD_INFO_DTYPE = np.dtype([("result", "u1"), ("set", "u1"), ("nhard", "u1"), (
                              ("psync", "<f4"), ("pad", "u1", (4,))])
 DEMOD_MAX_HARD_ERRORS = 174      # FT8GPU_DEMOD_MAX_HARD_ERRORS, the recommended gate
 DEMOD_SETS = 7                   # FT8GPU_DEMOD_SETS, the recommended mask of soft-bit sets
+# AP on the demodulated soft bits (ft8gpu_demod_soft, ft8gpu_ap_soft_candidates): soft [B][cap][3][SOFT_STRIDE] float32
+SOFT_STRIDE = 176                # FT8GPU_SOFT_STRIDE
+APSOFT_INFO_DTYPE = np.dtype([("result", "u1"), ("nhard", "u1"), ("hyp", "u1"), ("iters", "u1"), ("set", "u1"), ("pad", "u1", (3,)),
+                              ("results", "u1", (3, 4))])
+APSOFT_MAX_HARD_ERRORS = 174     # FT8GPU_APSOFT_MAX_HARD_ERRORS, the recommended gate
+assert APSOFT_INFO_DTYPE.itemsize == 20
 AUDIO_RATE = 12000               # FT8GPU_AUDIO_RATE
 AUDIO_NSAMPLES = 180000          # FT8GPU_AUDIO_NSAMPLES
 AUDIO_TAPS = 160                 # FT8GPU_AUDIO_TAPS
@@ -177,6 +183,11 @@ class DemodParams(C.Structure):
     _fields_ = [("sets", C.c_int32), ("max_hard_errors", C.c_int32), ("max_per_frame", C.c_int32)]
 
 
+class DemodApParams(C.Structure):
+    """ft8gpu_demod_ap_params: the demodulation's parameters, nhyp 0 (no AP) .. 4, ap_max_hard_errors 0..174, hyps[4]"""
+    _fields_ = [("demod", DemodParams), ("nhyp", C.c_int32), ("ap_max_hard_errors", C.c_int32), ("hyps", ApHypothesis * 4)]
+
+
 class Timings(C.Structure):
     _fields_ = [("waterfall_ms", C.c_float), ("sync_ms", C.c_float), ("heap_ms", C.c_float),
                 ("decode_ms", C.c_float), ("spots_ms", C.c_float), ("total_ms", C.c_float),
@@ -228,6 +239,7 @@ ABI_SYMBOLS = [
     "ft8gpu_subtract_messages", "ft8gpu_decode_messages_subtracted", "ft8gpu_subtract_twiddles",
     "ft8gpu_subtract_messages_shaped", "ft8gpu_decode_messages_subtracted_shaped",
     "ft8gpu_demod_candidates", "ft8gpu_decode_messages_demod",
+    "ft8gpu_demod_soft", "ft8gpu_ap_soft_candidates", "ft8gpu_decode_messages_demod_ap",
     "ft8gpu_audio_taps", "ft8gpu_audio_mixer", "ft8gpu_audio_frames", "ft8gpu_decode_audio", "ft8gpu_read_wav",
     "ft8gpu_gfsk_pulse", "ft8gpu_gfsk_ramp", "ft8gpu_gfsk_twiddles", "ft8gpu_synth_gfsk_frames", "ft8gpu_synth_gfsk_audio",
     "ft8gpu_write_wav",
@@ -408,6 +420,10 @@ def _declare(L):
     if hasattr(L, "ft8gpu_demod_candidates"):             # absent from older builds loaded by load_library_at
         L.ft8gpu_demod_candidates.argtypes = [vp, vp, vp, vp, vp, C.c_int, C.POINTER(DemodParams), vp, vp, C.c_int]
         L.ft8gpu_decode_messages_demod.argtypes = [vp, vp, C.c_int, C.POINTER(DemodParams), vp, vp, vp, C.c_int]
+    if hasattr(L, "ft8gpu_demod_soft"):                   # absent from older builds loaded by load_library_at
+        L.ft8gpu_demod_soft.argtypes = [vp, vp, vp, vp, vp, C.c_int, C.POINTER(DemodParams), vp, vp, vp, C.c_int]
+        L.ft8gpu_ap_soft_candidates.argtypes = [vp, vp, vp, vp, C.c_int, C.c_int, vp, C.c_int, C.c_int, vp, vp, C.c_int]
+        L.ft8gpu_decode_messages_demod_ap.argtypes = [vp, vp, C.c_int, C.POINTER(DemodApParams), vp, vp, vp, C.c_int]
     if hasattr(L, "ft8gpu_refine_messages"):              # absent from older builds loaded by load_library_at
         L.ft8gpu_refine_messages.argtypes = [vp, vp, vp, vp, C.c_int, vp, C.c_int]
         L.ft8gpu_decode_messages_refined.argtypes = [vp, vp, C.c_int, vp, vp, vp, C.c_int]
@@ -1303,6 +1319,83 @@ class Decoder:
         p = DemodParams(int(sets), int(max_hard_errors), int(max_per_frame))
         self._ck(self.lib.ft8gpu_decode_messages_demod(self.h, _ptr(iq_dev), int(nframes), C.byref(p), _ptr(msgs_dev), _ptr(n_msgs_dev),
                                                        None if n_by_stage_dev is None else _ptr(n_by_stage_dev), DEVICE_PTRS))
+
+    def demod_soft(self, iq, cands, counts, status_in, sets=DEMOD_SETS, max_hard_errors=DEMOD_MAX_HARD_ERRORS, max_per_frame=None,
+                   status_out=None, info=None, soft=None):
+        """ft8gpu_demod_soft -> (status_out, info as demod_candidates, soft [B][cap][3][176] float32: the normalised soft bits of
+        the sets bp_decode ran on, zero rows elsewhere), new arrays; records at and behind counts[f] keep what the arrays held"""
+        iq = np.ascontiguousarray(iq, np.float32).reshape(-1, 2, NSAMPLES)
+        B = iq.shape[0]
+        cands, counts, status_in, out, inf = self._cand_arrays(B, cands, counts, status_in, status_out, info, DEMOD_INFO_DTYPE)
+        shape = (B, self.max_candidates, 3, SOFT_STRIDE)
+        soft = np.zeros(shape, np.float32) if soft is None else np.array(soft, np.float32, copy=True, order="C").reshape(shape)
+        p = DemodParams(int(sets), int(max_hard_errors), int(self.max_candidates if max_per_frame is None else max_per_frame))
+        self._ck(self.lib.ft8gpu_demod_soft(self.h, iq.ctypes.data, cands.ctypes.data, counts.ctypes.data, status_in.ctypes.data,
+                                            B, C.byref(p), out.ctypes.data, inf.ctypes.data, soft.ctypes.data, HOST_PTRS))
+        return out.view(STATUS_DTYPE).reshape(B, self.max_candidates), inf, soft
+
+    def demod_soft_dev(self, iq_dev, cands_dev, counts_dev, status_in_dev, nframes, sets, max_hard_errors, max_per_frame,
+                       status_out_dev, info_dev, soft_dev):
+        """status_out_dev may be status_in_dev; iq_dev and soft_dev 16-byte aligned"""
+        p = DemodParams(int(sets), int(max_hard_errors), int(max_per_frame))
+        self._ck(self.lib.ft8gpu_demod_soft(self.h, _ptr(iq_dev), _ptr(cands_dev), _ptr(counts_dev), _ptr(status_in_dev), int(nframes),
+                                            C.byref(p), _ptr(status_out_dev), _ptr(info_dev), _ptr(soft_dev), DEVICE_PTRS))
+
+    def ap_soft_candidates(self, soft, counts, status_in, sets=DEMOD_SETS, hyps=("CQ ? ?",), max_hard_errors=APSOFT_MAX_HARD_ERRORS,
+                           status_out=None, info=None):
+        """ft8gpu_ap_soft_candidates -> (status_out [B][cap] STATUS_DTYPE, info [B][cap] APSOFT_INFO_DTYPE), new arrays; records
+        at and behind counts[f] keep what status_out / info held (zeros when None).  hyps: patterns or AP_HYP_DTYPE records"""
+        soft = np.ascontiguousarray(soft, np.float32).reshape(-1, self.max_candidates, 3, SOFT_STRIDE)
+        B = soft.shape[0]
+        counts = np.ascontiguousarray(counts, np.int32)
+        status_in = np.ascontiguousarray(status_in).view(np.uint8).reshape(B, self.max_candidates, 48)
+        assert counts.shape == (B,)
+        out = np.zeros((B, self.max_candidates, 48), np.uint8) if status_out is None else \
+            np.array(status_out, copy=True, order="C").view(np.uint8).reshape(B, self.max_candidates, 48)
+        inf = np.zeros((B, self.max_candidates), APSOFT_INFO_DTYPE) if info is None else \
+            np.array(info, copy=True, order="C").view(APSOFT_INFO_DTYPE).reshape(B, self.max_candidates)
+        hyps = _ap_hyps(hyps)
+        self._ck(self.lib.ft8gpu_ap_soft_candidates(self.h, soft.ctypes.data, counts.ctypes.data, status_in.ctypes.data, B, int(sets),
+                                                    hyps.ctypes.data, len(hyps), int(max_hard_errors), out.ctypes.data, inf.ctypes.data,
+                                                    HOST_PTRS))
+        return out.view(STATUS_DTYPE).reshape(B, self.max_candidates), inf
+
+    def ap_soft_candidates_dev(self, soft_dev, counts_dev, status_in_dev, nframes, sets, hyps, max_hard_errors, status_out_dev, info_dev):
+        """status_out_dev may be status_in_dev; soft_dev 16-byte aligned; info_dev: 20-byte records; hyps stay on the host"""
+        hyps = _ap_hyps(hyps)
+        self._ck(self.lib.ft8gpu_ap_soft_candidates(self.h, _ptr(soft_dev), _ptr(counts_dev), _ptr(status_in_dev), int(nframes), int(sets),
+                                                    hyps.ctypes.data, len(hyps), int(max_hard_errors), _ptr(status_out_dev),
+                                                    _ptr(info_dev), DEVICE_PTRS))
+
+    def _demod_ap_params(self, sets, max_hard_errors, max_per_frame, hyps, ap_max_hard_errors):
+        hyps = _ap_hyps(hyps)
+        p = DemodApParams(DemodParams(int(sets), int(max_hard_errors), int(self.max_candidates if max_per_frame is None else max_per_frame)),
+                          len(hyps), int(ap_max_hard_errors))
+        C.memmove(C.addressof(p.hyps), hyps.ctypes.data, min(hyps.nbytes, C.sizeof(p.hyps)))
+        return p
+
+    def decode_messages_demod_ap(self, iq, sets=DEMOD_SETS, max_hard_errors=DEMOD_MAX_HARD_ERRORS, max_per_frame=None,
+                                 hyps=("CQ ? ?",), ap_max_hard_errors=APSOFT_MAX_HARD_ERRORS, msgs=None):
+        """ft8gpu_decode_messages_demod_ap -> (msgs [B][50], n_msgs [B], n_by_stage [B][3]: the count after BP, after the second
+        demodulation and after AP on its soft bits); pad[1] = 1 + hypothesis and pad[3] = set on a record AP gained.  hyps = (): no AP"""
+        iq = np.ascontiguousarray(iq, np.float32).reshape(-1, 2, NSAMPLES)
+        B = iq.shape[0]
+        if msgs is None:
+            msgs = np.zeros((B, MAX_MESSAGES), MESSAGE_DTYPE)
+        assert msgs.dtype == MESSAGE_DTYPE and msgs.shape == (B, MAX_MESSAGES) and msgs.flags["C_CONTIGUOUS"]
+        n = np.zeros(B, np.int32)
+        nbs = np.zeros((B, 3), np.int32)
+        p = self._demod_ap_params(sets, max_hard_errors, max_per_frame, hyps, ap_max_hard_errors)
+        self._ck(self.lib.ft8gpu_decode_messages_demod_ap(self.h, iq.ctypes.data, B, C.byref(p), msgs.ctypes.data, n.ctypes.data,
+                                                          nbs.ctypes.data, HOST_PTRS))
+        return msgs, n, nbs
+
+    def decode_messages_demod_ap_dev(self, iq_dev, nframes, sets, max_hard_errors, max_per_frame, hyps, ap_max_hard_errors, msgs_dev,
+                                     n_msgs_dev, n_by_stage_dev=None):
+        """the same with every array in HBM (iq and msgs 16-byte aligned); n_by_stage_dev: [nframes][3] or None"""
+        p = self._demod_ap_params(sets, max_hard_errors, max_per_frame, hyps, ap_max_hard_errors)
+        self._ck(self.lib.ft8gpu_decode_messages_demod_ap(self.h, _ptr(iq_dev), int(nframes), C.byref(p), _ptr(msgs_dev), _ptr(n_msgs_dev),
+                                                          None if n_by_stage_dev is None else _ptr(n_by_stage_dev), DEVICE_PTRS))
 
     # ---- device-pointer API (inputs and outputs resident in HBM) --------------------------------
     def refine_messages(self, iq, msgs, n_msgs, refined=None):

@@ -17,6 +17,8 @@ int ensure_ap_buffers(ft8gpu_ctx *c) {
 
 int popcount8(unsigned v) { int n = 0; for (; v; v &= v - 1) ++n; return n; }
 
+}  // namespace
+
 int check_ap_args(const ft8gpu_ap_hypothesis *hyps, int nhyp, int max_hard_errors) {
     if (nhyp < 1 || nhyp > FT8GPU_AP_MAX_HYPOTHESES) return ft8_fail("nhyp %d out of range [1, %d]", nhyp, FT8GPU_AP_MAX_HYPOTHESES);
     if (max_hard_errors < 0 || max_hard_errors > kApMaxHard)
@@ -33,6 +35,8 @@ int check_ap_args(const ft8gpu_ap_hypothesis *hyps, int nhyp, int max_hard_error
     }
     return 0;
 }
+
+namespace {
 
 // AP on a pass's failures, in place, then the append step and the tags of what it gained; its count goes to column col
 int ap_step(const Chunk &k, const PassSet &f, int col, const ft8gpu_ap_params *q) {

@@ -1,5 +1,5 @@
 // cand_dev.h -- device code of the one-wave-per-candidate kernels, kept once: the LDPC kernel (decode.hip) and the kernels
-// that give its failures a second chance (osd.hip, ap.hip, match.hip, combine.hip, demod.hip).  Wave helpers, the soft bits
+// that give its failures a second chance (osd.hip, ap.hip, match.hip, combine.hip, demod.hip, apsoft.hip).  Wave helpers, the soft bits
 // of a candidate and their renormalisation in index order, the BP iteration in its counting form, the judgement and the
 // record of a success, and the LDPC tables with their host-side builder and upload.  For the five second-chance kernels also
 // what surrounds those: the head of the kernel (which candidate a wave has, and whether it is left alone), the launch
@@ -213,6 +213,38 @@ __device__ __forceinline__ bool renormalise_in_order(const float *llr, const boo
     }
     if (!__all(finite)) return false;
     if (!__all(gk >= kGuardMinSoft)) ieee = 1;        // a soft bit outside the set sends every iteration to the IEEE form
+    return true;
+}
+
+// A row of normalised soft bits another stage left in global memory (demod.hip's soft array, FT8GPU_SOFT_STRIDE floats a row:
+// apsoft.hip): the 174 values go to llr[0 .. 173] of the wave's LDS, stores published, and lane l gets row[l + 64 r] into cw[r]
+// (0 where !has[r]; elements 174 and 175 are not read).  Nothing is normalised again.  Returns whether the row is usable
+// (wave-uniform): every value finite and apmag = max |row[i]| != 0.  The values are arbitrary finite floats, so the division
+// guard is evaluated here, ahead of iteration 0, exactly as renormalise_in_order does: ieee is set where a value is neither 0
+// nor >= 2^-58 in magnitude.  apmag is one of the row's own magnitudes, so values forced to +-apmag stay inside the set.
+// (The copy in llr is for stages that read soft bits from LDS, as OSD and match do; the only caller so far, apsoft.hip, works
+// from cw and composes its record over llr, so there the stores and the sync behind them serve nobody yet.)
+__device__ __forceinline__ bool load_soft_row(const float *__restrict__ row, float *llr, const bool (&has)[3], int lane,
+                                              float (&cw)[3], float &apmag, int &ieee) {
+    bool finite = true;
+    uint32_t gk = 0xFFFFFFFFu, amax = 0u;
+#pragma unroll
+    for (int r = 0; r < 3; ++r) {
+        cw[r] = 0.0f;
+        if (has[r]) {
+            cw[r] = row[lane + 64 * r];
+            llr[lane + 64 * r] = cw[r];
+        }
+        const uint32_t a = __float_as_uint(cw[r]) & 0x7FFFFFFFu;
+        finite = finite && (a & 0x7F800000u) != 0x7F800000u;
+        amax = max(amax, a);
+        gk = min(gk, guard_key(cw[r]));
+    }
+    wave_lds_sync();
+    if (!__all(finite)) return false;
+    apmag = __uint_as_float(wave_max(amax));                          // non-negative floats order as their bit patterns
+    if (apmag == 0.0f) return false;
+    if (!__all(gk >= kGuardMinSoft)) ieee = 1;
     return true;
 }
 

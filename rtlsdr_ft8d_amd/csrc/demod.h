@@ -8,8 +8,10 @@
 hipError_t demod_tables_init(hipStream_t s);
 // iq [nframes][2][48000], cands / status_in / status_out / info [nframes][max_candidates], counts [nframes]; tab: the subtraction's
 // tables (w4).  status_out may be status_in.  Two launches: the marks of the attempted candidates, then the stage.
+// soft: nullptr, or [nframes][max_candidates][3][FT8GPU_SOFT_STRIDE] (16-byte aligned) for the kernel that also writes the
+// normalised soft bits of the sets it tried (ft8gpu_demod_soft).
 hipError_t launch_demod(const float *iq, const ft8gpu_candidate *cands, const int32_t *counts, const ft8gpu_decode_status *status_in,
-                        ft8gpu_decode_status *status_out, ft8gpu_demod_info *info, int nframes, int max_candidates,
+                        ft8gpu_decode_status *status_out, ft8gpu_demod_info *info, float *soft, int nframes, int max_candidates,
                         const SubTables *tab, int sets, int max_hard_errors, int max_per_frame, int ldpc_iters, int force_ieee_div,
                         hipStream_t s);
 // pad[3] = info[cand_index].set for the records [n_before[f], n_msgs[f]) of nframes frames

@@ -25,6 +25,9 @@
 //       maxima are taken on the bit patterns (the magnitudes are non-negative), so their order does not matter.
 //     normalisation in index order by every lane alike with the guard ahead of iteration 0, bp_decode, the judgement with the
 //       CRC and the record: cand_dev.h's code, as for combine.hip.
+//   ft8_demod_soft_kernel     the same body (demod_body, a template on "emits") that also writes x, the normalised soft bits
+//                             bp_decode ran on, of every set it reached into soft [frame][candidate][3][176], and zero rows
+//                             for everything else below the count: what apsoft.hip (AP on these soft bits) reads.
 //   launch_demod_tag          pad[3] of the records the append step added = the accepted set (cand_dev.h's tag kernel).
 //
 // LDS: 9 152 bytes per wave (the BP tile and the soft bits of cand_dev.h, 3 456, and Z, 5 696), 36 608 per workgroup.  No
@@ -222,15 +225,35 @@ void ft8_demod_select_kernel(const int32_t *__restrict__ counts, const ft8gpu_de
     }
 }
 
-__global__ __launch_bounds__(256)
-void ft8_demod_kernel(const float *__restrict__ iq, const ft8gpu_candidate *__restrict__ cands, const int32_t *__restrict__ counts,
-                      const ft8gpu_decode_status *status_in, ft8gpu_decode_status *status_out, ft8gpu_demod_info *info, int nframes,
-                      int max_candidates, const SubTables *__restrict__ tab, int sets, int max_hard_errors, int max_iters,
-                      int force_ieee_div, unsigned blocks_per_frame) {
-    __shared__ __attribute__((aligned(16))) float s_mem[4][kDemodLds];
+// Row n - 1 of a candidate's soft[3][FT8GPU_SOFT_STRIDE]: lane l stores the values l + 64 r it owns (elements 174 and 175 are
+// +0 in cw[2] already), or 176 times +0.
+constexpr int kSoftStride = FT8GPU_SOFT_STRIDE;
+static_assert(kSoftStride == 176 && kSoftStride >= kLdpcN && kSoftStride % 4 == 0, "soft rows");
+__device__ __forceinline__ void emit_row(float *rows, int n, const float (&cw)[3], int lane) {
+    float *row = rows + (n - 1) * kSoftStride;
+    row[lane] = cw[0];
+    row[lane + 64] = cw[1];
+    if (lane + 128 < kSoftStride) row[lane + 128] = cw[2];
+}
+__device__ __forceinline__ void zero_row(float *rows, int n, int lane) {
+    if (lane < kSoftStride / 4) reinterpret_cast<float4 *>(rows + (n - 1) * kSoftStride)[lane] = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+}
 
+// The body of both kernels, written once.  kEmit: the normalised soft bits of every set BP ran on go to soft (the rule is in
+// include/ft8gpu.h at ft8gpu_demod_soft); nothing else differs, and without it soft is not touched.
+template <bool kEmit>
+__device__ __forceinline__ void demod_body(float (*s_mem)[kDemodLds], const float *__restrict__ iq,
+                                           const ft8gpu_candidate *__restrict__ cands, const int32_t *__restrict__ counts,
+                                           const ft8gpu_decode_status *status_in, ft8gpu_decode_status *status_out,
+                                           ft8gpu_demod_info *info, float *soft, int nframes, int max_candidates,
+                                           const SubTables *__restrict__ tab, int sets, int max_hard_errors, int max_iters,
+                                           int force_ieee_div, unsigned blocks_per_frame) {
     // not marked by the select kernel: not attempted, the record copied, the four dwords of the info record zero
     const CandWave w = cand_prologue(blockIdx.x, blocks_per_frame, 0u, counts, status_in, status_out, info, nframes, max_candidates, true);
+    if (kEmit && w.verdict == kCandLeft) {                            // its three rows are zero (a gone wave writes nothing)
+        float *rows = soft + w.rec_index * (3 * kSoftStride);
+        for (int n = 1; n <= 3; ++n) zero_row(rows, n, w.lane);
+    }
     if (w.verdict != kCandRun) return;
     const int lane = w.lane, frame = w.frame;
     const size_t rec_index = w.rec_index;
@@ -328,10 +351,14 @@ void ft8_demod_kernel(const float *__restrict__ iq, const ft8gpu_candidate *__re
     const bool has[3] = { true, true, lane + 128 < kLdpcN };
     const uint64_t has2_mask = __ballot(has[2]);
     uint32_t *rec32 = reinterpret_cast<uint32_t *>(llr);              // the record is composed where the soft bits were
+    float *rows = kEmit ? soft + rec_index * (3 * kSoftStride) : nullptr;
     int result = 0, nhard = 0, set = 0;
 #pragma unroll 1
     for (int n = 1; n <= 3; ++n) {
-        if (((sets >> (n - 1)) & 1) == 0) continue;                   // wave-uniform
+        if (((sets >> (n - 1)) & 1) == 0) {                           // wave-uniform
+            if (kEmit) zero_row(rows, n, lane);
+            continue;
+        }
         set = n;
         nhard = 0;
         wave_lds_sync();                                              // the last set's reads of llr are done
@@ -339,19 +366,25 @@ void ft8_demod_kernel(const float *__restrict__ iq, const ft8gpu_candidate *__re
         wave_lds_sync();
         if (!finite_mag) {
             result = 6;
+            if (kEmit) zero_row(rows, n, lane);
             continue;
         }
         float cw[3];
         int ieee = force_ieee_div ? 1 : 0;                            // and the guard ahead of iteration 0 (cand_dev.h)
         if (!renormalise_in_order(llr, has, lane, cw, ieee)) {        // wave-uniform: BP does not run
             result = 6;
+            if (kEmit) zero_row(rows, n, lane);
             continue;
         }
+        if (kEmit) emit_row(rows, n, cw, lane);                       // x as bp_decode gets it
         const uint64_t X0 = __ballot(cw[0] > 0.0f), X1 = __ballot(cw[1] > 0.0f), X2 = __ballot(cw[2] > 0.0f);
 
         const BpWord bp = bp_decode_counting(cw, has, has2_mask, toc, ldpc_lane(d_ldpc, lane), lane, max_iters, ieee);
         result = judge_bp_word(bp, X0, X1, X2, max_hard_errors, dw0, d_ldpc.crc_bit, rec32, lane, nhard);
-        if (result == 1) break;
+        if (result == 1) {
+            if (kEmit) for (int m = n + 1; m <= 3; ++m) zero_row(rows, m, lane);   // the sets not reached
+            break;
+        }
     }
     store_record(out32, in32, rec32, mine, result == 1, lane);
     if (lane < 4) {
@@ -363,6 +396,27 @@ void ft8_demod_kernel(const float *__restrict__ iq, const ft8gpu_candidate *__re
     }
 }
 
+__global__ __launch_bounds__(256)
+void ft8_demod_kernel(const float *__restrict__ iq, const ft8gpu_candidate *__restrict__ cands, const int32_t *__restrict__ counts,
+                      const ft8gpu_decode_status *status_in, ft8gpu_decode_status *status_out, ft8gpu_demod_info *info, int nframes,
+                      int max_candidates, const SubTables *__restrict__ tab, int sets, int max_hard_errors, int max_iters,
+                      int force_ieee_div, unsigned blocks_per_frame) {
+    __shared__ __attribute__((aligned(16))) float s_mem[4][kDemodLds];
+    demod_body<false>(s_mem, iq, cands, counts, status_in, status_out, info, nullptr, nframes, max_candidates, tab, sets,
+                      max_hard_errors, max_iters, force_ieee_div, blocks_per_frame);
+}
+
+// the same with the soft bits of the sets written out: soft [nframes][max_candidates][3][FT8GPU_SOFT_STRIDE]
+__global__ __launch_bounds__(256)
+void ft8_demod_soft_kernel(const float *__restrict__ iq, const ft8gpu_candidate *__restrict__ cands, const int32_t *__restrict__ counts,
+                           const ft8gpu_decode_status *status_in, ft8gpu_decode_status *status_out, ft8gpu_demod_info *info,
+                           float *soft, int nframes, int max_candidates, const SubTables *__restrict__ tab, int sets,
+                           int max_hard_errors, int max_iters, int force_ieee_div, unsigned blocks_per_frame) {
+    __shared__ __attribute__((aligned(16))) float s_mem[4][kDemodLds];
+    demod_body<true>(s_mem, iq, cands, counts, status_in, status_out, info, soft, nframes, max_candidates, tab, sets,
+                     max_hard_errors, max_iters, force_ieee_div, blocks_per_frame);
+}
+
 }  // namespace
 
 hipError_t demod_tables_init(hipStream_t s) {
@@ -370,7 +424,7 @@ hipError_t demod_tables_init(hipStream_t s) {
 }
 
 hipError_t launch_demod(const float *iq, const ft8gpu_candidate *cands, const int32_t *counts, const ft8gpu_decode_status *status_in,
-                        ft8gpu_decode_status *status_out, ft8gpu_demod_info *info, int nframes, int max_candidates,
+                        ft8gpu_decode_status *status_out, ft8gpu_demod_info *info, float *soft, int nframes, int max_candidates,
                         const SubTables *tab, int sets, int max_hard_errors, int max_per_frame, int ldpc_iters, int force_ieee_div,
                         hipStream_t s) {
     if (nframes < 1) return hipSuccess;
@@ -378,8 +432,12 @@ hipError_t launch_demod(const float *iq, const ft8gpu_candidate *cands, const in
     if (cand_grid(nframes, max_candidates, g) != hipSuccess) return hipErrorInvalidValue;
     hipLaunchKernelGGL(ft8_demod_select_kernel, dim3((unsigned)nframes), dim3(64), 0, s, counts, status_in, info, max_candidates,
                        max_per_frame);
-    hipLaunchKernelGGL(ft8_demod_kernel, dim3(g.nblocks), dim3(256), 0, s, iq, cands, counts, status_in, status_out, info,
-                       nframes, max_candidates, tab, sets, max_hard_errors, ldpc_iters, force_ieee_div, g.bpf);
+    if (soft)
+        hipLaunchKernelGGL(ft8_demod_soft_kernel, dim3(g.nblocks), dim3(256), 0, s, iq, cands, counts, status_in, status_out, info, soft,
+                           nframes, max_candidates, tab, sets, max_hard_errors, ldpc_iters, force_ieee_div, g.bpf);
+    else
+        hipLaunchKernelGGL(ft8_demod_kernel, dim3(g.nblocks), dim3(256), 0, s, iq, cands, counts, status_in, status_out, info,
+                           nframes, max_candidates, tab, sets, max_hard_errors, ldpc_iters, force_ieee_div, g.bpf);
     return hipGetLastError();
 }
 

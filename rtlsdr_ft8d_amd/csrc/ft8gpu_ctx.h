@@ -88,6 +88,9 @@ struct ft8gpu_ctx {
     bool combine_tables = false;           // soft-bit memory: the constant tables are uploaded (on its first call)
     bool demod_tables = false;             // demodulation from the I/Q samples: likewise
     bool hint_tables = false;              // call hints: likewise
+    bool apsoft_tables = false;            // AP on the demodulated soft bits: likewise, and lazily on the first call that needs it
+    float *d_soft = nullptr;               //   a chunk's soft-bit array [max_frames][max_candidates][3][176] (grown as needed)
+    size_t soft_cap = 0;
     struct SubTables *d_subtab = nullptr;  // subtraction in the I/Q samples, lazily on its first call: the constant tables,
     uint32_t *d_sub_scratch = nullptr;     //   what the estimate kernel leaves for the apply kernel [sub_frames][50][2560],
     int sub_frames = 0;
@@ -285,6 +288,8 @@ int decode_messages_masked(ft8gpu_ctx *c, const float *iq, int nframes, int pass
 int ensure_osd_buffers(ft8gpu_ctx *c);
 int check_osd_args(int order, int max_hard_errors);
 int osd_step(const Chunk &k, const PassSet &f, int col, int order, int max_hard_errors);
+// api_ap.hip: refuses hypotheses and gates out of range, with the error text set (also for AP on the demodulated soft bits)
+int check_ap_args(const ft8gpu_ap_hypothesis *hyps, int nhyp, int max_hard_errors);
 // api_match.hip: the slot-major whole path behind ft8gpu_decode_messages_expected / _combined
 int decode_messages_slot_major(ft8gpu_ctx *c, const float *iq, int nstreams, int nslots, void *state, size_t state_bytes,
                                ft8gpu_message *msgs, int32_t *n_msgs, int32_t *n_by_stage, int flags, const SlotStages &slot);

@@ -4,7 +4,9 @@ percent, so only arms that share a box and a session are comparable.  Every arm 
 interleaved round by round; the records of all arms must be byte-identical.
   python tools/ab_libs.py --libs tools/ab/libft8gpu_prev.so rtlsdr_ft8d_amd/libft8gpu.so [--config 2|4] [--rounds 3] [--entry batch|messages]
 --entry messages times ft8gpu_decode_messages (64-byte records of every message) instead of ft8gpu_decode_batch; --entry
-subtracted times ft8gpu_decode_messages_subtracted at three passes (records, counts and the counts by pass in the digest)."""
+subtracted times ft8gpu_decode_messages_subtracted at three passes (records, counts and the counts by pass in the digest);
+--entry demod / demod_stage time ft8gpu_decode_messages_demod / ft8gpu_demod_candidates at 48 candidates per frame (the counts by
+stage, or the status and info records, in the digest).  A library may be named more than once (parent this this parent)."""
 import argparse
 import hashlib
 import json
@@ -23,7 +25,7 @@ def main():
     ap.add_argument("--config", type=int, default=2, choices=(2, 4))
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--rounds", type=int, default=3)
-    ap.add_argument("--entry", choices=("batch", "messages", "subtracted"), default="batch")
+    ap.add_argument("--entry", choices=("batch", "messages", "subtracted", "demod", "demod_stage"), default="batch")
     ap.add_argument("--torch-stream", action="store_true", help="run every arm on a torch.cuda.Stream (as bench.py does) instead of the context's own stream")
     args = ap.parse_args()
     import torch
@@ -47,8 +49,26 @@ def main():
     torch.cuda.synchronize()
     res = [{"lib": p, "ms": [], "stages": None, "digest": None} for p in args.libs]
     nbp = torch.zeros((B, 3), dtype=torch.int32, device="cuda")
+    extra = []                                # further outputs that go into the digest
+    if args.entry in ("demod", "demod_stage"):
+        # the demodulation from the I/Q samples at its recommended values, 48 candidates per frame: the whole path, or the stage
+        # alone on the first arm's BP status records
+        maxc = cfg["maxc"]
+        if args.entry == "demod_stage":
+            u8 = lambda n: torch.zeros((n,), dtype=torch.uint8, device="cuda")
+            mag, cands, status, status2, info = u8(B * ft8.MAG_ARRAY), u8(B * maxc * 8), u8(B * maxc * 48), u8(B * maxc * 48), u8(B * maxc * 16)
+            decs[0].waterfall_dev(iq, B, mag)
+            decs[0].find_sync_dev(mag, B, cands, nres)
+            decs[0].decode_candidates_dev(mag, cands, nres, B, status)
+            decs[0].synchronize()
+            extra = [status2, info]
+        else:
+            extra = [torch.zeros((B, 2), dtype=torch.int32, device="cuda")]
     run = {"batch": lambda d: d.decode_batch_dev(iq, B, spots, nres), "messages": lambda d: d.decode_messages_dev(iq, B, spots, nres),
-           "subtracted": lambda d: d.decode_messages_subtracted_dev(iq, B, 3, spots, nres, nbp)}[args.entry]
+           "subtracted": lambda d: d.decode_messages_subtracted_dev(iq, B, 3, spots, nres, nbp),
+           "demod": lambda d: d.decode_messages_demod_dev(iq, B, ft8.DEMOD_SETS, ft8.DEMOD_MAX_HARD_ERRORS, 48, spots, nres, extra[0]),
+           "demod_stage": lambda d: d.demod_candidates_dev(iq, cands, nres, status, B, ft8.DEMOD_SETS, ft8.DEMOD_MAX_HARD_ERRORS, 48,
+                                                           status2, info)}[args.entry]
     for _ in range(args.rounds):
         for dec, r in zip(decs, res):
             for _ in range(3):
@@ -61,11 +81,13 @@ def main():
             r.setdefault("host_enqueue_ms", []).append(round(1e3 * (time.perf_counter() - t0) / args.steps, 4))
             dec.synchronize()
             r["ms"].append(round(1e3 * (time.perf_counter() - t0) / args.steps, 4))
-            st = dec.timings()
+            if args.entry != "demod_stage":                            # a stage entry records no pipeline run
+                st = dec.timings()
+                r["stages"] = {k: round(v, 4) for k, v in st.items() if k.endswith("_ms")}
             dec.enable_timing(False)
-            r["stages"] = {k: round(v, 4) for k, v in st.items() if k.endswith("_ms")}
             r["digest"] = hashlib.sha256(spots.cpu().numpy().tobytes() + nres.cpu().numpy().tobytes() +
-                                         (nbp.cpu().numpy().tobytes() if args.entry == "subtracted" else b"")).hexdigest()[:16]
+                                         (nbp.cpu().numpy().tobytes() if args.entry == "subtracted" else b"") +
+                                         b"".join(t.cpu().numpy().tobytes() for t in extra)).hexdigest()[:16]
     for r in res:
         r["best_ms"] = min(r["ms"])
     out = {"frames": B, "config": args.config, "entry": args.entry, "steps": args.steps, "arms": res,

@@ -12,6 +12,7 @@ On the GPU (the default) the frames come from ft8gpu_synth_gfsk_frames_faded (no
   bp        ft8gpu_decode_messages
   deep      ft8gpu_decode_messages_ap with the hypothesis "CQ ? ?" and OSD of order 1 (the deep path: AP + OSD)
   demod     ft8gpu_decode_messages_demod at the recommended gate and mask
+  demod_ap  ft8gpu_decode_messages_demod_ap: the same, then AP under "CQ ? ?" on the demodulated soft bits at its recommended gate
 and the crowd frames (20 stations, all at the point's SNR, 70 Hz apart) through
   subtract_cpfsk, subtract_gfsk   ft8gpu_decode_messages_subtracted_shaped, three passes: planted messages after each pass.
 A station counts as decoded when its text is among the frame's records.  --cpu: the restated rule (tests/ft8_spec_channel.py) with
@@ -94,18 +95,22 @@ def run_gpu(a):
 
         for name in a.channels:
             t0 = time.time()
-            curves = {"bp": [], "deep": [], "demod": []}
+            curves = {"bp": [], "deep": [], "demod": [], "demod_ap": []}
             crowd = {"subtract_cpfsk": [], "subtract_gfsk": []}
             for k, snr in enumerate(snrs):
                 sig, want = single_signals(ft8, workload, F, snr)
                 dec.synth_gfsk_frames_faded_dev(sig, channels_of(ft8, name, sig.shape), F, 1, 1.0, SEED + k, 0, 0.5, iq)
                 stages = {"bp": lambda: dec.decode_messages_dev(iq, F, msgs, n),
                           "deep": lambda: dec.decode_messages_ap_dev(iq, F, 1, ("CQ ? ?",), ft8.AP_MAX_HARD_ERRORS, 1, ft8.OSD_MAX_HARD_ERRORS, msgs, n),
-                          "demod": lambda: dec.decode_messages_demod_dev(iq, F, ft8.DEMOD_SETS, ft8.DEMOD_MAX_HARD_ERRORS, 120, msgs, n)}
+                          "demod": lambda: dec.decode_messages_demod_dev(iq, F, ft8.DEMOD_SETS, ft8.DEMOD_MAX_HARD_ERRORS, 120, msgs, n),
+                          "demod_ap": lambda: dec.decode_messages_demod_ap_dev(iq, F, ft8.DEMOD_SETS, ft8.DEMOD_MAX_HARD_ERRORS, 120, ("CQ ? ?",),
+                                                                               ft8.APSOFT_MAX_HARD_ERRORS, msgs, n)}
                 for stage, run in stages.items():
                     run()
                     got = texts_of(*fetch(F))
                     curves[stage].append(sum(want[f] in got[f] for f in range(F)))
+                if FC < 1:                                            # --crowd-frames 0: the single-station rows only
+                    continue
                 sig, wantc = crowd_signals(ft8, workload, FC, snr)
                 dec.synth_gfsk_frames_faded_dev(sig, channels_of(ft8, name, sig.shape), FC, NCROWD, 1.0, SEED + 100 + k, 0, 0.5, iq)
                 for stage, shape in (("subtract_cpfsk", ft8.SUBTRACT_CPFSK), ("subtract_gfsk", ft8.SUBTRACT_GFSK)):
